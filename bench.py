@@ -10,7 +10,13 @@ impulsively, as the reference does; the first step (full assembly) and --spinup 
 "timing uses steps after a fixed warm-up") prepare the state, then come W warm-up steps and exactly K timed steps (default
 K = 100 on one GPU; under a launcher K = 30 behind 10 preparation steps).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--level L] [--ranks R] [--numbering first_touch|preordered] [--ranks-input Q]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR] [--level L] [--ranks R] [--numbering first_touch|preordered] [--ranks-input Q]
+
+A plain run measures the headline and nothing else: it sets up, prepares the state, warms up, times the K steps and prints the line.
+Everything the line carries beside the headline is measured with --full only: the hoisted twin (value_hoisted), the per-kernel
+HIP-event pass (kernels, roofline), the live rocprofv3 --pmc passes, the CPU baseline (cpu_baseline), the self_p2p twin of --comm
+rccl1 and the strong_10M leg of N > 1.  --dump-outputs DIR writes what the timed path computed in its last step -- the solution vector
+a caller receives, velocity.npy and pressure.npy (float64, the caller's numbering) -- so that two builds can be compared output for output.
 
 What the caller hands over (default): deal.II's OWN numbering -- first-touch order of distribute_dofs + component_wise on Q ranks
 per GPU (Q = 1: the serial reference, reference NavierStokes3D.cpp:16-19,58-69) -- and libnsx lays the nodes out behind the C-ABI
@@ -21,7 +27,7 @@ N > 1: one process per GPU under torch.distributed.run (the driver's launch line
 that launcher starts it as a child process.  ONE mesh is partitioned over the N GPUs (owned rows + ghost layers per
 rank, RCCL halo exchange of ghost DoFs inside every SpMV, RCCL all-reduce of every dot product, per-rank ILU(0) exactly
 as the reference's MPI run).  `value` is ALWAYS plain time-steps/s of the 1 089 643-DoF mesh of the N = 1 line ("scaling":
-"strong": value(N) / value(1) is the speed-up of that mesh).  The same invocation also partitions the 10 644 763-DoF mesh
+"strong": value(N) / value(1) is the speed-up of that mesh).  With --full the same invocation also partitions the 10 644 763-DoF mesh
 (level 16, BASELINE.json configs[3]) over the N GPUs and reports it under "strong_10M" beside its committed one-GPU base
 (profiles/r04_strong_10M_one_gpu.json): the >= 6x of SURVEY 8(d) is read from that entry.  A rank that fails in the headline run
 makes the whole job exit non-zero; the strong_10M leg runs after the headline is measured, under a deadline, and a failure there is
@@ -30,7 +36,7 @@ reported inside "strong_10M" instead of discarding the measured line.
 Other modes (not the driver's): --comm rccl1 (one GPU, 1-rank RCCL communicator: the distributed code path -- one launch + one
 ncclAllReduce per reduction -- timed on one card), --cpu-only (the cpu_baseline leg alone), --layout-table FILE (iteration counts
 and step times of the layouts a caller can hand over; its committed result is embedded in every bench line as
-"preconditioner_layouts").  Prints ONE JSON line on rank 0.
+"preconditioner_layouts").  Prints ONE JSON line on rank 0; "ms_per_step" is the time of one timed step.
 """
 import argparse
 import json
@@ -509,6 +515,37 @@ def committed_big_base():
         return None
 
 
+DUMP_LIMIT_BYTES = 60 * 10 ** 6  # --dump-outputs: the .npy files together stay below 64 MB (headers included)
+
+
+def dump_outputs(out_dir, n_u, x, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: what a caller of the timed path receives after its last step, the solution vector (the caller's numbering),
+    as out_dir/velocity.npy and out_dir/pressure.npy in float64.  Above `limit` bytes in all, each holds a fixed, seeded sample of
+    its entries (in index order) instead, the same sample for the same sizes in every run."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    x = np.asarray(x, dtype=np.float64)
+    parts = {"velocity": x[:n_u], "pressure": x[n_u:]}
+    total = sum(a.nbytes for a in parts.values())
+    for name, a in parts.items():
+        if total > limit:
+            keep = len(a) * limit // total
+            a = a[np.sort(np.random.default_rng(0).choice(len(a), keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def extras(args, world):
+    """What this invocation measures beside the headline.  A plain run measures nothing else; --full adds what the line carries
+    beside it (the explicit --cpu-only mode runs its CPU leg in any case)."""
+    full = args.full and not args.cpu_only and not args.layout_table
+    return {"cpu_baseline": world == 1 and (args.cpu_only or (full and not args.no_cpu)),
+            "pmc_live": full and world == 1 and args.pmc == "auto" and not args.no_cpu,
+            "hoisted_twin": full and world == 1 and args.level is None,
+            "profile_steps": args.profile_steps if full else 0,
+            "self_p2p": full and world == 1 and args.comm == "rccl1" and "NSX_EXT_SELF_P2P" not in os.environ,
+            "strong_10M": full and world > 1 and args.level is None and not args.no_big}
+
+
 def summarise_kernels(table, prof_stats):
     n_prof = max(1, len(prof_stats))
     kernels = {}
@@ -558,9 +595,15 @@ def main():
     ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
     ap.add_argument("--cpu-only", action="store_true", help="only the cpu_baseline leg (after a short GPU run that provides its state)")
     ap.add_argument("--layout-table", metavar="FILE", help="write the preconditioner-layout table to FILE and exit")
-    ap.add_argument("--profile-steps", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the line carries beside the headline: the hoisted twin, the per-kernel HIP-event pass and roofline, "
+                         "the live rocprofv3 --pmc passes, the CPU baseline, the self_p2p twin of --comm rccl1 and the strong_10M leg of N > 1 "
+                         "(a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the solution of the last timed step to DIR/velocity.npy and DIR/pressure.npy (float64)")
+    ap.add_argument("--profile-steps", type=int, default=5, help="with --full: steps of the per-kernel HIP-event pass")
     ap.add_argument("--pmc", choices=("auto", "off"), default="auto",
-                    help="auto: on one GPU with the cpu_baseline leg, measure roofline.traffic in two child runs under rocprofv3 --pmc "
+                    help="auto: with --full on one GPU with the cpu_baseline leg, measure roofline.traffic in two child runs under rocprofv3 --pmc "
                          "(FETCH_SIZE, WRITE_SIZE; ~1 min each); off: quote the committed profile")
     args = ap.parse_args()
     if os.environ.get("NSX_BENCH_HANG_DUMP"):  # development: where is every rank after that many seconds?
@@ -590,8 +633,9 @@ def main():
     def emit(obj):
         os.write(json_fd, (json.dumps(obj) + "\n").encode())
 
+    extra = extras(args, world)
     live_pmc, pmc_outcome = None, {"status": "skipped", "why": "not requested for this invocation"}
-    if args.pmc == "auto" and world == 1 and not args.no_cpu and not args.cpu_only and not args.layout_table:
+    if extra["pmc_live"]:
         tail = ["--ranks", str(args.ranks), "--schur-blocks", str(args.schur_blocks), "--ordering", args.ordering, "--balance", args.balance,
                 "--numbering", args.numbering, "--ranks-input", str(args.ranks_input), "--comm", args.comm]
         live_pmc, pmc_outcome = pmc_live(tail + (["--level", str(args.level)] if args.level is not None else []))
@@ -643,12 +687,14 @@ def main():
     level = args.level if args.level is not None else BASE_LEVEL
     steps, warmup = (args.steps, args.warmup) if not args.cpu_only else (2, 1)
     # ---- the headline: ONE mesh (1 089 643 DoF unless --level says otherwise) on N GPUs, plain time-steps/s
-    elapsed, stats, table, prof_stats, state, dofs = partitioned_run(level, steps, warmup, args.spinup, 0 if args.cpu_only else args.profile_steps,
-                                                                     want_state=(world == 1 and not args.no_cpu), twin=(world == 1 and not args.cpu_only and args.level is None))
+    elapsed, stats, table, prof_stats, state, dofs = partitioned_run(level, steps, warmup, args.spinup, extra["profile_steps"],
+                                                                     want_state=extra["cpu_baseline"] or bool(args.dump_outputs), twin=extra["hoisted_twin"])
     value = steps / elapsed
-    run_big = world > 1 and args.level is None and not args.no_big
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dofs.n_u, state[0])  # the state right behind the last timed step (before any --full leg)
+    run_big = extra["strong_10M"]
     self_p2p = None
-    if args.comm == "rccl1" and world == 1 and not args.cpu_only and "NSX_EXT_SELF_P2P" not in os.environ:
+    if extra["self_p2p"]:
         # a 1-rank ncclAllReduce launches no kernel: the same run once more with a self-addressed ncclSend / ncclRecv pair -- a real launch of
         # RCCL's device kernel -- in front of EVERY all-reduce, those inside the persistent sweep included (csrc/nsx_comm.hip)
         os.environ["NSX_EXT_SELF_P2P"] = "2"
@@ -805,10 +851,11 @@ def main():
         "roofline": roof,
         "pmc_live": pmc_outcome,
         "kernels": {k: {kk: (round(vv, 4) if isinstance(vv, float) else vv) for kk, vv in v.items()} for k, v in kernels.items()},
-        "kernel_profile": {"steps": len(prof_stats), "outer_iters_per_step": sum(s["outer_iterations"] for s in prof_stats) / max(1, len(prof_stats)),
-                           "kernel_ms_per_step": kernel_ms_per_profiled_step,
-                           "note": "per-kernel HIP-event pass over separate steps (not the timed ones); compare kernel_ms_per_step with "
-                                   "ms_per_step x outer_iters_per_step / gmres_outer_iters_per_step"},
+        "kernel_profile": ({"steps": len(prof_stats), "outer_iters_per_step": sum(s["outer_iterations"] for s in prof_stats) / max(1, len(prof_stats)),
+                            "kernel_ms_per_step": kernel_ms_per_profiled_step,
+                            "note": "per-kernel HIP-event pass over separate steps (not the timed ones); compare kernel_ms_per_step with "
+                                    "ms_per_step x outer_iters_per_step / gmres_outer_iters_per_step"} if prof_stats else None),
+        "full": bool(args.full),   # False: the headline alone; the fields measured beside it (--full) stay null or empty
     }
     if world > 1:
         out["strong_1M"] = {"time_steps_per_s": value, "n_dofs": dofs.n_dofs, "note": "= value: the mesh of the N = 1 line on %d GPUs" % world}
@@ -823,7 +870,7 @@ def main():
             out["strong_10M"] = err
             emit(out)
         out["strong_10M"] = big_leg(headline_only)
-    if world == 1 and not args.no_cpu:
+    if extra["cpu_baseline"]:
         out["cpu_baseline"] = cpu_baseline(dofs, state, local_rank)
         # lead with the stronger CPU code (compact storage, same algorithm): the stated baseline is the reference-shaped one
         out["gpu_over_best_cpu_all_cores"] = out["value"] / out["cpu_baseline"]["best_cpu"]["value"]

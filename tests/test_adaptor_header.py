@@ -1,6 +1,7 @@
 """include/nsx_dealii_adaptor.hpp cannot be compiled here (no deal.II / Trilinos).  What can be checked
 without them: every libnsx call it makes exists in include/nsx.h with the number of arguments used, every entry point a
 drop-in needs is actually used, and the file cites the reference members it replaces."""
+import json
 import os
 import re
 
@@ -63,11 +64,19 @@ def test_adaptor_cites_the_members_it_replaces_and_says_it_is_unverified():
         assert cite in raw, cite
     for cls in ("PreconditionSIMPLENsx", "PreconditionaSIMPLENsx", "PreconditionYosidaNsx", "PreconditionaYosidaNsx"):
         assert "class " + cls in raw
-    # the reference files the citations point at exist where this container has the reference (not on the GPU box)
-    ref = "/root/reference/Navier-Stokes"
-    if os.path.isdir(ref):
-        for rel in ("include/NavierStokes3D.hpp", "src/NavierStokes3D.cpp", "include/Preconditioners.hpp"):
-            assert os.path.exists(os.path.join(ref, rel))
+    # the reference files the citations point at exist, and every cited line lies inside its file (names and line counts of the
+    # reference's sources are recorded in tests/golden/reference_sources.json)
+    with open(os.path.join(ROOT, "tests", "golden", "reference_sources.json")) as f:
+        files = json.load(f)["files"]
+    for rel in ("include/NavierStokes3D.hpp", "src/NavierStokes3D.cpp", "include/Preconditioners.hpp"):
+        assert rel in files, rel
+    lines_of = {os.path.basename(rel): n for rel, n in files.items()}
+    cited = re.findall(r"\b(\w+\.(?:hpp|cpp)):(\d+(?:-\d+)?(?:,\d+(?:-\d+)?)*)", raw)
+    assert cited
+    for name, spans in cited:
+        assert name in lines_of, name
+        for line in re.findall(r"\d+", spans):
+            assert 1 <= int(line) <= lines_of[name], (name, spans)
 
 
 def test_adaptor_compiles_against_the_declared_interfaces():

@@ -65,6 +65,55 @@ def test_committed_bench_line_carries_the_contract_fields():
 def test_bench_help_runs_without_a_gpu():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and "--gpus" in r.stdout and "--steps" in r.stdout and "--warmup" in r.stdout
+    assert "--full" in r.stdout and "--dump-outputs" in r.stdout
+
+
+def _args(*argv):
+    """bench.py's options as main() sees them after its defaults are applied (one GPU)"""
+    import argparse
+    b = _bench()
+    a = argparse.Namespace(full=False, cpu_only=False, layout_table=None, no_cpu=False, no_big=False, pmc="auto", level=None, comm="auto",
+                           profile_steps=5)
+    for k in argv:
+        k, _, v = k.partition("=")
+        setattr(a, k, v if v else True)
+    return b, a
+
+
+def test_a_plain_run_measures_the_headline_only():
+    b, a = _args()
+    assert b.extras(a, 1) == {"cpu_baseline": False, "pmc_live": False, "hoisted_twin": False, "profile_steps": 0, "self_p2p": False, "strong_10M": False}
+    assert not any(b.extras(a, 4).values())
+    b, a = _args("comm=rccl1")
+    assert not any(b.extras(a, 1).values())
+
+
+def test_full_measures_what_the_line_carries_beside_the_headline():
+    b, a = _args("full")
+    assert b.extras(a, 1) == {"cpu_baseline": True, "pmc_live": True, "hoisted_twin": True, "profile_steps": 5, "self_p2p": False, "strong_10M": False}
+    assert b.extras(a, 4) == {"cpu_baseline": False, "pmc_live": False, "hoisted_twin": False, "profile_steps": 5, "self_p2p": False, "strong_10M": True}
+    b, a = _args("full", "comm=rccl1", "no_cpu")
+    e = b.extras(a, 1)
+    assert e["self_p2p"] and not e["cpu_baseline"] and not e["pmc_live"]
+    b, a = _args("cpu_only")  # the explicit CPU mode runs its leg with or without --full
+    assert b.extras(a, 1)["cpu_baseline"] and b.extras(a, 1)["profile_steps"] == 0
+
+
+def test_dump_outputs_writes_the_solution_in_float64(tmp_path):
+    import numpy as np
+    b = _bench()
+    x = np.random.default_rng(7).standard_normal(1000)
+    b.dump_outputs(str(tmp_path / "full"), 700, x)
+    u, p = np.load(tmp_path / "full" / "velocity.npy"), np.load(tmp_path / "full" / "pressure.npy")
+    assert u.dtype == np.float64 and p.dtype == np.float64 and (u == x[:700]).all() and (p == x[700:]).all()
+    # above the limit: the same seeded sample in every run, within the limit
+    for d in ("s1", "s2"):
+        b.dump_outputs(str(tmp_path / d), 700, x, limit=4000)
+    u1, p1 = np.load(tmp_path / "s1" / "velocity.npy"), np.load(tmp_path / "s1" / "pressure.npy")
+    assert u1.nbytes + p1.nbytes <= 4000 and len(u1) == 350 and len(p1) == 150
+    assert (u1 == np.load(tmp_path / "s2" / "velocity.npy")).all() and (p1 == np.load(tmp_path / "s2" / "pressure.npy")).all()
+    assert np.isin(u1, x[:700]).all() and np.isin(p1, x[700:]).all()
+    assert b.DUMP_LIMIT_BYTES + 2 * 128 <= 64 * 10 ** 6
 
 
 def test_round_tools_parse():

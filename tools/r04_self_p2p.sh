@@ -10,7 +10,7 @@ while [ $# -ge 3 ]; do
   LEVEL=$1; MAXWG=$2; export NSX_EXT_SELF_P2P=$3; shift 3
   i=$((i+1))
   if [ "$MAXWG" = "-" ]; then unset NSX_MGS_MAXWG; else export NSX_MGS_MAXWG=$MAXWG; fi
-  timeout -k 10 240 python3 $R/bench.py --comm rccl1 --level $LEVEL --steps 5 --warmup 2 --spinup 3 --no-cpu --profile-steps 2 --pmc off > $OUT/selfp2p_$i.json 2> $OUT/selfp2p_$i.err
+  timeout -k 10 240 python3 $R/bench.py --full --comm rccl1 --level $LEVEL --steps 5 --warmup 2 --spinup 3 --no-cpu --profile-steps 2 --pmc off > $OUT/selfp2p_$i.json 2> $OUT/selfp2p_$i.err
   rc=$?
   echo "== level $LEVEL, NSX_MGS_MAXWG=$MAXWG, NSX_EXT_SELF_P2P=$NSX_EXT_SELF_P2P: rc $rc"
   grep -h "warning\|failed" $OUT/selfp2p_$i.err | head -3

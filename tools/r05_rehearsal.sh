@@ -13,7 +13,7 @@ export NSX_BENCH_COMM=callbacks NSX_BENCH_PG=gloo NSX_BENCH_DEVICE=0 NSX_BENCH_B
 export NSX_BENCH_HANG_DUMP=${NSX_BENCH_HANG_DUMP:-600} HSA_ENABLE_IPC_MODE_LEGACY=0 MASTER_ADDR=127.0.0.1
 cd $R
 timeout -k 10 ${REHEARSAL_TIMEOUT:-1100} python3 -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port 29533 \
-  bench.py --gpus $N --steps ${REHEARSAL_STEPS:-4} --warmup 1 --spinup 2 --no-cpu > $OUT 2> $OUT.err
+  bench.py --full --gpus $N --steps ${REHEARSAL_STEPS:-4} --warmup 1 --spinup 2 --no-cpu > $OUT 2> $OUT.err
 rc=$?
 echo "rehearsal rc=$rc" >> $OUT.err
 grep -h "paths\|strong_10M\|failed\|Error\|warning" $OUT.err | cut -c1-600 | tail -40
