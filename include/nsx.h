@@ -164,8 +164,34 @@ int nsx_prec_initialize(nsx_handle *h, int prec_type);
 int nsx_prec_vmult(nsx_handle *h, int prec_type, double inner_rtol, int inner_maxiter, double *dst, const double *src,
                    nsx_solve_stats *stats);
 int nsx_system_vmult(nsx_handle *h, double *dst, const double *src); /* BlockSparseMatrix::vmult, host vectors n_u+n_p */
-/* One PreconditionILU::vmult with the factors of the last initialize: which = 0 (F, length n_u) or 1 (S, length n_p). */
+/* One PreconditionILU::vmult with the factors of the last initialize: which = 0 (F, length n_u; read in the handle's inner precision)
+ * or 1 (S, length n_p). */
 int nsx_ilu_apply(nsx_handle *h, int which, double *dst, const double *src);
+
+/* ---- inner precision (opt-in) ---- */
+/* How the two value streams of the INNER solves on the velocity block are stored.  NSX_INNER_FP64 (default): as doubles.  NSX_INNER_FP32:
+ * (1) the scalar velocity operator F as read by every F->vmult inside a preconditioner's vmult (the operator of the inner GMRES,
+ * reference Preconditioners.hpp:173,273,382,405, and aYosida's F->vmult(yu,yu), :507) and (2) the off-diagonal entries of ILU(0)(F) in the
+ * stream of the triangular solves (-L and -U/d) are stored and read as float; the inverse pivots 1/d stay double.  Everything is still
+ * COMPUTED in double, and everything else stays double: system_matrix.vmult of the outer GMRES, the right-hand side, the factorisation
+ * itself (factorised in double, rounded when the stream is written), the Schur complement, its factors and its CG, block(0,1) /
+ * block(1,0), all vectors, the Krylov bases, every reduction.  The linear system that is solved is unchanged; only the preconditioner
+ * differs, by the rounding of its data: NSX_INNER_FP32 computes what NSX_INNER_FP64 computes on (double)(float)value.
+ * The float copy of F and the float stream are written by nsx_prec_initialize from the F of that moment (the factors have always been
+ * those of the last initialisation; in NSX_INNER_FP32 the F of the inner products is, too: a later assembly or nsx_apply_boundary_values
+ * reaches them with the next initialisation, which every nsx_solve_time_step performs).
+ * Allowed any time after nsx_create; the preconditioner has to be initialised again afterwards (nsx_solve_time_step does; a
+ * nsx_prec_vmult before the next nsx_prec_initialize is the usual call-order error).  Unknown value: NSX_ERR_ARG.  A value of F or of its
+ * factors that is not finite as a float fails the initialisation with NSX_ERR_NUMERIC.
+ * Environment: NSX_INNER_PRECISION = fp32 | fp64 is read once by nsx_create as the handle's initial value (anything else: nsx_create fails
+ * with NSX_ERR_ARG).
+ * Paths without a float twin read the double values and say so (nsx_path_info [26], [27]): the plain velocity SpMV (no LDS-staged
+ * chunks), the level-per-launch and the workgroup-per-block triangular solves; the fused kernel of NSX_ILU_MGS=1 is not used. */
+enum { NSX_INNER_FP64 = 0, NSX_INNER_FP32 = 1 };
+int nsx_set_inner_precision(nsx_handle *h, int precision);
+/* Test hook: dst = F src exactly as the inner GMRES computes it (Preconditioners.hpp:382), in the handle's current inner precision; host
+ * vectors of length n_u in the caller's numbering, single-process handles, after nsx_prec_initialize. */
+int nsx_inner_F_vmult(nsx_handle *h, double *dst, const double *src);
 
 /* ---- export in the reference's own layout (Trilinos block CSR with all velocity couplings stored) ---- */
 /* which: 0 system_matrix, 1 mass_matrix, 2 convection_matrix, 3 stiffness_matrix, 4 pressure_mass
@@ -178,7 +204,8 @@ int nsx_export_block(nsx_handle *h, int which, int block, int n_rows, const int3
 int nsx_schur_nnz(nsx_handle *h, int64_t *nnz);
 int nsx_schur_get(nsx_handle *h, int32_t *rowptr, int32_t *colind, double *values);
 /* ILU(0) factors of the last initialize in the compact layout of the scalar velocity graph / the Schur graph
- * (strict lower = L, diagonal = 1/d, strict upper = U/d as Ifpack stores them); graph via nsx_scalar_graph. */
+ * (strict lower = L, diagonal = 1/d, strict upper = U/d as Ifpack stores them); graph via nsx_scalar_graph.  Always the double factors,
+ * whatever the inner precision. */
 int nsx_scalar_graph_nnz(nsx_handle *h, int which, int64_t *nnz); /* which: 0 velocity scalar P2 graph, 1 Schur graph */
 int nsx_scalar_graph(nsx_handle *h, int which, int32_t *rowptr, int32_t *colind);
 int nsx_ilu_get(nsx_handle *h, int which, double *values);
@@ -222,7 +249,10 @@ int nsx_persistent_state(nsx_handle *h, int state[4]);
  * entry of a partial-sum array of the two-launch CG (1: no fold launch), [21] the velocity sweep's instantiation on one GPU without a
  * communicator, [22] / [23] P2 / P1 nodes this handle owns, [24] 1 = the last persistent sweep had the triangular solves of the velocity
  * ILU(0) inside its launch (k_ilu_mgs: PreconditionILU::vmult + the orthogonalisation of one inner GMRES iteration, reference
- * Preconditioners.hpp:382,405, as ONE kernel), [25] such launches so far; [26..31] reserved (0). */
+ * Preconditioners.hpp:382,405, as ONE kernel), [25] such launches so far, [26] 1 = the inner F products of the last solve streamed float
+ * values (NSX_INNER_FP32 through the LDS-staged SpMV), [27] 1 = its velocity triangular solves did (the lane-owner stream) -- "solve":
+ * the last nsx_solve_time_step / nsx_prec_vmult, or the last call of the test hooks nsx_inner_F_vmult ([26]) / nsx_ilu_apply(0) ([27]);
+ * [28..31] reserved (0). */
 int nsx_path_info(nsx_handle *h, int info[32]);
 
 /* SolverGMRES' orthogonalisation (deal.II's modified Gram-Schmidt add_and_dot chain inside every solver.solve of the path: reference

@@ -165,8 +165,11 @@ public:
     ck(h, nsx_path_info(h, p));
     out << "nsx rank " << rank << ": LDS-staged SpMV " << p[0] << " (" << p[1] << " chunks, " << p[2] << " behind the ghost exchange), sweep " << p[3]
         << " entries per thread on " << p[4] << " workgroups, Schur CG path " << p[8] << " on " << p[9] << " blocks, " << p[10] << " neighbours, " << p[12]
-        << " ghost nodes" << std::endl;
+        << " ghost nodes, float values in the inner F products " << p[26] << ", in the velocity triangular solves " << p[27] << std::endl;
   }
+  // NSX_INNER_FP64 (default) / NSX_INNER_FP32: how F and the off-diagonal ILU(0) entries of F are stored for the inner solves (include/nsx.h);
+  // takes effect with the next solve_time_step
+  void set_inner_precision(const int precision) { ck(h, nsx_set_inner_precision(h, precision)); }
 
   // ---- the three members -------------------------------------------------------------------------------------------
   void assemble(const int flags) { ck(h, nsx_assemble(h, flags)); }                      // NavierStokes3D.cpp:163-324

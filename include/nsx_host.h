@@ -184,6 +184,11 @@ int nsxh_ilu_stream_stats(int n_rows, const int32_t *rowptr, const int32_t *coli
 int nsxh_ilu_stream_apply(int n_rows, const int32_t *rowptr, const int32_t *colind, int n_blocks, const int32_t *block_ptr,
                           int blocks_per_wave, int ncomp, int gap, int entries_per_tick, const double *lu, const double *b, double *x);
 
+/* The same replay with the values of the stream (the in-block off-diagonal entries, -L and -U/d) passed through float and the inverse
+ * pivots left in double: what the device kernel k_ilu_solve_lanes_f32 of a handle in NSX_INNER_FP32 computes (include/nsx.h). */
+int nsxh_ilu_stream_apply_f32(int n_rows, const int32_t *rowptr, const int32_t *colind, int n_blocks, const int32_t *block_ptr,
+                              int blocks_per_wave, int ncomp, int gap, int entries_per_tick, const double *lu, const double *b, double *x);
+
 /* ---- test hook: the internal layout of the device library (navierstokes_project_nm4pde_amd/host/layout.hpp, the code
  * nsx_set_internal_layout runs) for a serial DoF table: cell_dofs / cell_coords as for nsx_set_mesh, the caller's ranks as for
  * nsx_set_ranks.  Outputs: node_perm[n_u/dim], pnode_perm[n_p] (caller node -> internal node), the virtual ranks' node ranges

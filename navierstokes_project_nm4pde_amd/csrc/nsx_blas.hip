@@ -2318,6 +2318,8 @@ extern "C" int nsx_path_info(nsx_handle *h, int info[32]) {
     info[23] = h->NP;
     info[24] = h->mgs_last_fused;
     info[25] = h->mgs_fused_launches;
+    info[26] = h->inner_F_fp32_used;
+    info[27] = h->ilu_F_fp32_used;
   } catch (const nsx::Error &e) {
     h->err = e.msg;
     return e.code;

@@ -34,10 +34,12 @@ __device__ __forceinline__ T lanes_ld(const T *p) {
 // no static LDS, its dynamic array starts at 0.
 typedef __attribute__((address_space(3))) double lds_f64;
 
-// what a lane loads per tick: E values and the E + 1 halfwords h[0..E] (host/ilu_stream.hpp), as ceil((E + 1) / 2) dwords
-template <int E>
+// what a lane loads per tick: E values and the E + 1 halfwords h[0..E] (host/ilu_stream.hpp), as ceil((E + 1) / 2) dwords.
+// VT: the type the stream STORES its values in (double, or float for a handle in NSX_INNER_FP32: half the value bytes, same slots);
+// the arithmetic is double either way -- a float value is widened in the register it arrives in.
+template <int E, class VT = double>
 struct LaneSlot {
-  double v[E];
+  VT v[E];
   uint32_t m[(E + 2) / 2];
   __device__ __forceinline__ uint32_t half(int k) const { return (k & 1) ? (m[k / 2] >> 16) : (m[k / 2] & 0xffffu); }
   __device__ __forceinline__ uint32_t flags() const { return m[0]; }  // bit 0 FIRST, bit 1 LAST
@@ -48,8 +50,8 @@ struct LaneOperands {
   double g[E][NCOMP], f[NCOMP];
 };
 
-template <int NCOMP, int E>
-__device__ __forceinline__ void lane_read(const LaneSlot<E> &s, LaneOperands<NCOMP, E> &o) {
+template <int NCOMP, int E, class VT>
+__device__ __forceinline__ void lane_read(const LaneSlot<E, VT> &s, LaneOperands<NCOMP, E> &o) {
 #pragma unroll
   for (int e = 0; e < E; ++e) {
     const lds_f64 *xj = (const lds_f64 *)(uintptr_t)(e == 0 ? (s.m[0] & 0xfff8u) : s.half(e));
@@ -62,16 +64,16 @@ __device__ __forceinline__ void lane_read(const LaneSlot<E> &s, LaneOperands<NCO
 }
 
 // one tick: first the LDS reads of the NEXT tick (slot sn) into the other operand set, then this tick's arithmetic and write
-template <int NCOMP, int E>
-__device__ __forceinline__ void lane_tick(const LaneSlot<E> &s, const LaneSlot<E> &sn, uint32_t scratch, double (&acc)[NCOMP],
+template <int NCOMP, int E, class VT>
+__device__ __forceinline__ void lane_tick(const LaneSlot<E, VT> &s, const LaneSlot<E, VT> &sn, uint32_t scratch, double (&acc)[NCOMP],
                                           const LaneOperands<NCOMP, E> &cur, LaneOperands<NCOMP, E> &nxt) {
-  lane_read<NCOMP, E>(sn, nxt);
+  lane_read<NCOMP, E, VT>(sn, nxt);
   const bool first = (s.flags() & 1u) != 0;
 #pragma unroll
   for (int c = 0; c < NCOMP; ++c) {
     double a = first ? cur.f[c] : acc[c];
 #pragma unroll
-    for (int e = 0; e < E; ++e) a = __builtin_fma(s.v[e], cur.g[e][c], a);
+    for (int e = 0; e < E; ++e) a = __builtin_fma((double)s.v[e], cur.g[e][c], a);
     acc[c] = a;
   }
   lds_f64 *xi = (lds_f64 *)(uintptr_t)((s.flags() & 2u) ? s.half(E) : scratch);
@@ -85,10 +87,10 @@ __device__ __forceinline__ void lane_tick(const LaneSlot<E> &s, const LaneSlot<E
 // stay at eight slabs: the last load then reaches four slabs into whatever follows in the stream, which is never executed).
 // The stream is padded behind its end (ILU_STREAM_PAD slabs): prefetching needs no bounds check.  Uniform base + 32-bit lane
 // offset: the loads take the scalar-base addressing form (no 64-bit vector address arithmetic per load).
-template <int E, int PF>
-__device__ __forceinline__ void lane_load(LaneSlot<E> (&S)[PF], int s0, const uint32_t *__restrict__ meta, const double *__restrict__ val, unsigned lane) {
+template <int E, int PF, class VT>
+__device__ __forceinline__ void lane_load(LaneSlot<E, VT> (&S)[PF], int s0, const uint32_t *__restrict__ meta, const VT *__restrict__ val, unsigned lane) {
   constexpr int MW = (E + 2) / 2;
-  const double *vs_ = val + (size_t)s0 * (64 * E);
+  const VT *vs_ = val + (size_t)s0 * (64 * E);
   const uint32_t *ms_ = meta + (size_t)s0 * (64 * MW);
 #pragma unroll
   for (int k = 0; k < PF; ++k) {
@@ -101,19 +103,19 @@ __device__ __forceinline__ void lane_load(LaneSlot<E> (&S)[PF], int s0, const ui
 
 // A: the first PF slabs of the sweep, already requested by the caller (lane_load(A, sa, ...)): a wave that is alone on its SIMD
 // has nothing else to hide that first trip to memory behind, so the kernel issues it in front of its load / scale passes
-template <int NCOMP, int E, int PF>
-__device__ __forceinline__ void lane_sweep(LaneSlot<E> (&A)[PF], int sa, int sb, const uint32_t *__restrict__ meta, const double *__restrict__ val,
+template <int NCOMP, int E, int PF, class VT>
+__device__ __forceinline__ void lane_sweep(LaneSlot<E, VT> (&A)[PF], int sa, int sb, const uint32_t *__restrict__ meta, const VT *__restrict__ val,
                                            unsigned lane, uint32_t scratch) {
   static_assert(PF == 4 || PF == 8, "sweeps are padded to multiples of 8 slabs; the two operand sets of the gathers alternate tick by tick");
   constexpr int MW = (E + 2) / 2;
   if (sa >= sb) return;
-  LaneSlot<E> B[PF], idle;
+  LaneSlot<E, VT> B[PF], idle;
   LaneOperands<NCOMP, E> o0, o1;
   double acc[NCOMP];
 #pragma unroll
   for (int c = 0; c < NCOMP; ++c) acc[c] = 0.0;
 #pragma unroll
-  for (int e = 0; e < E; ++e) idle.v[e] = 0.0;
+  for (int e = 0; e < E; ++e) idle.v[e] = (VT)0;
 #pragma unroll
   for (int k = 0; k < MW; ++k) idle.m[k] = scratch | (scratch << 16);
   // PF ticks; the last one pre-reads for the first tick of the next PF slabs (nothing of this wave behind the sweep's end)
@@ -121,28 +123,28 @@ __device__ __forceinline__ void lane_sweep(LaneSlot<E> (&A)[PF], int sa, int sb,
   {                                                                                            \
     const bool more_ = (S0) + PF < sb;                                                         \
     _Pragma("unroll") for (int k = 0; k < PF; k += 2) {                                        \
-      lane_tick<NCOMP, E>(S[k], S[k + 1], scratch, acc, o0, o1);                               \
-      lane_tick<NCOMP, E>(S[k + 1], k + 2 < PF ? S[k + 2 < PF ? k + 2 : 0] : (more_ ? SNEXT : idle), scratch, acc, o1, o0); \
+      lane_tick<NCOMP, E, VT>(S[k], S[k + 1], scratch, acc, o0, o1);                               \
+      lane_tick<NCOMP, E, VT>(S[k + 1], k + 2 < PF ? S[k + 2 < PF ? k + 2 : 0] : (more_ ? SNEXT : idle), scratch, acc, o1, o0); \
     }                                                                                          \
   }
   // the sweep's last PF / 2 ticks (PF = 8 only: with PF = 4 a block is the alignment unit)
 #define NSX_USE_HALF(S)                                                                        \
   {                                                                                            \
     _Pragma("unroll") for (int k = 0; k < PF / 2; k += 2) {                                    \
-      lane_tick<NCOMP, E>(S[k], S[k + 1], scratch, acc, o0, o1);                               \
-      lane_tick<NCOMP, E>(S[k + 1], k + 2 < PF / 2 ? S[k + 2 < PF / 2 ? k + 2 : 0] : idle, scratch, acc, o1, o0); \
+      lane_tick<NCOMP, E, VT>(S[k], S[k + 1], scratch, acc, o0, o1);                               \
+      lane_tick<NCOMP, E, VT>(S[k + 1], k + 2 < PF / 2 ? S[k + 2 < PF / 2 ? k + 2 : 0] : idle, scratch, acc, o1, o0); \
     }                                                                                          \
   }
-  lane_read<NCOMP, E>(A[0], o0);
+  lane_read<NCOMP, E, VT>(A[0], o0);
   for (int s0 = sa; s0 < sb; s0 += 2 * PF) {
-    lane_load<E, PF>(B, s0 + PF, meta, val, lane);
+    lane_load<E, PF, VT>(B, s0 + PF, meta, val, lane);
     if (PF == 8 && sb - s0 < PF) {
       NSX_USE_HALF(A)
       break;
     }
     NSX_USE(A, B[0], s0)
     if (s0 + PF >= sb) break;
-    lane_load<E, PF>(A, s0 + 2 * PF, meta, val, lane);
+    lane_load<E, PF, VT>(A, s0 + 2 * PF, meta, val, lane);
     if (PF == 8 && sb - (s0 + PF) < PF) {
       NSX_USE_HALF(B)
       break;

@@ -137,6 +137,8 @@ struct IluSchedule {
   DevBuf<int32_t> pk_slot_of;   // [nnz]: position of every in-block off-diagonal CSR entry in pk_val, -1 otherwise
   DevBuf<double> pk_val;        // [(n_slabs + pad) * 64 * stream_epl]: -L and -U/d in stream order (unused slots stay 0)
   DevBuf<double> pk_dinv;       // [n_rows] inverse pivots in wave order
+  DevBuf<float> pk_val32;       // the same slots as pk_val, stored as float: written INSTEAD of pk_val by a factorisation in NSX_INNER_FP32
+  bool stream_f32 = false;      // which of the two the last factorisation wrote (the other one is stale)
   // explicit inverses (k_ilu_invert / k_ilu_apply_dense): P_b = (L D U)^-1 of every block as a dense row-major n_b x n_b
   // matrix; the triangular solves become one dependency-free dense product per block
   bool dense = false;
@@ -152,6 +154,10 @@ struct IluSchedule {
   DevBuf<int32_t> gl_f_rows, gl_b_rows, in_lo, in_hi;
   DevBuf<int32_t> gl_f_rec, gl_b_rec;  // [4 * rows] per row in level order: row, first entry, end of entries, diagonal (k_ilu_solve_level)
 };
+
+// The ONE test for "this schedule's triangular solves with ncomp right-hand sides run the lane-owner stream": the solve reads the stream
+// under it, and a factorisation in NSX_INNER_FP32 writes the float stream under it (with the stream's own ncomp), nowhere else
+inline bool ilu_lanes_stream(const IluSchedule &s, int ncomp) { return s.packed_ok && !s.levelled && !s.dense && s.stream_ncomp == ncomp; }
 
 // Ghost exchange plan of one scalar space (the Epetra_Import of every vmult): neighbours in ascending rank order,
 // what to pack for each, and where each neighbour's values land in the ghost part of a vector.
@@ -263,6 +269,10 @@ struct nsx_handle {
   nsx::DevCsr gA, gG, gB, gS, gPM;
   nsx::SpmvBlocked blkA;
   nsx::DevBuf<double> vS0, vMass, vStiff, vConv, vF, vG, vB, vPM, vSchur, luF, luS;
+  // ---- inner precision (nsx_set_inner_precision): how F and the off-diagonal ILU(0) entries of F are STORED for the inner solves
+  int inner_precision = NSX_INNER_FP64;
+  nsx::DevBuf<float> vF32;                 // float copy of vF, current behind every nsx_prec_initialize in NSX_INNER_FP32
+  int inner_F_fp32_used = 0, ilu_F_fp32_used = 0;  // the last solve's inner F products / velocity triangular solves streamed float values (nsx_path_info [26], [27])
   nsx::DevBuf<int32_t> bt_of_g;            // for every G entry (i,k): position of (k,i) in the B graph
   nsx::GatherMap gmA, gmG, gmB, gmPM;
   nsx::DevBuf<double> cellbuf;             // per-cell local matrices, SoA [(entry)][cell]
@@ -403,17 +413,19 @@ void run_dirichlet(nsx_handle *h, int n, const int32_t *dofs, const double *vals
 
 // sparse (nsx_sparse.hip)
 bool blocked_usable(const nsx_handle *h);                                                   // F->vmult goes through the LDS-staged SpMV
-void spmv_F(nsx_handle *h, const double *vals, const double *x, double *y);                 // y_u = A x_u   (dim comps)
+void spmv_F(nsx_handle *h, const double *vals, const double *x, double *y, const float *vals32 = nullptr);  // y_u = A x_u   (dim comps)
+void spmv_F_inner(nsx_handle *h, const double *x, double *y);  // F->vmult inside a preconditioner's vmult: F in the handle's inner precision
+void convert_F_f32(nsx_handle *h);                             // vF32 = (float)vF
 void spmv_saddle(nsx_handle *h, const double *x, double *y);                                // full block vmult
 void spmv_G(nsx_handle *h, const double *xp, double *yu, bool accumulate);                  // y_u (+)= block(0,1) x_p
 void spmv_B(nsx_handle *h, const double *xu, double *yp);                                   // y_p = block(1,0) x_u
 void spmv_S(nsx_handle *h, const double *x, double *y);                                     // y = negative_S x
 void schur_numeric(nsx_handle *h, const double *w);                                         // S = B diag(w) G
-void ilu_factor(nsx_handle *h, const DevCsr &g, IluSchedule &s, const double *vals, double *lu, const char *name);
+void ilu_factor(nsx_handle *h, const DevCsr &g, IluSchedule &s, const double *vals, double *lu, const char *name, bool f32 = false);
 void ilu_check(nsx_handle *h);  // after a synchronisation: throws if a factorisation kernel reported a failure
 // dot_slot >= 0: also leave b.x in that scalar slot when the packed kernel can do it; returns whether it did
 bool ilu_solve(nsx_handle *h, const DevCsr &g, const IluSchedule &s, const double *lu, const double *b, double *x, int ncomp,
-               const char *name, int dot_slot = -1);
+               const char *name, int dot_slot = -1, bool f32 = false, int *used_f32 = nullptr);
 void extract_diag(nsx_handle *h, const DevCsr &g, const double *vals, double *d);           // scalar diag
 void abs_rowsum(nsx_handle *h, const DevCsr &g, const double *vals, double *d);
 

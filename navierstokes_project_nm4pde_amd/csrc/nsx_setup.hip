@@ -255,6 +255,8 @@ void setup_ilu_schedule(nsx_handle *h, const Csr &g, const std::vector<int32_t> 
     s.pk_slot_of.upload(st.slot_of, h->stream);
     s.pk_val.alloc((size_t)(st.n_slabs + ILU_STREAM_PAD) * 64 * st.epl);
     s.pk_val.zero(h->stream);
+    s.pk_val32.release();  // the float twin of the stream is laid out again by the next factorisation that wants it
+    s.stream_f32 = false;
     s.pk_dinv.alloc(g.n_rows);
   }
 
@@ -588,6 +590,15 @@ int nsx_create(const nsx_params *p, nsx_handle **out) {
   h->prm = *p;
   h->dim = p->dim;
   if (getenv("NSX_GX_DROP_WG")) h->gx_drop_wg = atoi(getenv("NSX_GX_DROP_WG"));  // fault injection for the tests of the time-out fallbacks
+  if (const char *ip = getenv("NSX_INNER_PRECISION")) {  // the handle's initial inner precision (nsx_set_inner_precision)
+    if (!strcmp(ip, "fp32")) h->inner_precision = NSX_INNER_FP32;
+    else if (!strcmp(ip, "fp64")) h->inner_precision = NSX_INNER_FP64;
+    else {
+      g_create_error = std::string("NSX_INNER_PRECISION must be fp32 or fp64, not '") + ip + "'";
+      delete h;
+      return NSX_ERR_ARG;
+    }
+  }
   try {
     int ndev = 0;
     HIP_CHECK(hipGetDeviceCount(&ndev));

@@ -126,7 +126,7 @@ static SolveResult gmres(nsx_handle *h, const Op &A, double *x, const double *b,
     gram = h->ls_gram.p + (size_t)depth.d * 1024;
   }
   // (in place needs the lane-owner stream: its kernel loads the right-hand side rows into LDS before it writes anything)
-  const bool ilu_conv = P_is_ilu_F && !h->comm && h->schedF.packed_ok && !h->schedF.levelled && h->schedF.stream_ncomp == h->dim &&
+  const bool ilu_conv = P_is_ilu_F && h->inner_precision == NSX_INNER_FP64 /* the fused kernel reads the double stream only */ && !h->comm && h->schedF.packed_ok && !h->schedF.levelled && h->schedF.stream_ncomp == h->dim &&
                         (getenv("NSX_ILU_MGS") && atoi(getenv("NSX_ILU_MGS")) == 1);  // opt-in: see ilu_mgs_entries (nsx_blas.hip)
   double H[N_TMP][N_TMP - 1];
   double gamma[N_TMP], ci[N_TMP - 1], si[N_TMP - 1], hh[N_TMP + 2], h2[N_TMP + 2];
@@ -376,7 +376,9 @@ void prec_initialize(nsx_handle *h, int type) {
   v_scale_vec(h, n_u, h->schur_w.p, h->dirmask.p);
   v_scale(h, n_u, h->schur_w.p, -1.0);
   // preconditioner_F.initialize(*F)   (Prec.hpp:147,250,361,470): F changes every step
-  ilu_factor(h, h->gA, h->schedF, h->vF.p, h->luF.p, "ilu_factor_F");
+  const bool f32 = h->inner_precision == NSX_INNER_FP32;
+  if (f32) convert_F_f32(h);  // the float copy of F the inner products read
+  ilu_factor(h, h->gA, h->schedF, h->vF.p, h->luF.p, "ilu_factor_F", f32);
   // negative_S and preconditioner_S.initialize(negative_S)   (Prec.hpp:144-148,248-251,358-362,468-471).  The reference
   // rebuilds both in every step.  Their only inputs are block(1,0) (assembled once) and the weights w; when w is bit for bit
   // the vector of the previous initialisation (Yosida: D = diag(M / deltat) and the Dirichlet mask do not change in time) the
@@ -429,9 +431,14 @@ void prec_vmult(nsx_handle *h, int type, double tol, int maxit, double *dst, con
   const int n_u = h->n_u, n_p = h->n_p, dim = h->dim, len_u = h->len_u, len_p = h->len_p;
   const double *src_u = src, *src_p = src + h->off_p;
   double *dst_u = dst, *dst_p = dst + h->off_p;
-  Op Fm = [h](double *d, const double *s) { spmv_F(h, h->vF.p, s, d); };
+  Op Fm = [h](double *d, const double *s) { spmv_F_inner(h, s, d); };
+  const bool f32 = h->inner_precision == NSX_INNER_FP32;
   Op Sm = [h](double *d, const double *s) { spmv_S(h, s, d); };
-  Op PF = [h, dim](double *d, const double *s) { ilu_solve(h, h->gA, h->schedF, h->luF.p, s, d, dim, "ilu_solve_F"); };
+  Op PF = [h, dim, f32](double *d, const double *s) {
+    int used = 0;
+    ilu_solve(h, h->gA, h->schedF, h->luF.p, s, d, dim, "ilu_solve_F", -1, f32, &used);
+    if (used) h->ilu_F_fp32_used = 1;
+  };
   Op PS = [h](double *d, const double *s) { ilu_solve(h, h->gS, h->schedS, h->luS.p, s, d, 1, "ilu_solve_S"); };
   OpDot PSdot = [h](double *d, const double *s, int slot) { return ilu_solve(h, h->gS, h->schedS, h->luS.p, s, d, 1, "ilu_solve_S", slot); };
   // SolverCG on negative_S_tilde with tolerance tol * |b| (Prec.hpp:179-182,388-390,500-502): one persistent launch where the
@@ -495,7 +502,7 @@ void prec_vmult(nsx_handle *h, int type, double tol, int maxit, double *dst, con
     v_sadd(h, n_p, yp.p(), -1.0, 1.0, tmp2.p());      // :497
     count(st, false, cg_S(dst_p, yp.p()));          // :500-502
     v_copy(h, n_p, yp.p(), dst_p);                    // :504
-    spmv_F(h, h->vF.p, yu.p(), t.p());                // :507 F->vmult(yu,yu): Epetra multiplies out of place when the arguments alias
+    spmv_F_inner(h, yu.p(), t.p());                   // :507 F->vmult(yu,yu): Epetra multiplies out of place when the arguments alias
     v_copy(h, n_u, yu.p(), t.p());
     spmv_G(h, yp.p(), tmp.p(), false);                // :510
     v_sadd(h, n_u, yu.p(), -1.0, 1.0, tmp.p());       // :511
@@ -512,6 +519,7 @@ void solve_time_step(nsx_handle *h, int type, double tol, double inner_rtol, int
   nsx_solve_stats local;
   if (!st) st = &local;
   memset(st, 0, sizeof(*st));
+  h->inner_F_fp32_used = h->ilu_F_fp32_used = 0;
   v_copy(h, h->len_blk, h->prev_sol.p, h->sol.p);  // previous_solution = solution (NS3D.cpp:555)
   HIP_CHECK(hipStreamSynchronize(h->stream));
   double t0 = now_s();
@@ -598,6 +606,7 @@ int nsx_prec_vmult(nsx_handle *h, int prec_type, double inner_rtol, int inner_ma
     if (stats) memset(stats, 0, sizeof(*stats));
     h->defer_red = false;
     h->pending_red.clear();
+    h->inner_F_fp32_used = h->ilu_F_fp32_used = 0;
     nsx::prec_vmult(h, prec_type, inner_rtol, inner_maxiter, d.p(), s.p(), stats);
     if (stats) stats->persistent_fallbacks = h->n_persistent_fallbacks;
     nsx::vec_to_caller(h, d.p(), dst);
@@ -626,10 +635,32 @@ int nsx_ilu_apply(nsx_handle *h, int which, double *dst, const double *src) {
     const int n = which == 0 ? h->n_u : h->n_p;
     nsx::Tmp d(h, n), s(h, n);
     nsx::part_from_caller(h, which, s.p(), src);
-    if (which == 0) nsx::ilu_solve(h, h->gA, h->schedF, h->luF.p, s.p(), d.p(), h->dim, "ilu_solve_F");
+    if (which == 0) nsx::ilu_solve(h, h->gA, h->schedF, h->luF.p, s.p(), d.p(), h->dim, "ilu_solve_F", -1, h->inner_precision == NSX_INNER_FP32, &h->ilu_F_fp32_used);
     else nsx::ilu_solve(h, h->gS, h->schedS, h->luS.p, s.p(), d.p(), 1, "ilu_solve_S");
     nsx::part_to_caller(h, which, d.p(), dst);
     nsx::ilu_check(h);
+  })
+}
+
+int nsx_set_inner_precision(nsx_handle *h, int precision) {
+  NSX_API_BODY(h, {
+    if (precision != NSX_INNER_FP64 && precision != NSX_INNER_FP32) NSX_THROW(NSX_ERR_ARG, "unknown inner precision %d (NSX_INNER_FP64 = 0, NSX_INNER_FP32 = 1)", precision);
+    h->inner_precision = precision;
+    h->prec_ready = false;  // the float copy of F and the solve stream of its factors are written by the next initialisation
+  })
+}
+
+int nsx_inner_F_vmult(nsx_handle *h, double *dst, const double *src) {
+  NSX_API_BODY(h, {
+    if (!dst || !src || !h->assembled) NSX_THROW(NSX_ERR_ARG, "null vector / nothing assembled");
+    if (!h->prec_ready) NSX_THROW(NSX_ERR_ARG, "call nsx_prec_initialize first (it brings F's copy in the inner precision up to date)");
+    if (h->dist) NSX_THROW(NSX_ERR_UNSUPPORTED, "nsx_inner_F_vmult with host vectors works on a single-process handle only");
+    HIP_CHECK(hipSetDevice(h->prm.device));
+    nsx::Tmp d(h, h->n_u), s(h, h->n_u);
+    nsx::part_from_caller(h, 0, s.p(), src);
+    h->inner_F_fp32_used = 0;
+    nsx::spmv_F_inner(h, s.p(), d.p());
+    nsx::part_to_caller(h, 0, d.p(), dst);
   })
 }
 

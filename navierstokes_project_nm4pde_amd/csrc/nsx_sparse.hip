@@ -154,10 +154,14 @@ __device__ int g_spmv_dbg = 0;  // what the traced launch leaves out: 1 the x ga
 // LDS-staged SpMV: y[i][c] = sum_j A[i,j] x[j][c] with the chunk's x entries gathered ONCE into LDS (SpmvBlocked).
 // The per-non-zero stream is 8 B value + 2 B local column; the 24-B gathers of the plain kernel (10 M per product,
 // bound by the per-CU address rate, not by bytes) become ~1.5 M staged gathers + LDS reads.
-template <int DIM, int W>
-__global__ __launch_bounds__(256) void k_spmv_blocked(int n_rows, const int32_t *__restrict__ desc, const int32_t *__restrict__ rp, const uint16_t *__restrict__ lidx,
-                                                      const double *__restrict__ av, const int32_t *__restrict__ ucols, const double *__restrict__ x,
-                                                      double *__restrict__ y) {
+// VT: the type the matrix stream stores its values in.  double: F as assembled.  float (NSX_INNER_FP32, k_spmv_blocked_f32): the float
+// copy of F the inner solves read -- 4 B value + 2 B local column per non-zero; a value is widened to double in the register it arrives
+// in, so lanes, trips, row order and the grouping of every row's sum are those of the double kernel: the result is the double kernel's on
+// (double)(float)F up to nothing (same operations on the same operands in the same order).
+template <int DIM, int W, class VT>
+__device__ __forceinline__ void spmv_blocked_rows(int n_rows, const int32_t *__restrict__ desc, const int32_t *__restrict__ rp,
+                                                  const uint16_t *__restrict__ lidx, const VT *__restrict__ av, const int32_t *__restrict__ ucols,
+                                                  const double *__restrict__ x, double *__restrict__ y) {
   extern __shared__ double xs[];
   __shared__ int rps[449];
   // launch order (SpmvBlocked::desc): workgroups are dealt round-robin over the 8 XCDs and XCD k takes a contiguous range of chunks, so
@@ -177,7 +181,8 @@ __global__ __launch_bounds__(256) void k_spmv_blocked(int n_rows, const int32_t 
   }
   __syncthreads();
   SPMV_STAMP(1);
-  constexpr int G = 256 / W, U = 4;  // rows in flight per pass, loads per lane kept in flight
+  static_assert(W == 8 || W == 16 || W == 32, "lanes per row");
+  constexpr int G = 256 / W, U = 64 / W;  // rows in flight per pass, loads per lane kept in flight (W = 16: 4; a register set holds 64 entries of a row)
   const int grp = threadIdx.x / W, lane = threadIdx.x % W;
   // software pipeline over the rows of this lane group: the loads of the next row are issued before the current row is
   // reduced, so a wave always has 2*U value loads + 2*U index loads outstanding instead of one dependent chain per row
@@ -191,7 +196,7 @@ __global__ __launch_bounds__(256) void k_spmv_blocked(int n_rows, const int32_t 
     for (int k = 0; k < U; ++k) {
       const int q = p0 + k * W;
       const bool ok = q < e;
-      va[k] = ok ? ld_stream<2>(av + q) : 0.0;
+      va[k] = ok ? (double)ld_stream<2>(av + q) : 0.0;
       vl[k] = ok ? (int)ld_stream<2>(lidx + q) : 0;
     }
   };
@@ -208,7 +213,7 @@ __global__ __launch_bounds__(256) void k_spmv_blocked(int n_rows, const int32_t 
     }
     const int e = rps[rw - r0 + 1];
     for (int p = rps[rw - r0] + lane + U * W; p < e; p += W) {  // rows longer than U*W entries (rare)
-      const double av_ = av[p];
+      const double av_ = (double)av[p];
       const double *xj = xs + (int)lidx[p] * DIM;
 #pragma unroll
       for (int c = 0; c < DIM; ++c) acc[c] += av_ * xj[c];
@@ -242,8 +247,36 @@ __global__ __launch_bounds__(256) void k_spmv_blocked(int n_rows, const int32_t 
 #endif
 }
 
-static double bytes_vel(nsx_handle *h, bool with_g) {
-  double b = 12.0 * h->gA.nnz() + (double)h->N2 * (4 + 8.0 * h->dim * 2);
+template <int DIM, int W>
+__global__ __launch_bounds__(256) void k_spmv_blocked(int n_rows, const int32_t *__restrict__ desc, const int32_t *__restrict__ rp, const uint16_t *__restrict__ lidx,
+                                                      const double *__restrict__ av, const int32_t *__restrict__ ucols, const double *__restrict__ x,
+                                                      double *__restrict__ y) {
+  spmv_blocked_rows<DIM, W, double>(n_rows, desc, rp, lidx, av, ucols, x, y);
+}
+#ifndef NSX_SPMV_F32_W
+#define NSX_SPMV_F32_W 16  // lanes per row of the float kernel (compile time; 16 = the double kernel's, the only value with its grouping of the sums)
+#endif
+// the same product with the float copy of the values (NSX_INNER_FP32: the operator of the inner GMRES on F and aYosida's F->vmult)
+template <int DIM, int W>
+__global__ __launch_bounds__(256) void k_spmv_blocked_f32(int n_rows, const int32_t *__restrict__ desc, const int32_t *__restrict__ rp, const uint16_t *__restrict__ lidx,
+                                                          const float *__restrict__ av, const int32_t *__restrict__ ucols, const double *__restrict__ x,
+                                                          double *__restrict__ y) {
+  spmv_blocked_rows<DIM, W, float>(n_rows, desc, rp, lidx, av, ucols, x, y);
+}
+
+// float copy of a value array (F for the inner products of a handle in NSX_INNER_FP32); a value beyond float's range raises the word
+// ilu_check() reads (code 4) instead of leaving an inf in the stream
+__global__ __launch_bounds__(256) void k_to_f32(int64_t n, const double *__restrict__ v, float *__restrict__ out, int *__restrict__ err) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const double d = v[i];
+  const float f = (float)d;
+  out[i] = f;
+  if (!(fabsf(f) <= 3.402823466e+38f)) __hip_atomic_store(err, 4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);  // inf or NaN
+}
+
+static double bytes_vel(nsx_handle *h, bool with_g, bool f32 = false) {
+  double b = (f32 ? 8.0 : 12.0) * h->gA.nnz() + (double)h->N2 * (4 + 8.0 * h->dim * 2);  // per non-zero: value (8 B, float copy: 4 B) + column
   if (with_g) b += (4.0 + 8.0 * h->dim) * h->gG.nnz() + 4.0 * h->N2 + 8.0 * h->NP;
   return b;
 }
@@ -296,7 +329,7 @@ bool blocked_usable(const nsx_handle *h) {
 }
 // part 0: the table of a one-GPU handle / the chunks of a distributed handle whose staged columns are all owned; part 1: the chunks that
 // stage a ghost column (distributed handles only; an empty table launches nothing)
-static bool launch_blocked(nsx_handle *h, const double *vals, const double *x, double *y, int part = 0) {
+static bool launch_blocked(nsx_handle *h, const double *vals, const double *x, double *y, int part = 0, const float *vals32 = nullptr) {
   const SpmvBlocked &b = h->blkA;
   if (!blocked_usable(h)) return false;
   const size_t shm = (size_t)b.max_ucols * h->dim * sizeof(double);
@@ -305,6 +338,16 @@ static bool launch_blocked(nsx_handle *h, const double *vals, const double *x, d
   if (grid == 0) return true;
 #define NSX_BLK(D) \
   hipLaunchKernelGGL((k_spmv_blocked<D, 16>), dim3(grid), dim3(256), shm, h->stream, h->N2, desc, h->gA.rowptr.p, b.lidx.p, vals, b.ucols.p, x, y)
+  if (vals32) {  // the float stream: same chunks, same launch tables
+    // NSX_SPMV_F32_W = 16 lanes per row as in the double kernel: the same lanes take the same entries, so every row's sum is grouped as
+    // there.  -DNSX_SPMV_F32_W=32 / 8 (compile time, measurements only: another grouping of the sums) lets a lane group read 128 / 32
+    // contiguous bytes of values per trip instead of 64; both are slower (profiles/inner_fp32_spmv_width.json)
+    if (h->dim == 2)
+      hipLaunchKernelGGL((k_spmv_blocked_f32<2, NSX_SPMV_F32_W>), dim3(grid), dim3(256), shm, h->stream, h->N2, desc, h->gA.rowptr.p, b.lidx.p, vals32, b.ucols.p, x, y);
+    else
+      hipLaunchKernelGGL((k_spmv_blocked_f32<3, NSX_SPMV_F32_W>), dim3(grid), dim3(256), shm, h->stream, h->N2, desc, h->gA.rowptr.p, b.lidx.p, vals32, b.ucols.p, x, y);
+    return true;
+  }
 #ifdef NSX_SPMV_TRACE
   static int n_call = 0;
   const bool traced = getenv("NSX_SPMV_TRACE_OUT") && ++n_call == (getenv("NSX_SPMV_TRACE_CALL") ? atoi(getenv("NSX_SPMV_TRACE_CALL")) : 5000);
@@ -347,7 +390,12 @@ static double bytes_halo(const HaloPlan &p, int ncomp) {
   return nn ? 16.0 * (p.send_ptr[nn] + p.recv_ptr[nn]) * ncomp : 0.0;
 }
 
-void spmv_F(nsx_handle *h, const double *vals, const double *x, double *y) {
+// vals32: the float copy of vals (the inner products of a handle in NSX_INNER_FP32).  Only the LDS-staged kernel has a float twin: where
+// it cannot be used the plain kernel reads the double values, and the handle does not report a float product (nsx_path_info [26]).
+void spmv_F(nsx_handle *h, const double *vals, const double *x, double *y, const float *vals32) {
+  if (vals32 && !blocked_usable(h)) vals32 = nullptr;
+  const bool f32 = vals32 != nullptr;
+  if (f32) h->inner_F_fp32_used = 1;
   if (h->dist) {
     // Scopes: "spmv_F" = the rows that need no ghost (they run while the exchange is in flight), "spmv_F_if" = the rows behind it,
     // "halo_u_wait" = what the compute stream waits for the exchange once the first launch is through (its exposed part).
@@ -360,8 +408,8 @@ void spmv_F(nsx_handle *h, const double *vals, const double *x, double *y) {
     const double frac_if = blk ? h->blkA.frac_if : (double)h->splitA.n_interface / std::max(1, h->N2);
     comm_halo_begin(h, h->haloU, xx, h->dim);
     {
-      LaunchScope ls(h, "spmv_F", bytes_vel(h, false) * (1.0 - frac_if));
-      if (blk) launch_blocked(h, vals, x, y, 0);
+      LaunchScope ls(h, "spmv_F", bytes_vel(h, false, f32) * (1.0 - frac_if));
+      if (blk) launch_blocked(h, vals, x, y, 0, vals32);
       else launch_vel(h, false, vals, x, nullptr, y, h->splitA.interior.p, h->splitA.n_interior);
     }
     {
@@ -369,14 +417,19 @@ void spmv_F(nsx_handle *h, const double *vals, const double *x, double *y) {
       comm_halo_finish(h, h->haloU, xx, h->dim);
     }
     {
-      LaunchScope ls(h, "spmv_F_if", bytes_vel(h, false) * frac_if);
-      if (blk) launch_blocked(h, vals, x, y, 1);
+      LaunchScope ls(h, "spmv_F_if", bytes_vel(h, false, f32) * frac_if);
+      if (blk) launch_blocked(h, vals, x, y, 1, vals32);
       else launch_vel(h, false, vals, x, nullptr, y, h->splitA.interface.p, h->splitA.n_interface);
     }
     return;
   }
-  LaunchScope ls(h, "spmv_F", bytes_vel(h, false));
-  if (!launch_blocked(h, vals, x, y)) launch_vel(h, false, vals, x, nullptr, y, nullptr, h->N2);
+  LaunchScope ls(h, "spmv_F", bytes_vel(h, false, f32));
+  if (!launch_blocked(h, vals, x, y, 0, vals32)) launch_vel(h, false, vals, x, nullptr, y, nullptr, h->N2);
+}
+
+// F->vmult inside a preconditioner's vmult (the operator of the inner GMRES, Preconditioners.hpp:173,273,382,405; aYosida's :507)
+void spmv_F_inner(nsx_handle *h, const double *x, double *y) {
+  spmv_F(h, h->vF.p, x, y, h->inner_precision == NSX_INNER_FP32 ? h->vF32.p : nullptr);
 }
 
 static double bytes_B(nsx_handle *h) { return (4.0 + 8.0 * h->dim) * h->gB.nnz() + 12.0 * h->NP + 8.0 * h->dim * h->N2; }
@@ -483,6 +536,15 @@ void build_row_splits(nsx_handle *h) {
             h->NP, h->splitS.n_interface, h->NP);
 }
 
+// the float copy of F for the inner products (NSX_INNER_FP32), rebuilt by every nsx_prec_initialize: F changes with every assembly and
+// every apply_boundary_values, and each of them is followed by an initialisation before the next inner solve
+void convert_F_f32(nsx_handle *h) {
+  const int64_t n = h->gA.nnz();
+  h->vF32.alloc((size_t)n);
+  LaunchScope ls(h, "F_to_f32", 12.0 * (double)n);
+  if (n > 0) hipLaunchKernelGGL(k_to_f32, dim3(cdiv(n, 256)), dim3(256), 0, h->stream, n, h->vF.p, h->vF32.p, (int *)(h->pub_dev + N_SLOTS + 3));
+}
+
 // ------------------------------------------------------------------ diagonals
 __global__ void k_extract_diag(int n_nodes, int dim, const int32_t *__restrict__ diag, const double *__restrict__ v, double *__restrict__ d) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -576,13 +638,27 @@ void schur_numeric(nsx_handle *h, const double *w) {
 constexpr int ILU_WAVES = 4;
 constexpr int ILU_MAXROW = 1024;
 
+// one off-diagonal entry of the factor into the packed solve stream: the double stream, or -- pk_val32 != null, a handle in
+// NSX_INNER_FP32 -- the float stream INSTEAD (factorised in double, rounded on the way out; a value beyond float's range is reported
+// through the word ilu_check() reads, code 5)
+__device__ __forceinline__ void pk_store(double *__restrict__ pk_val, float *__restrict__ pk_val32, int sl, double v, int *err) {
+  if (pk_val32) {
+    const float f = (float)v;
+    pk_val32[sl] = f;
+    if (!(fabsf(f) <= 3.402823466e+38f)) __hip_atomic_store(err, 5, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  } else {
+    pk_val[sl] = v;
+  }
+}
+
 __global__ __launch_bounds__(ILU_WAVES * 64) void k_ilu_factor(const int32_t *__restrict__ bptr, const int32_t *__restrict__ lvl_off,
                                                               const int32_t *__restrict__ lvl_ptr, const int32_t *__restrict__ lvl_rows,
                                                               const int32_t *__restrict__ rp, const int32_t *__restrict__ ci,
                                                               const int32_t *__restrict__ diag, const double *__restrict__ a,
                                                               double *__restrict__ lu, const int32_t *__restrict__ slot_of,
                                                               double *__restrict__ pk_val, double *__restrict__ pk_dinv,
-                                                              int *__restrict__ err, const int32_t *__restrict__ dinv_slot) {
+                                                              int *__restrict__ err, const int32_t *__restrict__ dinv_slot,
+                                                              float *__restrict__ pk_val32) {
   __shared__ double wv[ILU_WAVES][ILU_MAXROW];
   const int blk = blockIdx.x, wave = threadIdx.x / 64, lane = threadIdx.x % 64;
   const int r0 = bptr[blk], r1 = bptr[blk + 1];
@@ -631,7 +707,7 @@ __global__ __launch_bounds__(ILU_WAVES * 64) void k_ilu_factor(const int32_t *__
         lu[p0 + t] = v;
         if (slot_of) {
           const int sl = slot_of[p0 + t];
-          if (sl >= 0) pk_val[sl] = -v;  // the stream adds value * x[col]: it stores -L and -U/d
+          if (sl >= 0) pk_store(pk_val, pk_val32, sl, -v, err);  // the stream adds value * x[col]: it stores -L and -U/d
           if (t == dpos) pk_dinv[dinv_slot[i]] = dinv;
         }
       }
@@ -764,7 +840,8 @@ __global__ __launch_bounds__(ILU_WAVES * 64) void k_ilu_factor_small(const int32
                                                                     const int32_t *__restrict__ diag, const double *__restrict__ a,
                                                                     double *__restrict__ lu, const int32_t *__restrict__ slot_of,
                                                                     double *__restrict__ pk_val, double *__restrict__ pk_dinv,
-                                                                    int *__restrict__ err, const int32_t *__restrict__ dinv_slot) {
+                                                                    int *__restrict__ err, const int32_t *__restrict__ dinv_slot,
+                                                                    float *__restrict__ pk_val32) {
   __shared__ double wv[ILU_WAVES][ILU_DENSE_ROWS];
   __shared__ short posv[ILU_WAVES][ILU_DENSE_ROWS];
   const int blk = blockIdx.x, wave = threadIdx.x / 64, lane = threadIdx.x % 64;
@@ -813,7 +890,7 @@ __global__ __launch_bounds__(ILU_WAVES * 64) void k_ilu_factor_small(const int32
         lu[p0 + t] = v;
         if (slot_of) {
           const int sl = slot_of[p0 + t];
-          if (sl >= 0) pk_val[sl] = -v;  // the stream adds value * x[col]: it stores -L and -U/d
+          if (sl >= 0) pk_store(pk_val, pk_val32, sl, -v, err);  // the stream adds value * x[col]: it stores -L and -U/d
           if (t == dpos) pk_dinv[dinv_slot[i]] = dinv;
         }
       }
@@ -841,7 +918,8 @@ __global__ __launch_bounds__(ILU_WAVES * 64) void k_ilu_factor_lds(const int32_t
                                                                   const double *__restrict__ a, double *__restrict__ lu,
                                                                   const int32_t *__restrict__ slot_of, double *__restrict__ pk_val,
                                                                   double *__restrict__ pk_dinv, int *__restrict__ err,
-                                                                  const int32_t *__restrict__ dinv_slot, int max_rows, int max_nz) {
+                                                                  const int32_t *__restrict__ dinv_slot, int max_rows, int max_nz,
+                                                                  float *__restrict__ pk_val32) {
   extern __shared__ double lds_f[];
   const int nzp = (max_nz + 3) & ~3, mr = max_rows + 4;
   volatile double *lv = lds_f;                       // [nzp] the block's in-block entries, compact numbering
@@ -941,7 +1019,7 @@ __global__ __launch_bounds__(ILU_WAVES * 64) void k_ilu_factor_lds(const int32_t
       lu[p] = v;
       if (slot_of) {
         const int sl = slot_of[p];
-        if (sl >= 0) pk_val[sl] = -v;  // the stream adds value * x[col]: it stores -L and -U/d
+        if (sl >= 0) pk_store(pk_val, pk_val32, sl, -v, err);  // the stream adds value * x[col]: it stores -L and -U/d
       }
     }
     if (slot_of)
@@ -1062,11 +1140,24 @@ void ilu_check(nsx_handle *h) {
   *err = 0;
   if (herr == 1) NSX_THROW(NSX_ERR_UNSUPPORTED, "ILU: a row has more than %d entries", ILU_MAXROW);
   if (herr == 3) NSX_THROW(NSX_ERR_HIP, "ILU: the lane-owner triangular solve found its LDS array away from address 0 and did not run (internal: a static __shared__ object in k_ilu_solve_lanes?)");
+  if (herr == 4) NSX_THROW(NSX_ERR_NUMERIC, "inner precision FP32: an entry of F is not finite as a float (beyond 3.4e38, or NaN)");
+  if (herr == 5) NSX_THROW(NSX_ERR_NUMERIC, "inner precision FP32: an entry of the ILU(0) factors of F is not finite as a float (beyond 3.4e38, or NaN)");
   NSX_THROW(NSX_ERR_NUMERIC, "ILU: zero pivot");
 }
 
-void ilu_factor(nsx_handle *h, const DevCsr &g, IluSchedule &s, const double *vals, double *lu, const char *name) {
+// f32: write the off-diagonal entries into the FLOAT solve stream (pk_val32) instead of the double one -- only where the solve will
+// read the lane-owner stream (ilu_lanes_stream, the predicate ilu_solve uses); lu itself always holds the double factors
+void ilu_factor(nsx_handle *h, const DevCsr &g, IluSchedule &s, const double *vals, double *lu, const char *name, bool f32) {
   int *err = (int *)(h->pub_dev + N_SLOTS + 3);
+  float *pk32 = nullptr;
+  if (f32 && ilu_lanes_stream(s, s.stream_ncomp)) {
+    if (s.pk_val32.n != s.pk_val.n || !s.pk_val32.p) {  // (released whenever the schedule is rebuilt: unused slots must read 0)
+      s.pk_val32.alloc(s.pk_val.n);
+      s.pk_val32.zero(h->stream);
+    }
+    pk32 = s.pk_val32.p;
+  }
+  s.stream_f32 = pk32 != nullptr;
   {
     LaunchScope ls(h, name, 20.0 * g.nnz() + 12.0 * g.n_rows());
     static const bool small_ok = !(getenv("NSX_ILU_SMALL") && atoi(getenv("NSX_ILU_SMALL")) == 0);
@@ -1088,15 +1179,15 @@ void ilu_factor(nsx_handle *h, const DevCsr &g, IluSchedule &s, const double *va
       }
       hipLaunchKernelGGL(k_ilu_factor_lds, dim3(s.n_blocks), dim3(ILU_WAVES * 64), lds, h->stream, s.fac_order.p, s.block_ptr.p, s.blk_lvl_off.p, s.fwd_lvl_ptr.p,
                          s.fwd_rows.p, g.rowptr.p, g.colind.p, g.diag.p, s.in_lo.p, s.in_cptr.p, s.in_cpos.p, vals, lu,
-                         s.packed_ok ? s.pk_slot_of.p : nullptr, s.pk_val.p, s.pk_dinv.p, err, s.pk_dinv_slot.p, s.max_rows, (int)s.max_block_nnz);
+                         s.packed_ok ? s.pk_slot_of.p : nullptr, s.pk_val.p, s.pk_dinv.p, err, s.pk_dinv_slot.p, s.max_rows, (int)s.max_block_nnz, pk32);
     } else if (small_ok && s.max_rows <= ILU_DENSE_ROWS)
       hipLaunchKernelGGL(k_ilu_factor_small, dim3(s.n_blocks), dim3(ILU_WAVES * 64), 0, h->stream, s.block_ptr.p, s.blk_lvl_off.p,
                          s.fwd_lvl_ptr.p, s.fwd_rows.p, g.rowptr.p, g.colind.p, g.diag.p, vals, lu, s.packed_ok ? s.pk_slot_of.p : nullptr,
-                         s.pk_val.p, s.pk_dinv.p, err, s.pk_dinv_slot.p);
+                         s.pk_val.p, s.pk_dinv.p, err, s.pk_dinv_slot.p, pk32);
     else
       hipLaunchKernelGGL(k_ilu_factor, dim3(s.n_blocks), dim3(ILU_WAVES * 64), 0, h->stream, s.block_ptr.p, s.blk_lvl_off.p, s.fwd_lvl_ptr.p,
                          s.fwd_rows.p, g.rowptr.p, g.colind.p, g.diag.p, vals, lu, s.packed_ok ? s.pk_slot_of.p : nullptr, s.pk_val.p,
-                         s.pk_dinv.p, err, s.pk_dinv_slot.p);
+                         s.pk_dinv.p, err, s.pk_dinv_slot.p, pk32);
   }
   if (s.dense) {
     LaunchScope ls(h, "ilu_invert", 8.0 * (double)s.dn_entries + 12.0 * g.nnz());
@@ -1196,11 +1287,13 @@ __global__ __launch_bounds__(256) void k_ilu_solve(const int32_t *__restrict__ b
 // ---- lane-owner stream: device side in nsx_ilu_lanes.hpp (shared with tools/ilu_lanes_bench.hip), schedule in host/ilu_stream.hpp
 constexpr int LANES_K = 12;  // rows per lane and memory trip in the load / scale / store passes of k_ilu_solve_lanes (768 rows: one trip for a wave of 8 blocks)
 
-template <int NCOMP, int E, int PF>
-__global__ __launch_bounds__(64) void k_ilu_solve_lanes(const int32_t *__restrict__ row_ptr, const int32_t *__restrict__ rows,
-                                                        const int32_t *__restrict__ slab_ptr, const uint32_t *__restrict__ meta,
-                                                        const double *__restrict__ val, const double *__restrict__ dinv, const double *b, double *x,
-                                                        double *__restrict__ dot_partial, int *err_host, int force_guard) {
+// VT: the type the stream stores its off-diagonal values in (double: k_ilu_solve_lanes; float: k_ilu_solve_lanes_f32, a handle in
+// NSX_INNER_FP32 -- same slots, same meta words, same ticks, half the value bytes; the inverse pivots stay double)
+template <int NCOMP, int E, int PF, class VT>
+__device__ __forceinline__ void ilu_solve_lanes_wave(const int32_t *__restrict__ row_ptr, const int32_t *__restrict__ rows,
+                                                     const int32_t *__restrict__ slab_ptr, const uint32_t *__restrict__ meta,
+                                                     const VT *__restrict__ val, const double *__restrict__ dinv, const double *b, double *x,
+                                                     double *__restrict__ dot_partial, int *err_host, int force_guard) {
   extern __shared__ double xs[];  // the only LDS of this kernel: the stream's addresses are absolute (nsx_ilu_lanes.hpp)
   // The stream's 16-bit fields are absolute LDS byte addresses: the dynamic array must start at address 0, i.e. the kernel (and
   // every helper inlined into it) must own no static __shared__ object.  Should that ever change, x is NOT written -- so the word
@@ -1220,8 +1313,8 @@ __global__ __launch_bounds__(64) void k_ilu_solve_lanes(const int32_t *__restric
   // the store at the end then need no further trip); then the right-hand side (one dependent trip).  Waves with more rows go
   // through the same three passes chunk by chunk for the rest.
   constexpr int K = LANES_K;
-  LaneSlot<E> A[PF];
-  lane_load<E, PF>(A, s0, meta, val, lane);
+  LaneSlot<E, VT> A[PF];
+  lane_load<E, PF, VT>(A, s0, meta, val, lane);
   int idx0[K];
   double d0[K];
 #pragma unroll
@@ -1266,8 +1359,8 @@ __global__ __launch_bounds__(64) void k_ilu_solve_lanes(const int32_t *__restric
   for (int c = 0; c < NCOMP; ++c) xs[(nr + lane) * NCOMP + c] = 0.0;  // the scratch rows of the idle slots
   const uint32_t scratch = (uint32_t)(nr + lane) * (8u * NCOMP);
   __builtin_amdgcn_wave_barrier();
-  lane_sweep<NCOMP, E, PF>(A, s0, s1, meta, val, lane, scratch);  // y = L^{-1} b
-  lane_load<E, PF>(A, s1, meta, val, lane);                       // (the backward sweep's first slabs fly during the scaling)
+  lane_sweep<NCOMP, E, PF, VT>(A, s0, s1, meta, val, lane, scratch);  // y = L^{-1} b
+  lane_load<E, PF, VT>(A, s1, meta, val, lane);                       // (the backward sweep's first slabs fly during the scaling)
 #pragma unroll
   for (int k = 0; k < K; ++k) {                                   // y *= D^{-1} (inverse pivots stored in the wave's row order)
     const int t = 64 * k + (int)lane;
@@ -1293,7 +1386,7 @@ __global__ __launch_bounds__(64) void k_ilu_solve_lanes(const int32_t *__restric
     }
   }
   __builtin_amdgcn_wave_barrier();
-  lane_sweep<NCOMP, E, PF>(A, s1, s2, meta, val, lane, scratch);  // x = U^{-1} y
+  lane_sweep<NCOMP, E, PF, VT>(A, s1, s2, meta, val, lane, scratch);  // x = U^{-1} y
   double dot = 0.0;  // b . x over this wave's rows (CG's g.h right after the preconditioner, Prec.hpp:388 / SolverCG)
   for (int base = 0; base < nr; base += 64 * K) {
     int idx[K];
@@ -1326,8 +1419,23 @@ __global__ __launch_bounds__(64) void k_ilu_solve_lanes(const int32_t *__restric
   }
 }
 
+template <int NCOMP, int E, int PF>
+__global__ __launch_bounds__(64) void k_ilu_solve_lanes(const int32_t *__restrict__ row_ptr, const int32_t *__restrict__ rows,
+                                                        const int32_t *__restrict__ slab_ptr, const uint32_t *__restrict__ meta,
+                                                        const double *__restrict__ val, const double *__restrict__ dinv, const double *b, double *x,
+                                                        double *__restrict__ dot_partial, int *err_host, int force_guard) {
+  ilu_solve_lanes_wave<NCOMP, E, PF, double>(row_ptr, rows, slab_ptr, meta, val, dinv, b, x, dot_partial, err_host, force_guard);
+}
+template <int NCOMP, int E, int PF>
+__global__ __launch_bounds__(64) void k_ilu_solve_lanes_f32(const int32_t *__restrict__ row_ptr, const int32_t *__restrict__ rows,
+                                                            const int32_t *__restrict__ slab_ptr, const uint32_t *__restrict__ meta,
+                                                            const float *__restrict__ val, const double *__restrict__ dinv, const double *b, double *x,
+                                                            double *__restrict__ dot_partial, int *err_host, int force_guard) {
+  ilu_solve_lanes_wave<NCOMP, E, PF, float>(row_ptr, rows, slab_ptr, meta, val, dinv, b, x, dot_partial, err_host, force_guard);
+}
+
 template <int NCOMP>
-static void launch_lanes(nsx_handle *h, const IluSchedule &s, const double *b, double *x, double *dot_partial) {
+static void launch_lanes(nsx_handle *h, const IluSchedule &s, const double *b, double *x, double *dot_partial, bool f32) {
   const size_t shm = (size_t)(s.max_wave_rows + 64) * NCOMP * sizeof(double);
   static const int pf = getenv("NSX_PF") ? atoi(getenv("NSX_PF")) : 8;
   int *err = (int *)(h->pub_dev + N_SLOTS + 3);  // the mapped word ilu_check() reads
@@ -1335,8 +1443,13 @@ static void launch_lanes(nsx_handle *h, const IluSchedule &s, const double *b, d
 #define NSX_GO(E_, PF_)                                                                                                                        \
   hipLaunchKernelGGL((k_ilu_solve_lanes<NCOMP, E_, PF_>), dim3(s.n_waves), dim3(64), shm, h->stream, s.pk_row_ptr.p, s.pk_rows.p, s.pk_slab_ptr.p, \
                      reinterpret_cast<const uint32_t *>(s.pk_meta.p), s.pk_val.p, s.pk_dinv.p, b, x, dot_partial, err, force_guard)
-#define NSX_GO_E(E_)  \
-  if (pf == 4) NSX_GO(E_, 4); else NSX_GO(E_, 8)
+#define NSX_GO32(E_, PF_)                                                                                                                          \
+  hipLaunchKernelGGL((k_ilu_solve_lanes_f32<NCOMP, E_, PF_>), dim3(s.n_waves), dim3(64), shm, h->stream, s.pk_row_ptr.p, s.pk_rows.p, s.pk_slab_ptr.p, \
+                     reinterpret_cast<const uint32_t *>(s.pk_meta.p), s.pk_val32.p, s.pk_dinv.p, b, x, dot_partial, err, force_guard)
+#define NSX_GO_E(E_)                                            \
+  if (f32) {                                                    \
+    if (pf == 4) NSX_GO32(E_, 4); else NSX_GO32(E_, 8);         \
+  } else if (pf == 4) NSX_GO(E_, 4); else NSX_GO(E_, 8)
   switch (s.stream_epl) {
     case 1: NSX_GO_E(1); break;
     case 2: NSX_GO_E(2); break;
@@ -1345,6 +1458,7 @@ static void launch_lanes(nsx_handle *h, const IluSchedule &s, const double *b, d
     default: NSX_THROW(NSX_ERR_ARG, "internal: %d entries per tick", s.stream_epl);
   }
 #undef NSX_GO_E
+#undef NSX_GO32
 #undef NSX_GO
 }
 
@@ -1361,8 +1475,11 @@ static void launch_ilu_solve(nsx_handle *h, const DevCsr &g, const IluSchedule &
 #undef NSX_ILU_ARGS
 }
 
+// f32: read the float solve stream where the last factorisation wrote one (IluSchedule::stream_f32); every other path reads the double
+// factors and *used_f32 (optional) says which it was
 bool ilu_solve(nsx_handle *h, const DevCsr &g, const IluSchedule &s, const double *lu, const double *b, double *x, int ncomp,
-               const char *name, int dot_slot) {
+               const char *name, int dot_slot, bool f32, int *used_f32) {
+  if (used_f32) *used_f32 = 0;
   if (s.levelled) {
     LaunchScope ls(h, name, 12.0 * (double)s.in_block_nnz + (double)g.n_rows() * (4 + 16.0 * ncomp));
     if (ncomp == 1) ilu_solve_levelled<1>(h, g, s, lu, b, x);
@@ -1370,7 +1487,7 @@ bool ilu_solve(nsx_handle *h, const DevCsr &g, const IluSchedule &s, const doubl
     else ilu_solve_levelled<3>(h, g, s, lu, b, x);
     return false;
   }
-  const bool packed = s.packed_ok && s.stream_ncomp == ncomp;  // (the schedule already checked that a wave's rows fit 64 KiB of LDS)
+  const bool packed = ilu_lanes_stream(s, ncomp);  // (the schedule already checked that a wave's rows fit 64 KiB of LDS)
   if (s.dense && ncomp == 1 && (size_t)s.max_rows * sizeof(double) <= 48 * 1024) {
     LaunchScope ls(h, name, 8.0 * (double)s.dn_entries + 16.0 * g.n_rows());
     const bool with_dot = dot_slot >= 0 && !h->comm && s.n_blocks >= 2 && s.n_blocks <= 512;  // a communicator needs equal counts on all ranks
@@ -1382,13 +1499,17 @@ bool ilu_solve(nsx_handle *h, const DevCsr &g, const IluSchedule &s, const doubl
   // algorithmic bytes (nnz(L+U) * 12 + n * (4 + 8 + 8) per component set): what ONE application of a per-rank ILU(0)
   // has to read -- the IN-BLOCK entries of the factor (diagonal included; couplings between ranks are dropped by Ifpack's
   // local filter and are never touched) + right-hand side and solution.  The packed stream itself moves 768 B per slab.
-  LaunchScope ls(h, name, 12.0 * (double)s.in_block_nnz + (double)g.n_rows() * (4 + 16.0 * ncomp));
+  const bool lanes32 = packed && f32 && s.stream_f32;
+  if (packed && s.stream_f32 && !lanes32) NSX_THROW(NSX_ERR_ARG, "internal: the double solve stream is stale (the last factorisation wrote the float stream)");
+  // (float stream: the off-diagonal entries cost 4 + 4 bytes, the inverse pivots stay 8 + 4)
+  LaunchScope ls(h, name, 12.0 * (double)s.in_block_nnz - (lanes32 ? 4.0 * (double)(s.in_block_nnz - g.n_rows()) : 0.0) + (double)g.n_rows() * (4 + 16.0 * ncomp));
   if (packed) {
+    if (used_f32) *used_f32 = lanes32 ? 1 : 0;
     const bool with_dot = dot_slot >= 0 && !h->comm && s.n_waves >= 2 && s.n_waves <= 512;  // one partial sum per wave
     double *dp = with_dot ? red_out(h, dot_slot, s.n_waves) : nullptr;
-    if (ncomp == 1) launch_lanes<1>(h, s, b, x, dp);
-    else if (ncomp == 2) launch_lanes<2>(h, s, b, x, dp);
-    else launch_lanes<3>(h, s, b, x, dp);
+    if (ncomp == 1) launch_lanes<1>(h, s, b, x, dp, lanes32);
+    else if (ncomp == 2) launch_lanes<2>(h, s, b, x, dp, lanes32);
+    else launch_lanes<3>(h, s, b, x, dp, lanes32);
     if (with_dot) after_reduction(h, dot_slot, s.n_waves);
     return with_dot;
   }

@@ -73,6 +73,7 @@ def _lib():
         "nsxh_tables_dN1": (_f64p, [vp]),
         "nsxh_ilu_stream_stats": (C.c_int, [C.c_int, _i32p, _i32p, C.c_int, _i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
         "nsxh_ilu_stream_apply": (C.c_int, [C.c_int, _i32p, _i32p, C.c_int, _i32p, C.c_int, C.c_int, C.c_int, C.c_int, _f64p, _f64p, _f64p]),
+        "nsxh_ilu_stream_apply_f32": (C.c_int, [C.c_int, _i32p, _i32p, C.c_int, _i32p, C.c_int, C.c_int, C.c_int, C.c_int, _f64p, _f64p, _f64p]),
         "nsxh_internal_layout": (C.c_int, [C.c_int, C.c_int, C.c_int, _i32p, _f64p, C.c_int, C.c_int, C.c_int, _i32p, _i32p, C.c_int, C.c_int, C.c_int,
                                            _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p]),
     }
@@ -300,16 +301,18 @@ def ilu_stream_stats(rowptr, colind, block_ptr, blocks_per_wave=8, ncomp=3, gap=
     return d
 
 
-def ilu_stream_apply(rowptr, colind, block_ptr, lu, b, ncomp=1, blocks_per_wave=8, gap=2, entries_per_tick=1):
-    """Host replay of the packed ILU(0) solve stream (nsxh_ilu_stream_apply): x = U^-1 D^-1 L^-1 b per block."""
+def ilu_stream_apply(rowptr, colind, block_ptr, lu, b, ncomp=1, blocks_per_wave=8, gap=2, entries_per_tick=1, f32=False):
+    """Host replay of the packed ILU(0) solve stream (nsxh_ilu_stream_apply): x = U^-1 D^-1 L^-1 b per block.
+    f32: the stream's values (in-block off-diagonal entries) pass through float, as on a handle in NSX_INNER_FP32."""
     rp, ci, bp = (np.ascontiguousarray(a, dtype=np.int32) for a in (rowptr, colind, block_ptr))
     lu, b = np.ascontiguousarray(lu, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
     x = np.empty_like(b)
-    rc = _lib().nsxh_ilu_stream_apply(len(rp) - 1, rp.ctypes.data_as(_i32p), ci.ctypes.data_as(_i32p), len(bp) - 1, bp.ctypes.data_as(_i32p),
-                                      int(blocks_per_wave), int(ncomp), int(gap), int(entries_per_tick), lu.ctypes.data_as(_f64p), b.ctypes.data_as(_f64p),
-                                      x.ctypes.data_as(_f64p))
+    fn = _lib().nsxh_ilu_stream_apply_f32 if f32 else _lib().nsxh_ilu_stream_apply
+    rc = fn(len(rp) - 1, rp.ctypes.data_as(_i32p), ci.ctypes.data_as(_i32p), len(bp) - 1, bp.ctypes.data_as(_i32p),
+            int(blocks_per_wave), int(ncomp), int(gap), int(entries_per_tick), lu.ctypes.data_as(_f64p), b.ctypes.data_as(_f64p),
+            x.ctypes.data_as(_f64p))
     if rc:
-        raise ValueError("nsxh_ilu_stream_apply failed (%d)" % rc)
+        raise ValueError("nsxh_ilu_stream_apply%s failed (%d)" % ("_f32" if f32 else "", rc))
     return x
 
 

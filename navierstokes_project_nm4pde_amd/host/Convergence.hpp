@@ -285,6 +285,11 @@ protected:
     const int rc = nsx_solve_time_step(h, (int)preconditioner_type, tol_abs, inner_rtol, 100000, 100000, &st);
     if (rc) throw std::runtime_error(std::string("nsx: ") + nsx_last_error(h));
     gmres_iterations.push_back(st.outer_iterations);
+    if (gmres_iterations.size() == 1) {  // once: which inner precision the handle runs (nsx_set_inner_precision / NSX_INNER_PRECISION), from the first solve's paths
+      int info[32];
+      ck(nsx_path_info(h, info));
+      out() << "nsx: inner precision " << (info[26] || info[27] ? "FP32" : "FP64") << " (float values in the inner F products " << info[26] << ", in the velocity triangular solves " << info[27] << ")" << std::endl;
+    }
     out() << "Result:  " << st.outer_iterations << " GMRES iterations" << std::endl;
   }
   void ck(int rc) const {

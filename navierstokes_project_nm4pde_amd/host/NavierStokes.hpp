@@ -245,6 +245,11 @@ protected:
     time_prec.push_back(st.t_prec);
     time_solve.push_back(st.t_solve);
     gmres_iterations.push_back(st.outer_iterations);
+    if (gmres_iterations.size() == 1) {  // once: which inner precision the handle runs (nsx_set_inner_precision / NSX_INNER_PRECISION), from the first solve's paths
+      int info[32];
+      ck(nsx_path_info(h, info));
+      out() << "nsx: inner precision " << (info[26] || info[27] ? "FP32" : "FP64") << " (float values in the inner F products " << info[26] << ", in the velocity triangular solves " << info[27] << ")" << std::endl;
+    }
     out() << "Result:  " << st.outer_iterations << " GMRES iterations" << std::endl;
     if (dim == 2 && write_csv) {  // NavierStokes2D.cpp:622-636
       const int Re = int(0.1 * 1.5 * std::sin(inlet_velocity.get_time() * M_PI / 8.0) / .001);

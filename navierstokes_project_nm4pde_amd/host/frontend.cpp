@@ -1375,6 +1375,27 @@ extern "C" int nsxh_ilu_stream_apply(int n_rows, const int32_t *rowptr, const in
   }
 }
 
+// The same replay with the stream's values passed through float: what a handle in NSX_INNER_FP32 streams (include/nsx.h) -- the entries
+// that have a slot in the stream (the in-block off-diagonal ones, -L and -U/d) are rounded, the inverse pivots are not.
+extern "C" int nsxh_ilu_stream_apply_f32(int n_rows, const int32_t *rowptr, const int32_t *colind, int n_blocks, const int32_t *block_ptr,
+                                         int blocks_per_wave, int ncomp, int gap, int entries_per_tick, const double *lu, const double *b, double *x) {
+  if (!rowptr || !colind || !block_ptr || !lu || !b || !x || ncomp < 1 || gap < 1 || entries_per_tick < 1 || entries_per_tick > 4) return -1;
+  try {
+    const nsx::Csr g = csr_of(n_rows, rowptr, colind);
+    const std::vector<int32_t> bptr(block_ptr, block_ptr + n_blocks + 1);
+    nsx::IluStream s;
+    nsx::build_ilu_stream(g, bptr, blocks_per_wave, ncomp, gap, s, entries_per_tick);
+    if (!s.ok) return -3;
+    std::vector<double> lu32(lu, lu + g.nnz());
+    for (int64_t q = 0; q < g.nnz(); ++q)
+      if (s.slot_of[q] >= 0) lu32[q] = (double)(float)lu[q];
+    nsx::replay_ilu_stream(g, bptr, s, lu32.data(), b, x);
+    return 0;
+  } catch (const std::exception &) {
+    return -1;
+  }
+}
+
 // ---------------------------------------------------------------- test hook: the internal layout of the device library
 // (host/layout.hpp is what nsx_set_internal_layout runs; this entry point lets the CPU tests build a layout for any serial DoF table)
 extern "C" int nsxh_internal_layout(int dim, int n_cells, int dofs_per_cell, const int32_t *cell_dofs, const double *cell_coords, int n_u, int n_p,

@@ -24,9 +24,13 @@ API = [
     "nsx_export_block", "nsx_schur_nnz", "nsx_schur_get", "nsx_scalar_graph_nnz", "nsx_scalar_graph", "nsx_ilu_get",
     "nsx_profile_enable", "nsx_profile_reset", "nsx_profile_count", "nsx_profile_get", "nsx_persistent_state", "nsx_path_info", "nsx_comm_self_halo_test", "nsx_comm_unique_id",
     "nsx_comm_init", "nsx_comm_init_callbacks", "nsx_comm_counters", "nsx_set_mesh_distributed", "nsx_set_force_faces", "nsx_compute_forces",
-    "nsx_set_internal_layout", "nsx_layout_info", "nsx_layout_get", "nsx_gram_schmidt_cycle",
+    "nsx_set_internal_layout", "nsx_layout_info", "nsx_layout_get", "nsx_gram_schmidt_cycle", "nsx_set_inner_precision",
 ]
+# declared in include/nsx.h as well, but with a capital letter in its name, which the header scan of tests/test_abi.py (lower case only)
+# does not see: kept beside the list that scan is compared with; build() checks both
+API_EXTRA = ["nsx_inner_F_vmult"]
 FIRST_TOUCH, COLOUR, COLOUR_ALL = 0, 1, 2  # node order of nsx_set_internal_layout
+INNER_FP64, INNER_FP32 = 0, 1  # nsx_set_inner_precision: how F and the ILU(0) entries of F are stored for the inner solves
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, _f64p, C.c_int)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(_f64p), C.POINTER(C.c_int),
@@ -100,6 +104,8 @@ def lib():
                                            _i32p, _i32p, C.c_int, _i32p, _i32p, _i32p, _i32p, _i32p]
     L.nsx_set_force_faces.argtypes = [vp, C.c_int, _i32p, _i32p, C.c_int, _f64p, _f64p, _f64p, _f64p]
     L.nsx_compute_forces.argtypes = [vp, _f64p, _f64p]
+    L.nsx_set_inner_precision.argtypes = [vp, C.c_int]
+    L.nsx_inner_F_vmult.argtypes = [vp, _f64p, _f64p]
     L._nsx_ready = True
     return L
 
@@ -151,11 +157,13 @@ def gloo_callbacks():
 class Nsx:
     """One device-side `NavierStokes` problem (a handle of libnsx)."""
 
-    def __init__(self, dofs, tables, nu, deltat, device=0, rank=0, world=1, comm="rccl", layout=None):
+    def __init__(self, dofs, tables, nu, deltat, device=0, rank=0, world=1, comm="rccl", layout=None, inner_precision=None):
         """world == 1: the whole problem on one GPU.  world > 1: this process holds rank `rank` of a run with one
         process per GPU (mesh partitioned with Mesh.partition(world, n_sub)); `comm` = "rccl" (needs an initialised
         torch.distributed group to broadcast the unique id) or "callbacks" (host buffers over torch.distributed).
-        layout = (n_virtual_ranks, order, schur_max_rows): nsx_set_internal_layout, requested before the mesh is handed over."""
+        layout = (n_virtual_ranks, order, schur_max_rows): nsx_set_internal_layout, requested before the mesh is handed over.
+        inner_precision = INNER_FP64 / INNER_FP32 (nsx_set_inner_precision); None leaves the library's initial value (the environment's
+        NSX_INNER_PRECISION, else FP64)."""
         L = lib()
         self.L = L
         self._h = C.c_void_p()
@@ -169,6 +177,8 @@ class Nsx:
         self.rank, self.world = rank, world
         N2, dN2, N1, w = _cd(tables.N2), _cd(tables.dN2), _cd(tables.N1), _cd(tables.weights)
         self._ck(L.nsx_set_tables(self._h, tables.n_q, tables.n_p2, tables.n_p1, _d(N2), _d(dN2), _d(N1), _d(w)))
+        if inner_precision is not None:
+            self.set_inner_precision(inner_precision)
         if layout:
             self.set_internal_layout(*layout)
         if world == 1:
@@ -208,7 +218,8 @@ class Nsx:
     PATH_KEYS = ("spmv_lds_staged", "spmv_chunks", "spmv_chunks_behind_halo", "sweep_entries_per_thread", "sweep_grid", "sweep_collective_inside",
                  "sweep_entries_per_thread_max", "cus_reserved", "schur_cg_path", "schur_blocks", "neighbours", "nodes_sent_per_exchange", "ghost_nodes",
                  "schur_dense_inverses", "sweep_off", "fallbacks", "rccl_sweep_velocity_plain", "rccl_sweep_velocity_masked", "rccl_sweep_block_plain",
-                 "rccl_sweep_block_masked", "schur_blocks_per_partial", "sweep_velocity_one_gpu", "owned_p2_nodes", "owned_p1_nodes", "sweep_with_ilu_inside", "fused_launches")
+                 "rccl_sweep_block_masked", "schur_blocks_per_partial", "sweep_velocity_one_gpu", "owned_p2_nodes", "owned_p1_nodes", "sweep_with_ilu_inside", "fused_launches",
+                 "inner_F_fp32", "ilu_F_fp32")
 
     def path_info(self):
         """dict: which code paths the handle's products and solves take (nsx_path_info; schur_cg_path: 1 launch per operation,
@@ -271,6 +282,10 @@ class Nsx:
 
     def set_internal_layout(self, n_virtual_ranks, order=COLOUR, schur_max_rows=0):
         self._ck(self.L.nsx_set_internal_layout(self._h, int(n_virtual_ranks), int(order), int(schur_max_rows)))
+
+    def set_inner_precision(self, precision):
+        """INNER_FP64 / INNER_FP32 (nsx_set_inner_precision); takes effect with the next prec_initialize / solve_time_step"""
+        self._ck(self.L.nsx_set_inner_precision(self._h, int(precision)))
 
     def layout_info(self):
         info = (C.c_int * 5)()
@@ -359,6 +374,13 @@ class Nsx:
         src = _cd(src)
         dst = np.zeros_like(src)
         self._ck(self.L.nsx_system_vmult(self._h, _d(dst), _d(src)))
+        return dst
+
+    def inner_F_vmult(self, src):
+        """F src exactly as the inner GMRES computes it, in the handle's inner precision (nsx_inner_F_vmult; after prec_initialize)"""
+        src = _cd(src)
+        dst = np.empty_like(src)
+        self._ck(self.L.nsx_inner_F_vmult(self._h, _d(dst), _d(src)))
         return dst
 
     def ilu_apply(self, which, src):
