@@ -278,7 +278,7 @@ typedef int (*nsx_exchange_fn)(void *ctx, int n, const int *ranks, const double 
 int nsx_comm_init_callbacks(nsx_handle *h, int rank, int world, nsx_allreduce_fn allreduce, nsx_exchange_fn exchange, void *ctx);
 /* Collectives issued by this handle since the communicator was set: counts[0] all-reduces (the MPI_Allreduce behind Epetra's
  * Dot / Norm2, reference Preconditioners.hpp:157,179,371,388,403 and every SolverGMRES / SolverCG iteration), counts[1] ghost
- * exchanges (the Epetra_Import of every vmult).  The orthogonalisation of a Krylov vector costs ONE all-reduce (csrc/nsx_blas.hip,
+ * exchanges (the Epetra_Import of every vmult).  The orthogonalisation of a Krylov vector costs ONE all-reduce (csrc/nsx_mgs.hip,
  * mgs_lowsync; a second one only when the sweep removes more than 99 % of the vector's norm) where the reference pays one per link
  * of the add_and_dot chain. */
 int nsx_comm_counters(const nsx_handle *h, long long counts[2]);

@@ -84,7 +84,7 @@ void comm_allreduce_partials(nsx_handle *h, double *partials, int count) {
   }
 }
 
-// ---- a collective INSIDE a persistent kernel's grid-wide exchange (nsx_blas.hip: k_mgs_one<.., true>) ---------------------------
+// ---- a collective INSIDE a persistent kernel's grid-wide exchange (nsx_mgs.hip: k_mgs_one<.., true>) ---------------------------
 // The persistent grid runs on the compute stream and cannot call RCCL.  Its reducers leave the rank-local sums in `vals` and count
 // themselves in at `arrive`; on the COMMUNICATION stream, enqueued right behind the grid's launch: a one-thread kernel that spins
 // until the count is complete, the all-reduce, and a one-thread kernel that stores the sweep's sequence number in `flag`, which
@@ -413,8 +413,8 @@ void comm_destroy(nsx_handle *h) {
     }
   }
   h->cu_reserve_failed = false;
-  h->mgs_leave_req = false;
-  h->mgs_local_timeouts = 0;
+  h->mgs.leave_req = false;
+  h->mgs.local_timeouts = 0;
   for (HaloPlan *p : {&h->haloU, &h->haloP})
     if (p->ev_done) {
       (void)hipEventDestroy(p->ev_done);
@@ -454,8 +454,8 @@ int nsx_comm_init(nsx_handle *h, int rank, int world, const uint8_t id[128]) {
     NCCL_CHECK(ncclCommInitRank(&h->comm->comm, world, u, rank));
     h->self_p2p = getenv("NSX_EXT_SELF_P2P") ? atoi(getenv("NSX_EXT_SELF_P2P")) : 0;
     nsx::comm_prepare_streams(h);
-    h->mgs_dist_state = -1;  // a new communicator: the paths the ranks choose together are chosen again
-    h->mgs_dist_fit.clear();
+    h->mgs.dist_state = -1;  // a new communicator: the paths the ranks choose together are chosen again
+    h->mgs.dist_fit.clear();
     h->cgd_agreed = -1;
   } catch (const nsx::Error &e) {
     h->err = e.msg;
@@ -520,8 +520,8 @@ int nsx_comm_init_callbacks(nsx_handle *h, int rank, int world, nsx_allreduce_fn
   h->comm->allreduce = allreduce;
   h->comm->exchange = exchange;
   h->comm->ctx = ctx;
-  h->mgs_dist_state = -1;
-  h->mgs_dist_fit.clear();
+  h->mgs.dist_state = -1;
+  h->mgs.dist_fit.clear();
   h->cgd_agreed = -1;
   return NSX_OK;
 }

@@ -222,6 +222,39 @@ struct ProfEntry {
   std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
 };
 
+// State of the modified Gram-Schmidt sweep (nsx_mgs.hip), grouped by lifetime.
+struct MgsState {
+  // ---- per handle: allocated / read from the environment once (mgs_setup, mgs_lowsync), given up by mgs_recover after a time-out
+  DevBuf<unsigned long long> box;      // persistent sweep: two mailbox regions used alternately by successive launches, then one commit word per workgroup
+  int parity = 0, max_wg = 0;          // region of the next launch; max_wg = 0: the launch-per-link chain is used
+  int used_wg[2] = {0, 0}, used_steps[2] = {0, 0};  // what the last launch on each region filled
+  int max_wg_e[3] = {0, 0, 0};         // resident-grid limit of the 8 / 10 / 12 (link-by-link variants: 20) entries-per-thread instantiations
+  int max_wg_dist[3] = {0, 0, 0};      // resident-grid limits of the distributed instantiations (8 / 10 / 12 entries per thread), room left for the collective
+  int dist_cap_reserved[3] = {0, 0, 0};  // grid limits of the distributed sweep's instantiations on the masked compute stream
+  int links = 0;                       // links of the add_and_dot chain per grid-wide exchange (NSX_MGS_LINKS; 0 = all of them: k_mgs_one, 1 = k_mgs)
+  bool disabled = false;
+  double guard_override = -1.0;        // >= 0: threshold of the Gram formula for |w'|^2 for the duration of nsx_gram_schmidt_cycle
+  // distributed sweep with two collectives (mgs_lowsync): partial sums / all-reduced values / one 32 x 32 Gram matrix per GMRES nesting level
+  DevBuf<double> ls_partial, ls_vals, ls_gram;
+  int ls_mode = -1;                    // NSX_MGS_LOWSYNC, read once: 0 chain, 1 two collectives, 2 one
+  // the persistent sweep of a distributed run (k_mgs_one<.., true>): two value buffers used alternately, arrival counter, release flag
+  DevBuf<double> ext_vals;
+  DevBuf<unsigned long long> ext_words;  // [0] release flag, [1] arrival counter (32 bits used), [2] the sweep the grid gave up on
+  unsigned int ext_expected = 0;
+  int ext_parity = 0;
+  bool redo_ahead = false;             // a sweep fell back to the chain after work depending on its w had been enqueued (read and cleared by the GMRES driver)
+  // ---- per communicator: what the ranks chose together (reset by nsx_comm_init and comm_destroy)
+  int dist_state = -1;                 // -1 not decided yet, 0 two-pass sweep (mgs_lowsync), 1 the collective inside the persistent grid
+  std::map<int, int> dist_fit;         // role of the vector in the solve (mgs_role) -> do ALL ranks' resident grids hold their vector of that role (agreed once per role; asked again when the sizes change)
+  bool leave_req = false;              // a flag wait of this rank's grid timed out on its own: the next sweep asks all ranks to leave the persistent path
+  int local_timeouts = 0;
+  // ---- per schedule: the fused kernel's resident-grid limits hold for one LDS request (the velocity ILU schedule's largest wave)
+  int ilu_cap[3] = {-1, -1, -1}, ilu_cap_rows = -1;
+  // ---- last launch: diagnostics for nsx_path_info
+  int last_e = 0, last_nwg = 0, last_dist = 0, max_e_seen = 0;  // the last persistent sweep: entries per thread, grid, collective inside
+  int last_fused = 0, fused_launches = 0;  // the last persistent sweep had the velocity triangular solves inside (k_ilu_mgs)
+};
+
 struct Comm;  // RCCL state (nsx_comm.hip)
 
 enum { N_SLOTS = 128 };  // device scalar slots (reduction results)
@@ -303,45 +336,21 @@ struct nsx_handle {
   double *pub_host = nullptr, *pub_dev = nullptr;  // [N_SLOTS] values, then the flag word
   unsigned long long pub_seq = 0;
   nsx::DevBuf<unsigned int> pub_counter;
-  // persistent Gram-Schmidt kernel (nsx_blas.hip: k_mgs): two mailbox regions used alternately by successive launches
-  nsx::DevBuf<unsigned long long> mgs_box;
+  nsx::MgsState mgs;        // the modified Gram-Schmidt sweep of the GMRES drivers (nsx_mgs.hip)
   bool sched_dirty = true;  // the ILU schedules do not match the current rank tables yet
-  int mgs_used_wg[2] = {0, 0}, mgs_used_steps[2] = {0, 0};  // what the last launch on each region filled
-  int mgs_parity = 0, mgs_max_wg = 0;  // mgs_max_wg = 0: the launch-per-link chain is used
-  int mgs_max_wg_e[3] = {0, 0, 0};     // resident-grid limit of the 8 / 10 / 12 (link-by-link variants: 20) entries-per-thread instantiations
-  int mgs_links = 2;                   // links of the add_and_dot chain per grid-wide exchange (NSX_MGS_LINKS; 1 = k_mgs)
-  bool mgs_disabled = false;
-  double mgs_guard_override = -1.0;    // >= 0: threshold of the Gram formula for |w'|^2 for the duration of nsx_gram_schmidt_cycle
   int gx_drop_wg = -1;                 // NSX_GX_DROP_WG (fault injection, tests): this workgroup of a persistent grid never posts its sums
   int n_persistent_fallbacks = 0;      // persistent kernels that timed out on this handle (nsx_solve_stats::persistent_fallbacks)
-  // distributed sweep with two collectives (mgs_lowsync): partial sums / all-reduced values / one 32 x 32 Gram matrix per GMRES nesting level
-  nsx::DevBuf<double> ls_partial, ls_vals, ls_gram;
-  int gmres_depth = 0, ls_mode = -1;
-  // the persistent sweep of a distributed run (k_mgs_one<.., true>): two value buffers used alternately, arrival counter, release flag
-  nsx::DevBuf<double> mgs_ext_vals;
-  nsx::DevBuf<unsigned long long> mgs_ext_words;  // [0] release flag, [1] arrival counter (32 bits used), [2] the sweep the grid gave up on
-  unsigned int mgs_ext_expected = 0;
-  int mgs_ext_parity = 0;
-  std::map<int, int> mgs_dist_fit;   // role of the vector in the solve (mgs_role) -> do ALL ranks' resident grids hold their vector of that role (agreed once per role)
+  int gmres_depth = 0;                 // GMRES nesting level of the running solve (one Gram matrix of mgs.ls_gram per level)
   bool cu_reserve_failed = false;    // the ranks tried to mask their streams and one of them could not: all are back on plain streams, nobody asks again
-  bool mgs_leave_req = false;        // a flag wait of this rank's grid timed out on its own: the next sweep asks all ranks to leave the persistent path
-  int mgs_local_timeouts = 0;
-  int mgs_last_fused = 0, mgs_fused_launches = 0;  // the last persistent sweep had the velocity triangular solves inside (k_ilu_mgs)
-  int ilu_mgs_cap[3] = {-1, -1, -1}, ilu_mgs_cap_rows = -1;  // resident-grid limits of the fused kernel's two instantiations (for the LDS request of the current schedule)
-  int mgs_last_e = 0, mgs_last_nwg = 0, mgs_last_dist = 0, mgs_max_e_seen = 0;  // the last persistent sweep: entries per thread, grid, collective inside (nsx_path_info)
   int cgd_agreed = -1;               // two-launch Schur CG: -1 not decided for the current schedules, 0 / 1 the ranks' common answer
   nsx::DevBuf<double> ext_self;           // development (NSX_EXT_SELF_P2P): operands of the self-addressed send / receive in front of the sweep's collective
   hipStream_t stream_plain = nullptr;  // the compute stream of the handle's creation once `stream` has been replaced by one with a CU mask (comm_reserve_cus)
   std::vector<hipStream_t> retired_streams;  // streams RCCL has launched on and the handle no longer uses: destroyed behind ncclCommDestroy (comm_destroy)
   int cu_reserved = 0;               // CUs (one per XCD) the compute stream leaves to the communication stream's kernels
-  int mgs_dist_cap_reserved[3] = {0, 0, 0};  // grid limits of the distributed sweep's instantiations on the masked compute stream
   int comm_probe_local = -1;         // -1 not probed, 0 / 1: kernels of the communication stream run beside a waiting kernel of the compute stream (comm_prepare_streams)
-  int mgs_dist_state = -1;           // -1 not decided yet, 0 two-pass sweep (mgs_lowsync), 1 the collective inside the persistent grid
-  int mgs_max_wg_dist[3] = {0, 0, 0};  // resident-grid limits of the distributed instantiations (8 / 10 / 12 entries per thread), room left for the collective
   long long n_allreduce = 0, n_halo = 0;  // collectives issued (nsx_comm_counters)
   int self_p2p = 0;                       // development (NSX_EXT_SELF_P2P, read by nsx_comm_init): self-addressed send / receive pairs in front of collectives
   int n_ext_collectives = 0;              // collectives inside a persistent grid so far (fault injection: NSX_EXT_LATE_RELEASE)
-  bool mgs_redo_ahead = false;         // a sweep fell back to the chain after work depending on its w had been enqueued
   // persistent Schur-complement CG (nsx_cg.hip: k_cg_schur): mailbox regions, work vectors (d double-buffered, h)
   nsx::DevBuf<unsigned long long> cg_box;
   nsx::CgPlan cgplan;
@@ -484,12 +493,36 @@ void finalize_slots(nsx_handle *h, int slot0, int count);
 // bookkeeping (and the all-reduce of a distributed run) once the kernel is launched
 double *red_out(nsx_handle *h, int slot, int nb);
 void after_reduction(nsx_handle *h, int slot, int nb);
+int red_blocks(nsx_handle *h, int n);  // per-block partial sums of a reduction over n entries (with a communicator: the same count on every rank)
+// fixed-order sum over the block's waves (blockDim.x <= 256), valid in thread 0; sh: 4 doubles
+__device__ __forceinline__ double block_sum_256(double v, double *sh) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
+  if (l == 0) sh[w] = v;
+  __syncthreads();
+  double t = 0.0;
+  if (threadIdx.x == 0) {
+    for (int k = 0; k < (int)(blockDim.x >> 6); ++k) t += sh[k];
+  }
+  return t;  // valid in thread 0
+}
 void defer_reductions(nsx_handle *h, bool on);  // hold back / release (merged) the all-reduces of a distributed run
 double read_scalar(nsx_handle *h, int slot);
 void read_scalars(nsx_handle *h, int slot0, int count, double *out);
 unsigned long long publish_scalars(nsx_handle *h, int slot0, int count);  // asynchronous half of read_scalars
 void collect_published(nsx_handle *h, unsigned long long seq, int slot0, int count, double *out);
 void wait_published(nsx_handle *h, unsigned long long seq);  // host waits for the sequence number of a publication
+// Gram-Schmidt sweep (nsx_mgs.hip): what the BLAS file's diagnostics use of it
+void mgs_setup(nsx_handle *h);        // mailboxes and resident-grid limits of the persistent sweep, once per handle
+int mgs_dirty_words(nsx_handle *h);   // diagnostics: non-empty words of the mailbox region the next sweep would use
+// THE choice of a persistent sweep's instantiation: the first of n_inst instantiations (es[k] entries per thread, at most caps[k] resident
+// workgroups; caps[k] <= 0: not available) whose grid covers n entries, else the last available one (then per_thread > e)
+struct MgsPick {
+  int e = 0, nwg = 1, per_thread = 1 << 30;  // entries per thread of the instantiation (0: none available), grid, entries a thread has to take
+  bool fits() const { return e != 0 && per_thread <= e; }
+};
+MgsPick mgs_pick(int n, const int *caps, int n_inst, const int *es);
 // persistent CG on the Schur complement (nsx_cg.hip); false: not applicable here, use the launch-per-operation solver
 void build_cg_plan(nsx_handle *h);   // with the ILU schedules
 void cg_pack_values(nsx_handle *h);  // after every schur_numeric

@@ -443,7 +443,7 @@ static void refresh_rank_products(nsx_handle *h) {
   h->sched_dirty = true;
   h->prec_ready = false;
   h->schur_valid = false;  // the Schur ILU blocks follow the tables
-  h->mgs_dist_fit.clear();  // sizes may have changed: what the ranks agreed on for the old ones is asked again (every rank gets here alike)
+  h->mgs.dist_fit.clear();  // sizes may have changed: what the ranks agreed on for the old ones is asked again (every rank gets here alike)
 }
 
 void ensure_schedules(nsx_handle *h) {

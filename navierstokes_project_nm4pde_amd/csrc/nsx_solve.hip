@@ -119,15 +119,15 @@ static SolveResult gmres(nsx_handle *h, const Op &A, double *x, const double *b,
   } depth(h);
   double *gram = nullptr;
   if (depth.d < 4) {  // also used on one GPU when a vector is too long for the persistent sweep (v_mgs)
-    if (!h->ls_gram.p) {
-      h->ls_gram.alloc(4 * 1024);
-      h->ls_gram.zero(h->stream);
+    if (!h->mgs.ls_gram.p) {
+      h->mgs.ls_gram.alloc(4 * 1024);
+      h->mgs.ls_gram.zero(h->stream);
     }
-    gram = h->ls_gram.p + (size_t)depth.d * 1024;
+    gram = h->mgs.ls_gram.p + (size_t)depth.d * 1024;
   }
   // (in place needs the lane-owner stream: its kernel loads the right-hand side rows into LDS before it writes anything)
   const bool ilu_conv = P_is_ilu_F && h->inner_precision == NSX_INNER_FP64 /* the fused kernel reads the double stream only */ && !h->comm && h->schedF.packed_ok && !h->schedF.levelled && h->schedF.stream_ncomp == h->dim &&
-                        (getenv("NSX_ILU_MGS") && atoi(getenv("NSX_ILU_MGS")) == 1);  // opt-in: see ilu_mgs_entries (nsx_blas.hip)
+                        (getenv("NSX_ILU_MGS") && atoi(getenv("NSX_ILU_MGS")) == 1);  // opt-in: see ilu_mgs_entries (nsx_mgs.hip)
   double H[N_TMP][N_TMP - 1];
   double gamma[N_TMP], ci[N_TMP - 1], si[N_TMP - 1], hh[N_TMP + 2], h2[N_TMP + 2];
   int accumulated = 0, state = 0, dim = 0;
@@ -205,8 +205,8 @@ static SolveResult gmres(nsx_handle *h, const Op &A, double *x, const double *b,
         }
       };
       bool normalized = v_mgs(h, n, vv, dim, basis, S_H, !re_orth, hh, &next_A, consider, gram, fuse ? vv : nullptr);
-      if (h->mgs_redo_ahead) {  // the sweep fell back to the launch-per-link chain: A * vv was enqueued on an unfinished vv
-        h->mgs_redo_ahead = false;
+      if (h->mgs.redo_ahead) {  // the sweep fell back to the launch-per-link chain: A * vv was enqueued on an unfinished vv
+        h->mgs.redo_ahead = false;
         ahead = 0;
       }
       double s = std::sqrt(hh[dim]);

@@ -596,8 +596,6 @@ __global__ __launch_bounds__(64) void k_schur(int n_rows, const int32_t *__restr
     const int j = sci[e];
     double acc = 0.0;
     // both rows are sorted by column: one pass over row j with a cursor into row i's LDS copy (round 5; a binary search per entry of
-    // row j before: 1.24 ms per step).  The products enter the sum in row j's order as before: bit-identical.
-    // both rows are sorted by column: one pass over row j with a cursor into row i's LDS copy (round 5; a binary search per entry of
     // row j before: 1.24 ms per step, now 0.93).  The products enter the sum in row j's order as before: bit-identical.  What bounds it
     // now is the gather rate: every lane walks another row j, so a load instruction touches 64 different sectors (430 M lane-loads per
     // product); fetching eight entries per trip changed nothing (1.02 ms).  A wave per (i, j) pair would read row j coalesced, but

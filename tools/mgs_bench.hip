@@ -1,12 +1,21 @@
-// mgs_bench.hip — development tool: the Gram-Schmidt sweep kernels of csrc/nsx_blas.hip on their own, with wall-clock stamps
+// mgs_bench.hip — development tool: the Gram-Schmidt sweep kernels of csrc/nsx_mgs.hip on their own, with wall-clock stamps
 // of workgroup 0 and of the last workgroup (NSX_MGS_TRACE), to see where a sweep's microseconds go.  Build + run on the GPU box:
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -munsafe-fp-atomics -DNSX_MGS_TRACE -Dnsx=nsx_tool -o gpurun_out/mgs_bench tools/mgs_bench.hip
 // (-Dnsx=nsx_tool: the kernels get names of their own, libnsx.so is not linked)
 #include "../navierstokes_project_nm4pde_amd/csrc/nsx_blas.hip"
+#include "../navierstokes_project_nm4pde_amd/csrc/nsx_mgs.hip"
 
-namespace nsx {  // the two functions of nsx_comm.hip the host code of nsx_blas.hip refers to (never called here)
+namespace nsx {  // what the host code of the two files refers to in the rest of libnsx (never called here)
 void comm_allreduce_partials(nsx_handle *, double *, int) {}
 void comm_allreduce_scalars(nsx_handle *, int, int) {}
+bool comm_agree_all(nsx_handle *, bool mine) { return mine; }
+bool comm_reserve_cus(nsx_handle *) { return false; }
+void comm_release_cus(nsx_handle *) {}
+bool comm_streams_concurrent(nsx_handle *) { return false; }
+bool comm_on_stream(const nsx_handle *) { return false; }
+void comm_ext_allreduce(nsx_handle *, double *, int, int, unsigned int *, unsigned int, unsigned long long *, unsigned long long) {}
+bool ilu_solve(nsx_handle *, const DevCsr &, const IluSchedule &, const double *, const double *, double *, int, const char *, int, bool, int *) { return false; }
+bool blocked_usable(const nsx_handle *) { return false; }
 int cg_dirty_words(nsx_handle *) { return 0; }
 }  // namespace nsx
 
@@ -22,7 +31,7 @@ __global__ void k_set_trace(u64 *p) { g_mgs_trace = p; }
 template <int E, int M, bool PF>
 static void run(const char *name, int n, int dim, int nwg, double *w, double *w0, MgsArgs V, u64 *box, double *scal, int *err, u64 *tail,
                 double *pub, u64 *trace_dev, bool trace) {
-  const size_t region = std::max(MGS_REGION, MGS_BLK_REGION);
+  const size_t region = MGS_BOX_REGION;
   hipEvent_t a, b;
   HIP_CHECK(hipEventCreate(&a));
   HIP_CHECK(hipEventCreate(&b));
@@ -79,7 +88,7 @@ __global__ void k_flush(const double *__restrict__ p, size_t n, double *out) {
 template <int E, int DMAX>
 static void run_one(const char *name, int n, int dim, double *w, double *w0, MgsArgs V, u64 *box, double *scal, int *err, u64 *tail, double *pub,
                     u64 *trace_dev, double *gram, const double *flush, size_t n_flush) {
-  const size_t region = std::max(MGS_REGION, MGS_BLK_REGION);
+  const size_t region = MGS_BOX_REGION;
   const int nwg = cdiv(n, E * 256);
   HIP_CHECK(hipMemset(box, 0xff, 2 * region * sizeof(u64)));
   HIP_CHECK(hipMemset(gram, 0, 1024 * 8));
@@ -98,8 +107,8 @@ static void run_one(const char *name, int n, int dim, double *w, double *w0, Mgs
     if (flush) hipLaunchKernelGGL(k_flush, dim3(2048), dim3(256), 0, 0, flush, n_flush, scal + 63);
     u64 *bx = box + (size_t)parity * region, *bn = box + (size_t)(1 - parity) * region;
     HIP_CHECK(hipEventRecord(a, 0));
-    hipLaunchKernelGGL((k_mgs_one<E, DMAX>), dim3(nwg), dim3(256), 0, 0, n, n, 0, w, V, dim, gram, bx, bn, rep ? words : 0, scal, err, tail, 1, 0, pub,
-                       (u64 *)(pub + 64), seq, -1, 1e-2);
+    hipLaunchKernelGGL((k_mgs_one<E, DMAX, false>), dim3(nwg), dim3(256), 0, 0, n, n, 0, w, V, dim, gram, bx, bn, rep ? words : 0, scal, err, tail, 1, 0, pub,
+                       (u64 *)(pub + 64), seq, -1, 1e-2, MgsExt{});
     HIP_CHECK(hipEventRecord(b, 0));
     HIP_CHECK(hipEventSynchronize(b));
     float ms = 0;
@@ -125,7 +134,7 @@ int main(int argc, char **argv) {
   double *w, *w0, *vs, *scal, *pub;
   int *err;
   u64 *box, *tail, *trace;
-  const size_t region = std::max(MGS_REGION, MGS_BLK_REGION);
+  const size_t region = MGS_BOX_REGION;
   HIP_CHECK(hipMalloc(&w, (size_t)n * 8));
   HIP_CHECK(hipMalloc(&w0, (size_t)n * 8));
   HIP_CHECK(hipMalloc(&vs, (size_t)n * 8 * nvec));
