@@ -263,6 +263,16 @@ int nsx_path_info(nsx_handle *h, int info[32]);
  * is left and sums it explicitly otherwise; 0 = always the formula, 1e300 = always the explicit sum, < 0 = the library's own (1e-2).
  * A test hook for that formula; m <= 30. */
 int nsx_gram_schmidt_cycle(nsx_handle *h, int n, int m, double *vectors, double norm_guard, double *coeffs, double *norms2);
+/* The same cycle with the arguments of the sweep that nsx_gram_schmidt_cycle fixes, ONE sweep per vector (SolverGMRES' second,
+ * re-orthogonalising sweep is not imitated).  vectors[m][n + gap] is in the device layout of a distributed block vector: logical
+ * entry i of a vector lives at i + (i >= split ? gap : 0) (0 <= split <= n; split == n needs gap == 0); the gap entries are uploaded
+ * and downloaded as they are and no sweep may touch them.  flags bit 0: the sweep also returns |w|^2 BEFORE it (norms2_before[k];
+ * 0 without the bit, [0] = norms2[0]) and decides itself, by SolverGMRES' test |w'| <= 10 |w| sqrt(eps), whether a second sweep
+ * would follow -- it then leaves w unnormalised; flags bit 1: the sweep does not normalise at all (the first sweep of a
+ * re-orthogonalising iteration).  normalized[k] = 1 where the sweep normalised vector k itself, 0 where the hook scaled it with
+ * 1 / sqrt(norms2[k]) afterwards ([0] = 0: vector 0 is always scaled by the hook).  coeffs, norms2, norm_guard, m <= 30: as above. */
+int nsx_gram_schmidt_sweeps(nsx_handle *h, int n, int split, int gap, int m, double *vectors, double norm_guard, int flags, double *coeffs,
+                            double *norms2, double *norms2_before, int *normalized);
 
 /* ---- multi-GPU (one process per GPU, RCCL over xGMI) ---- */
 /* Replaces the MPI communicator inside Epetra (reference NavierStokes3D.hpp:93-94,102): MPI_Allreduce behind every

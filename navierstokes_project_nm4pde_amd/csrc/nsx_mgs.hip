@@ -1410,7 +1410,7 @@ __global__ __launch_bounds__(256) void k_ls_update(int n, int split, int gap, do
 // below the tightest tolerance the parity tests solve to); otherwise |w'|^2 is summed over the vector (one more exchange / collective).
 static double mgs_norm_guard(const nsx_handle *h) {
   static const double g = getenv("NSX_MGS_NORM_GUARD") ? atof(getenv("NSX_MGS_NORM_GUARD")) : 1e-2;
-  return h->mgs.guard_override >= 0.0 ? h->mgs.guard_override : g;  // the override: nsx_gram_schmidt_cycle (tests)
+  return h->mgs.guard_override >= 0.0 ? h->mgs.guard_override : g;  // the override: nsx_gram_schmidt_cycle / nsx_gram_schmidt_sweeps (tests)
 }
 
 static void mgs_ls_buffers(nsx_handle *h) {
@@ -1848,36 +1848,57 @@ int mgs_dirty_words(nsx_handle *h) {
 // normalised.  norm_guard >= 0 replaces the threshold below which the Gram formula for |w'|^2 is refused (0: always the formula,
 // 1e300: always the explicitly summed norm); < 0 keeps the handle's.  For the tests of that formula (tests/test_gpu_errors.py).
 extern "C" int nsx_gram_schmidt_cycle(nsx_handle *h, int n, int m, double *vectors, double norm_guard, double *coeffs, double *norms2) {
-  if (!h || !vectors || !coeffs || !norms2 || n < 1 || m < 1 || m > 30) return NSX_ERR_ARG;
+  if (m < 1 || m > 30) return NSX_ERR_ARG;
+  double before[32];
+  int normalized[32];
+  return nsx_gram_schmidt_sweeps(h, n, n, 0, m, vectors, norm_guard, 0, coeffs, norms2, before, normalized);  // Span(n), consider = false, normalize = true
+}
+
+// The cycle itself, with the arguments of v_mgs that nsx_gram_schmidt_cycle fixes: the vectors live in the device layout of a
+// Span(n, split, gap) (the distributed block vector's: logical entry i at i + (i >= split ? gap : 0); the gap entries travel up
+// and down untouched by the hook), flags bit 0 = consider (|w|^2 before the sweep in out[dim + 1], and the sweep's own decision
+// whether it may normalise), flags bit 1 = do not normalise inside the sweep.  ONE sweep per vector: where v_mgs reports that it
+// did not normalise, the vector is scaled here with the norm the sweep returned, so the basis stays orthonormal for the later
+// sweeps.  For tests/test_gpu_mgs_sweep.py.
+extern "C" int nsx_gram_schmidt_sweeps(nsx_handle *h, int n, int split, int gap, int m, double *vectors, double norm_guard, int flags, double *coeffs,
+                                       double *norms2, double *norms2_before, int *normalized) {
+  if (!h || !vectors || !coeffs || !norms2 || !norms2_before || !normalized || n < 1 || m < 1 || m > 30 || split < 0 || split > n || gap < 0 ||
+      (flags & ~3) != 0 || (split == n && gap != 0))
+    return NSX_ERR_ARG;
   try {
     HIP_CHECK(hipSetDevice(h->prm.device));
+    const size_t len = (size_t)n + gap;
     std::vector<nsx::DevBuf<double>> v(m);
-    for (int k = 0; k < m; ++k) v[k].upload(vectors + (size_t)k * n, n, h->stream);
+    for (int k = 0; k < m; ++k) v[k].upload(vectors + (size_t)k * len, len, h->stream);
     if (!h->mgs.ls_gram.p) {
       h->mgs.ls_gram.alloc(4 * 1024);
       h->mgs.ls_gram.zero(h->stream);
     }
+    const bool consider = (flags & 1) != 0, normalize = (flags & 2) == 0;
     const double keep = h->mgs.guard_override;
     h->mgs.guard_override = norm_guard;
     try {
-      const nsx::Span sp(n);
+      const nsx::Span sp(n, split, gap);
       nsx::v_dot(h, sp, v[0].p, v[0].p, 40);
-      norms2[0] = nsx::read_scalar(h, 40);
+      norms2[0] = norms2_before[0] = nsx::read_scalar(h, 40);
+      normalized[0] = 0;
       nsx::v_scale(h, sp, v[0].p, 1.0 / std::sqrt(norms2[0]));
       for (int k = 1; k < m; ++k) {
         double *vs[32], out[34];
         for (int i = 0; i < k; ++i) vs[i] = v[i].p;
-        const bool normalized = nsx::v_mgs(h, sp, v[k].p, k, vs, 8, true, out, nullptr, false, h->mgs.ls_gram.p);
+        const bool done = nsx::v_mgs(h, sp, v[k].p, k, vs, 8, normalize, out, nullptr, consider, h->mgs.ls_gram.p);
         for (int i = 0; i < k; ++i) coeffs[(size_t)k * m + i] = out[i];
         norms2[k] = out[k];
-        if (!normalized && out[k] > 0.0) nsx::v_scale(h, sp, v[k].p, 1.0 / std::sqrt(out[k]));
+        norms2_before[k] = consider ? out[k + 1] : 0.0;
+        normalized[k] = done ? 1 : 0;
+        if (!done && out[k] > 0.0) nsx::v_scale(h, sp, v[k].p, 1.0 / std::sqrt(out[k]));
       }
     } catch (...) {
       h->mgs.guard_override = keep;
       throw;
     }
     h->mgs.guard_override = keep;
-    for (int k = 0; k < m; ++k) v[k].download(vectors + (size_t)k * n, n, h->stream);
+    for (int k = 0; k < m; ++k) v[k].download(vectors + (size_t)k * len, len, h->stream);
   } catch (const nsx::Error &e) {
     h->err = e.msg;
     return e.code;

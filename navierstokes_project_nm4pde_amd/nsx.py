@@ -25,6 +25,7 @@ API = [
     "nsx_profile_enable", "nsx_profile_reset", "nsx_profile_count", "nsx_profile_get", "nsx_persistent_state", "nsx_path_info", "nsx_comm_self_halo_test", "nsx_comm_unique_id",
     "nsx_comm_init", "nsx_comm_init_callbacks", "nsx_comm_counters", "nsx_set_mesh_distributed", "nsx_set_force_faces", "nsx_compute_forces",
     "nsx_set_internal_layout", "nsx_layout_info", "nsx_layout_get", "nsx_gram_schmidt_cycle", "nsx_set_inner_precision",
+    "nsx_gram_schmidt_sweeps",
 ]
 # declared in include/nsx.h as well, but with a capital letter in its name, which the header scan of tests/test_abi.py (lower case only)
 # does not see: kept beside the list that scan is compared with; build() checks both
@@ -74,6 +75,7 @@ def lib():
     L.nsx_layout_info.argtypes = [vp, C.POINTER(C.c_int)]
     L.nsx_layout_get.argtypes = [vp, _i32p, _i32p, _i32p, _i32p, _i32p]
     L.nsx_gram_schmidt_cycle.argtypes = [vp, C.c_int, C.c_int, _f64p, C.c_double, _f64p, _f64p]
+    L.nsx_gram_schmidt_sweeps.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, _f64p, C.c_double, C.c_int, _f64p, _f64p, _f64p, _i32p]
     for f in ("nsx_set_solution", "nsx_get_solution", "nsx_get_solution_ghosted", "nsx_get_rhs", "nsx_set_rhs"):
         getattr(L, f).argtypes = [vp, _f64p]
     L.nsx_assemble.argtypes = [vp, C.c_int]
@@ -396,6 +398,20 @@ class Nsx:
         coeffs, norms2 = np.zeros((m, m)), np.zeros(m)
         self._ck(self.L.nsx_gram_schmidt_cycle(self._h, n, m, _d(v), float(norm_guard), _d(coeffs), _d(norms2)))
         return v, coeffs, norms2
+
+    SWEEP_CONSIDER, SWEEP_NO_NORMALIZE = 1, 2  # flags of nsx_gram_schmidt_sweeps
+
+    def gram_schmidt_sweeps(self, vectors, split=None, gap=0, norm_guard=-1.0, flags=0):
+        """nsx_gram_schmidt_sweeps on vectors[m][n + gap] in the device layout of a Span(n, split, gap): (vectors after the cycle
+        in the same layout, coefficients [m][m], |w|^2 after each sweep, |w|^2 before it (flags & SWEEP_CONSIDER), whether the
+        sweep normalised the vector itself)"""
+        v = np.ascontiguousarray(vectors, dtype=np.float64).copy()
+        m, n = v.shape[0], v.shape[1] - int(gap)
+        split = n if split is None else int(split)
+        coeffs, norms2, before, normalized = np.zeros((m, m)), np.zeros(m), np.zeros(m), np.zeros(m, dtype=np.int32)
+        self._ck(self.L.nsx_gram_schmidt_sweeps(self._h, n, split, int(gap), m, _d(v), float(norm_guard), int(flags), _d(coeffs), _d(norms2),
+                                                _d(before), _i(normalized)))
+        return v, coeffs, norms2, before, normalized
 
     # -- forces --------------------------------------------------------------------------------
     def set_force_faces(self, cells, lfaces, ftab):
