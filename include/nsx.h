@@ -222,6 +222,42 @@ int nsx_set_force_faces(nsx_handle *h, int n_faces, const int32_t *cells, const 
                         const double *dN2f, const double *N1f, const double *wf);
 int nsx_compute_forces(nsx_handle *h, double *drag, double *lift);
 
+/* ---- flow diagnostics ---- */
+/* How the flow is doing, from the state the handle holds -- the reference prints nothing of the kind; a deal.II application would call
+ * VectorTools::integrate_difference, which imports the ghosted vector and loops over the cells on the host.  u is the velocity part of
+ * `solution` (the ghosted vector: current after nsx_set_solution and after nsx_solve_time_step), previous_solution is what the handle
+ * holds (reference NavierStokes3D.cpp:555; zero until the first solve).  The integrals use the quadrature rule of nsx_set_tables, the one
+ * of the assembly.  lambda_k are the barycentric coordinates of a cell: grad lambda_k = row k of J^-1 for k = 1..dim, grad lambda_0 = minus
+ * their sum, so u_q . grad lambda_k is a component of the reference-cell velocity J^-1 u_q; cfl_max >= 1 means: in one time step the flow
+ * crosses a cell's height towards one of its faces.
+ * nsx_compute_diagnostics reads state only: no vector, matrix or solver state of the handle changes and a following solve computes what
+ * it would have computed without the call.  In a multi-process run a cell that several ranks hold is counted by the rank that owns its
+ * lowest global P2 node, every rank gets the same totals, and the two all-reduces of a call do count in nsx_comm_counters; all ranks
+ * must call it together.  The sums are folded in the caller's cell order in a fixed tree: the results are bitwise reproducible and do not
+ * depend on nsx_set_ranks / nsx_set_internal_layout.
+ * Returns NSX_ERR_ARG before nsx_set_tables / nsx_set_mesh(_distributed), NSX_ERR_UNSUPPORTED for a (dim, n_p2, n_q) the cell kernels are
+ * not instantiated for (the set nsx_assemble accepts), and NSX_ERR_NUMERIC when any per-cell value (of any rank) is not finite -- *out is
+ * then still filled, the values that are not finite propagated (the maxima do not drop a NaN). */
+typedef struct {
+  double kinetic_energy;  /* 1/2 int |u|^2 */
+  double div_l2;          /* ( int (div u)^2 )^(1/2) */
+  double grad_l2_sq;      /* int grad u : grad u   (nu * this = viscous dissipation) */
+  double enstrophy;       /* 1/2 int |curl u|^2   (2D: the scalar curl) */
+  double change_l2;       /* ( int |u - previous_solution|^2 )^(1/2) */
+  double volume;          /* sum of |cell| over the cells counted */
+  double cfl_max;         /* deltat * max over cells, quadrature points q, k = 0..dim of |u_q . grad lambda_k| */
+  double speed_max;       /* max over cells and quadrature points of |u_q| */
+  int64_t n_cells;        /* cells counted (all ranks) */
+} nsx_flow_diag;
+enum { NSX_DIAG_ENERGY = 0, NSX_DIAG_DIV2, NSX_DIAG_GRAD2, NSX_DIAG_ENSTROPHY, NSX_DIAG_CHANGE2, NSX_DIAG_VOLUME, NSX_DIAG_CFL, NSX_DIAG_SPEED,
+       NSX_DIAG_COUNT };
+int nsx_compute_diagnostics(nsx_handle *h, nsx_flow_diag *out);
+/* The per-cell values of the last nsx_compute_diagnostics, values[n_cells of nsx_set_mesh(_distributed)] in the caller's cell order.  Sums: the
+ * cell's share of the integral (NSX_DIAG_DIV2: int_cell (div u)^2, no root; NSX_DIAG_CHANGE2 likewise; energy and enstrophy with their 1/2);
+ * maxima: the cell's own maximum, NSX_DIAG_CFL already multiplied by deltat.  A cell another rank counts has 0 everywhere.
+ * NSX_ERR_ARG before any nsx_compute_diagnostics on the current mesh and for a `which` outside [0, NSX_DIAG_COUNT). */
+int nsx_get_cell_diagnostic(nsx_handle *h, int which, double *values);
+
 /* ---- measurement ---- */
 /* Per-kernel HIP-event timing of the hot path (bench.py roofline): enable, run, then read name/count/total-ms. */
 int nsx_profile_enable(nsx_handle *h, int on);

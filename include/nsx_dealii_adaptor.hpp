@@ -216,6 +216,13 @@ public:
     for (const auto i : solution_owned.locally_owned_elements()) solution_owned[i] = x[i];
     solution_owned.compress(VectorOperation::insert);
   }
+  // monitoring a run (not in the reference): energy, divergence, CFL number ... of the state the handle holds, computed on the device;
+  // collective over the ranks, reads state only.  Throws when a value is not finite -- the run has blown up.
+  nsx_flow_diag flow_diagnostics() const {
+    nsx_flow_diag d{};
+    ck(h, nsx_compute_diagnostics(h, &d));
+    return d;
+  }
 
   // ---- export back into the reference's Trilinos objects (one-rank handles: nsx_export_block) ------------------------
   // which: 0 system_matrix, 1 mass_matrix, 2 convection_matrix, 3 stiffness_matrix, 4 pressure_mass (NavierStokes3D.hpp:230-239)

@@ -368,6 +368,13 @@ struct nsx_handle {
   int ff_n = 0, ff_nq = 0;
   nsx::DevBuf<int32_t> ff_cells, ff_lf;
   nsx::DevBuf<double> ff_N2, ff_dN2, ff_N1, ff_w, ff_out;
+  // ---- flow diagnostics (nsx_diag.hip)
+  nsx::DevBuf<uint8_t> diag_counted;  // [n_cells] 1 = this handle counts the cell (distributed: the owner of its lowest global P2 node does)
+  int diag_n_counted = 0;
+  nsx::DevBuf<double> diag_planes;    // [NSX_DIAG_COUNT][n_cells] per-cell values of the last nsx_compute_diagnostics (allocated by the first one)
+  nsx::DevBuf<double> diag_fold;      // the levels of their fold
+  nsx::DevBuf<double> diag_max;       // [2 * world] the ranks' maxima on their way through the SUM collective
+  bool diag_valid = false;            // diag_planes holds the values of a finished call on the current mesh
   // ---- profiling
   bool prof_on = false;
   std::map<std::string, nsx::ProfEntry> prof;
@@ -419,6 +426,9 @@ void ensure_schedules(nsx_handle *h);  // (re)build the ILU schedules if the ran
 // assembly (nsx_assemble.hip)
 void run_assemble(nsx_handle *h, bool first, int flags);
 void run_dirichlet(nsx_handle *h, int n, const int32_t *dofs, const double *vals);
+
+// flow diagnostics (nsx_diag.hip)
+void diag_mesh_setup(nsx_handle *h);  // with every mesh set-up: which cells this handle counts
 
 // sparse (nsx_sparse.hip)
 bool blocked_usable(const nsx_handle *h);                                                   // F->vmult goes through the LDS-staged SpMV

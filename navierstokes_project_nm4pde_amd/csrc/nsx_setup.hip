@@ -811,6 +811,7 @@ void setup_mesh(nsx_handle *h, int n_cells, int n_cells1, const double *cell_coo
   }
   build_schur_graph(h);
   build_row_splits(h);
+  diag_mesh_setup(h);
   HIP_CHECK(hipStreamSynchronize(h->stream));
   h->have_mesh = true;
   h->assembled = false;

@@ -10,6 +10,7 @@
 #pragma once
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <fstream>
 #include <iomanip>
 #include <iostream>
@@ -130,6 +131,7 @@ public:
       else assemble_time_step(time);
       solve_time_step();
       current_time = time;
+      if (diagnostics_csv) write_diagnostics(time_step, time);
       // NavierStokes3D.cpp:725-726, as written: an EXACT floating-point comparison of the accumulated time with T - deltat (true or false
       // by the rounding of the additions; the reference's own run decides it the same way, so the mirror does not "repair" it)
       if (dim == 3 && time == T - deltat) compute_pressure_difference();
@@ -165,6 +167,17 @@ public:
     vec_drag_coeff.push_back(c_d);
     vec_lift_coeff.push_back(c_l);
     return {c_d, c_l};
+  }
+
+  // Not in the reference: energy, divergence, dissipation, enstrophy, change against previous_solution, CFL number and largest speed of
+  // the state the handle holds, computed on the device (nsx_compute_diagnostics).  *numeric (optional): set when a value is not finite
+  // (the struct is filled all the same); without it such a state throws like every other error.
+  nsx_flow_diag compute_diagnostics(bool *numeric = nullptr) const {
+    nsx_flow_diag d{};
+    const int rc = nsx_compute_diagnostics(h, &d);
+    if (numeric) *numeric = rc == NSX_ERR_NUMERIC;
+    if (!(numeric && rc == NSX_ERR_NUMERIC)) ck(rc);
+    return d;
   }
 
   // NavierStokes::output (NavierStokes3D.cpp:643-683; NavierStokes2D.cpp:642-695 also appends the coefficients to coeff_2.csv)
@@ -259,6 +272,19 @@ protected:
     }
   }
 
+  // opt-in monitor (NSX_DIAGNOSTICS=1): one row per time step in diagnostics_{2D,3D}.csv; a state that is not finite ends the run behind its row
+  void write_diagnostics(const unsigned int time_step, const double time) const {
+    bool numeric = false;
+    const nsx_flow_diag d = compute_diagnostics(&numeric);
+    char row[512];
+    snprintf(row, sizeof(row), "%u,%.17g,%.17g,%.17g,%.17g,%.17g,%.17g,%.17g,%.17g\n", time_step, time, d.kinetic_energy, d.div_l2, d.grad_l2_sq,
+             d.enstrophy, d.change_l2, d.cfl_max, d.speed_max);
+    std::ofstream file(dim == 3 ? "diagnostics_3D.csv" : "diagnostics_2D.csv", std::ios::app);
+    if (!file.is_open()) throw std::runtime_error("cannot write the diagnostics file");
+    file << row;
+    if (numeric) throw std::runtime_error(std::string("nsx: ") + nsx_last_error(h));
+  }
+
   void setup_force_faces() {  // faces with boundary id 3 and the face-quadrature tables (FEFaceValues of compute_forces)
     static const int TETF[4][3] = {{0, 1, 2}, {1, 0, 3}, {0, 2, 3}, {2, 1, 3}};
     static const int TRIF[3][2] = {{0, 1}, {1, 2}, {2, 0}};
@@ -308,6 +334,7 @@ protected:
   nsx_handle *h = nullptr;
   int n_u = 0, n_p = 0;
   double current_time = 0.0;
+  const bool diagnostics_csv = std::getenv("NSX_DIAGNOSTICS") && std::string(std::getenv("NSX_DIAGNOSTICS")) == "1";
 };
 
 }  // namespace nsx

@@ -25,13 +25,15 @@ API = [
     "nsx_profile_enable", "nsx_profile_reset", "nsx_profile_count", "nsx_profile_get", "nsx_persistent_state", "nsx_path_info", "nsx_comm_self_halo_test", "nsx_comm_unique_id",
     "nsx_comm_init", "nsx_comm_init_callbacks", "nsx_comm_counters", "nsx_set_mesh_distributed", "nsx_set_force_faces", "nsx_compute_forces",
     "nsx_set_internal_layout", "nsx_layout_info", "nsx_layout_get", "nsx_gram_schmidt_cycle", "nsx_set_inner_precision",
-    "nsx_gram_schmidt_sweeps",
+    "nsx_gram_schmidt_sweeps", "nsx_compute_diagnostics", "nsx_get_cell_diagnostic",
 ]
 # declared in include/nsx.h as well, but with a capital letter in its name, which the header scan of tests/test_abi.py (lower case only)
 # does not see: kept beside the list that scan is compared with; build() checks both
 API_EXTRA = ["nsx_inner_F_vmult"]
 FIRST_TOUCH, COLOUR, COLOUR_ALL = 0, 1, 2  # node order of nsx_set_internal_layout
 INNER_FP64, INNER_FP32 = 0, 1  # nsx_set_inner_precision: how F and the ILU(0) entries of F are stored for the inner solves
+# planes of nsx_get_cell_diagnostic (NSX_DIAG_*)
+DIAG_ENERGY, DIAG_DIV2, DIAG_GRAD2, DIAG_ENSTROPHY, DIAG_CHANGE2, DIAG_VOLUME, DIAG_CFL, DIAG_SPEED, DIAG_COUNT = range(9)
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, _f64p, C.c_int)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(_f64p), C.POINTER(C.c_int),
@@ -51,10 +53,21 @@ class Stats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class FlowDiag(C.Structure):
+    """nsx_flow_diag"""
+    _fields_ = [("kinetic_energy", C.c_double), ("div_l2", C.c_double), ("grad_l2_sq", C.c_double), ("enstrophy", C.c_double),
+                ("change_l2", C.c_double), ("volume", C.c_double), ("cfl_max", C.c_double), ("speed_max", C.c_double),
+                ("n_cells", C.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class NsxError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("nsx error %d: %s" % (code, msg))
         self.code = code
+        self.diag = None  # Nsx.diagnostics(): the values of a call that found some of them not finite
 
 
 def lib():
@@ -106,6 +119,8 @@ def lib():
                                            _i32p, _i32p, C.c_int, _i32p, _i32p, _i32p, _i32p, _i32p]
     L.nsx_set_force_faces.argtypes = [vp, C.c_int, _i32p, _i32p, C.c_int, _f64p, _f64p, _f64p, _f64p]
     L.nsx_compute_forces.argtypes = [vp, _f64p, _f64p]
+    L.nsx_compute_diagnostics.argtypes = [vp, C.POINTER(FlowDiag)]
+    L.nsx_get_cell_diagnostic.argtypes = [vp, C.c_int, _f64p]
     L.nsx_set_inner_precision.argtypes = [vp, C.c_int]
     L.nsx_inner_F_vmult.argtypes = [vp, _f64p, _f64p]
     L._nsx_ready = True
@@ -431,6 +446,26 @@ class Nsx:
         d, l = C.c_double(), C.c_double()
         self._ck(self.L.nsx_compute_forces(self._h, C.byref(d), C.byref(l)))
         return d.value, l.value
+
+    # -- flow diagnostics ----------------------------------------------------------------------
+    def diagnostics(self):
+        """nsx_compute_diagnostics as a dict (the fields of nsx_flow_diag).  Values that are not finite raise NsxError (code -5) with
+        that dict attached as `.diag`."""
+        d = FlowDiag()
+        rc = self.L.nsx_compute_diagnostics(self._h, C.byref(d))
+        if rc == -5:
+            err = NsxError(rc, (self.L.nsx_last_error(self._h) or b"").decode())
+            err.diag = d.as_dict()
+            raise err
+        self._ck(rc)
+        return d.as_dict()
+
+    def cell_diagnostic(self, which):
+        """per-cell values (DIAG_*) of the last diagnostics(), in the order of the cells handed to the handle (nsx_get_cell_diagnostic)"""
+        n = self.dofs.n_cells if self.world == 1 else int(self.view["n_cells"])
+        v = np.empty(n)
+        self._ck(self.L.nsx_get_cell_diagnostic(self._h, int(which), _d(v)))
+        return v
 
     # -- export --------------------------------------------------------------------------------
     def export_block(self, which, block, graph=None):
