@@ -192,6 +192,14 @@ int nsx_set_inner_precision(nsx_handle *h, int precision);
 /* Test hook: dst = F src exactly as the inner GMRES computes it (Preconditioners.hpp:382), in the handle's current inner precision; host
  * vectors of length n_u in the caller's numbering, single-process handles, after nsx_prec_initialize. */
 int nsx_inner_F_vmult(nsx_handle *h, double *dst, const double *src);
+/* Test hook: ONE SolverCG<Vector>(SolverControl(maxiter, rtol * |b|)).solve(negative_S_tilde, x, b, preconditioner_S) on the caller's
+ * vectors (Preconditioners.hpp:179-182,388-390,500-502), by the very function the preconditioners' vmult calls: the persistent kernel
+ * where the layout allows it, else two launches per iteration, else one launch per operation (nsx_path_info [8], [28], [29] say which).
+ * x: initial guess in, iterate out; steps / last_residual / status (0 converged, 1 not converged) as SolverControl leaves them.
+ * Single-process handles (with or without a 1-rank communicator): x and b have length n_p, in the caller's numbering.  Distributed
+ * handles: length n_p of the whole mesh, globally indexed as for nsx_system_vmult; every rank calls, only the owned entries of b and x
+ * are read and only the owned entries of x are written.  After nsx_prec_initialize (otherwise the usual call-order NSX_ERR_ARG). */
+int nsx_schur_cg(nsx_handle *h, double rtol, int maxiter, double *x, const double *b, int *steps, double *last_residual, int *status);
 
 /* ---- export in the reference's own layout (Trilinos block CSR with all velocity couplings stored) ---- */
 /* which: 0 system_matrix, 1 mass_matrix, 2 convection_matrix, 3 stiffness_matrix, 4 pressure_mass
@@ -288,7 +296,9 @@ int nsx_persistent_state(nsx_handle *h, int state[4]);
  * Preconditioners.hpp:382,405, as ONE kernel), [25] such launches so far, [26] 1 = the inner F products of the last solve streamed float
  * values (NSX_INNER_FP32 through the LDS-staged SpMV), [27] 1 = its velocity triangular solves did (the lane-owner stream) -- "solve":
  * the last nsx_solve_time_step / nsx_prec_vmult, or the last call of the test hooks nsx_inner_F_vmult ([26]) / nsx_ilu_apply(0) ([27]);
- * [28..31] reserved (0). */
+ * [28] rows per lane group of the register-resident block inverses in the last Schur-complement CG (6: blocks of up to 96 rows, 8: up to
+ * 128; 0: the inverses were streamed, or the persistent kernel did not run), [29] 1 = that kernel held the operator's rows in LDS;
+ * [30..31] reserved (0). */
 int nsx_path_info(nsx_handle *h, int info[32]);
 
 /* SolverGMRES' orthogonalisation (deal.II's modified Gram-Schmidt add_and_dot chain inside every solver.solve of the path: reference

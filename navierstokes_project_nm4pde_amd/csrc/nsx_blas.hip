@@ -430,6 +430,8 @@ extern "C" int nsx_path_info(nsx_handle *h, int info[32]) {
     info[25] = h->mgs.fused_launches;
     info[26] = h->inner_F_fp32_used;
     info[27] = h->ilu_F_fp32_used;
+    info[28] = h->cg_last_rpg;
+    info[29] = h->cg_last_lres;
   } catch (const nsx::Error &e) {
     h->err = e.msg;
     return e.code;

@@ -590,6 +590,8 @@ bool cg_schur_persistent(nsx_handle *h, double *x, const double *b, double rtol,
     }
     h->cg_resident = pres;
     h->cg_lds_resident = lres;
+    h->cg_last_rpg = rpg;
+    h->cg_last_lres = lres ? 1 : 0;
   }
   h->cg_parity ^= 1;
   h->cg_last_path = 2;
@@ -604,6 +606,7 @@ bool cg_schur_persistent(nsx_handle *h, double *x, const double *b, double rtol,
     h->cg_max_wg = 0;
     h->cg_disabled = true;
     h->n_persistent_fallbacks++;
+    h->cg_last_rpg = h->cg_last_lres = 0;  // the solve that is reported is the one the caller runs next
     fprintf(stderr, "[nsx] warning: the persistent Schur CG timed out (grid not co-resident): this handle uses one launch per operation from now on\n");
     return false;
   }

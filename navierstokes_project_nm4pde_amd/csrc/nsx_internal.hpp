@@ -363,6 +363,7 @@ struct nsx_handle {
   bool cg_disabled = false;
   nsx::DevBuf<double> cgd_raw;              // ... per-block partial sums of a rank with more Schur blocks than entries of a partial-sum array (k_cgd_fold)
   int cg_last_path = 0;                     // the last Schur CG: 0 none yet, 1 one launch per operation, 2 one persistent launch, 3 two launches per iteration
+  int cg_last_rpg = 0, cg_last_lres = 0;    // ... its persistent kernel's rows per lane group (0, 6, 8) and whether the operator sat in LDS (nsx_path_info [28], [29]); 0 when it did not run
   nsx::DevBuf<double> cgd_vec, cgd_parts;   // distributed Schur CG in two launches per iteration (cg_schur_fused): g, h, S d, d (double-buffered, with ghosts); partial sums
   // ---- force evaluation (compute_forces): obstacle faces + face-quadrature tables
   int ff_n = 0, ff_nq = 0;
@@ -419,6 +420,8 @@ void vec_from_caller(nsx_handle *h, double *dev, const double *host, bool with_g
 void vec_to_caller(nsx_handle *h, const double *dev, double *host);                      // owned entries only
 void part_from_caller(nsx_handle *h, int which, double *dev, const double *host);        // one space, single-process handles: 0 velocity [n_u], 1 pressure [n_p]
 void part_to_caller(nsx_handle *h, int which, const double *dev, double *host);
+void pressure_from_caller(nsx_handle *h, double *dev, const double *host);  // one pressure vector, distributed handles too (globally indexed host, owned entries)
+void pressure_to_caller(nsx_handle *h, const double *dev, double *host);
 inline int32_t node_to_internal(const nsx_handle *h, int32_t local_node) { return h->layout_on ? h->perm2_h[local_node] : local_node; }
 inline int32_t pnode_to_internal(const nsx_handle *h, int32_t local_node) { return h->layout_on ? h->perm1_h[local_node] : local_node; }
 void ensure_schedules(nsx_handle *h);  // (re)build the ILU schedules if the rank / Schur block tables changed

@@ -503,6 +503,24 @@ void part_to_caller(nsx_handle *h, int which, const double *dev, double *host) {
   HIP_CHECK(hipStreamSynchronize(h->stream));
 }
 
+// One pressure vector, any handle.  Single-process: n_p entries in the caller's numbering (part_from_caller).  Distributed: host is
+// globally indexed [n_p_glob] as the pressure part of vec_from_caller's vectors; the owned entries go in, the ghosts of dev [len_p]
+// are zeroed (the halo exchanges of whatever runs next fill them), and only the owned entries come back.
+void pressure_from_caller(nsx_handle *h, double *dev, const double *host) {
+  if (!h->dist) return part_from_caller(h, 1, dev, host);
+  std::vector<double> loc(h->len_p, 0.0);
+  for (int i = 0; i < h->NP; ++i) loc[pnode_to_internal(h, i)] = host[(size_t)h->goff_p + i];
+  HIP_CHECK(hipMemcpyAsync(dev, loc.data(), loc.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIP_CHECK(hipStreamSynchronize(h->stream));
+}
+void pressure_to_caller(nsx_handle *h, const double *dev, double *host) {
+  if (!h->dist) return part_to_caller(h, 1, dev, host);
+  std::vector<double> loc(h->n_p);
+  HIP_CHECK(hipMemcpyAsync(loc.data(), dev, loc.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIP_CHECK(hipStreamSynchronize(h->stream));
+  for (int i = 0; i < h->NP; ++i) host[(size_t)h->goff_p + i] = loc[pnode_to_internal(h, i)];
+}
+
 void vec_from_caller(nsx_handle *h, double *dev, const double *host, bool with_ghosts) {
   const int dim = h->dim;
   if (!h->dist) {

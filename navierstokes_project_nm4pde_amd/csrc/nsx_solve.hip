@@ -318,6 +318,29 @@ static double norm2(nsx_handle *h, Span n, const double *v) {
   return std::sqrt(read_scalar(h, S_T));
 }
 
+// negative_S_tilde and its ILU(0) as operators of the Krylov solvers (the Schur CG below, aSIMPLE's GMRES in prec_vmult)
+static Op schur_product(nsx_handle *h) {
+  return [h](double *d, const double *s) { spmv_S(h, s, d); };
+}
+static Op schur_ilu(nsx_handle *h) {
+  return [h](double *d, const double *s) { ilu_solve(h, h->gS, h->schedS, h->luS.p, s, d, 1, "ilu_solve_S"); };
+}
+
+// SolverCG on negative_S_tilde with tolerance rtol * |b| and the Schur ILU(0) as preconditioner (Prec.hpp:179-182,388-390,500-502): one
+// persistent launch where the layout allows it (nsx_cg.hip), else two launches per iteration, else the launch-per-operation solver
+// above.  The preconditioners' vmult and the test hook nsx_schur_cg both solve through here.
+static SolveResult schur_cg(nsx_handle *h, double rtol, int maxit, double *x, const double *b) {
+  int steps = 0, status = 0;
+  double last = 0.0;
+  h->cg_last_rpg = h->cg_last_lres = 0;
+  if (cg_schur_persistent(h, x, b, rtol, maxit, &steps, &last, &status)) return SolveResult{status, steps, last};
+  if (cg_schur_fused(h, x, b, rtol, maxit, &steps, &last, &status)) return SolveResult{status, steps, last};  // distributed, or too many blocks for a resident grid: two launches per iteration
+  h->cg_last_path = 1;
+  const Op Sm = schur_product(h), PS = schur_ilu(h);
+  OpDot PSdot = [h](double *d, const double *s, int slot) { return ilu_solve(h, h->gS, h->schedS, h->luS.p, s, d, 1, "ilu_solve_S", slot); };
+  return cg(h, Sm, x, b, PS, h->n_p, h->len_p, rtol * norm2(h, h->n_p, b), maxit, &PSdot);
+}
+
 // ------------------------------------------------------------------ preconditioners
 __global__ void k_same_and_keep(int n, const double *__restrict__ w, double *__restrict__ prev, int *changed) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -433,24 +456,13 @@ void prec_vmult(nsx_handle *h, int type, double tol, int maxit, double *dst, con
   double *dst_u = dst, *dst_p = dst + h->off_p;
   Op Fm = [h](double *d, const double *s) { spmv_F_inner(h, s, d); };
   const bool f32 = h->inner_precision == NSX_INNER_FP32;
-  Op Sm = [h](double *d, const double *s) { spmv_S(h, s, d); };
+  const Op Sm = schur_product(h), PS = schur_ilu(h);
   Op PF = [h, dim, f32](double *d, const double *s) {
     int used = 0;
     ilu_solve(h, h->gA, h->schedF, h->luF.p, s, d, dim, "ilu_solve_F", -1, f32, &used);
     if (used) h->ilu_F_fp32_used = 1;
   };
-  Op PS = [h](double *d, const double *s) { ilu_solve(h, h->gS, h->schedS, h->luS.p, s, d, 1, "ilu_solve_S"); };
-  OpDot PSdot = [h](double *d, const double *s, int slot) { return ilu_solve(h, h->gS, h->schedS, h->luS.p, s, d, 1, "ilu_solve_S", slot); };
-  // SolverCG on negative_S_tilde with tolerance tol * |b| (Prec.hpp:179-182,388-390,500-502): one persistent launch where the
-  // layout allows it (nsx_cg.hip), else the launch-per-operation solver above
-  auto cg_S = [&](double *x, const double *b) {
-    int steps = 0, status = 0;
-    double last = 0.0;
-    if (cg_schur_persistent(h, x, b, tol, maxit, &steps, &last, &status)) return SolveResult{status, steps, last};
-    if (cg_schur_fused(h, x, b, tol, maxit, &steps, &last, &status)) return SolveResult{status, steps, last};  // distributed, or too many blocks for a resident grid: two launches per iteration
-    h->cg_last_path = 1;
-    return cg(h, Sm, x, b, PS, n_p, len_p, tol * norm2(h, n_p, b), maxit, &PSdot);
-  };
+  auto cg_S = [&](double *x, const double *b) { return schur_cg(h, tol, maxit, x, b); };  // SolverCG on negative_S_tilde with tolerance tol * |b|
 
   if (type == NSX_PREC_YOSIDA) {  // Prec.hpp:365-408
     Tmp yu(h, len_u), yp(h, len_p), tmp(h, len_p), tmp2(h, len_u), res(h, len_u);
@@ -661,6 +673,25 @@ int nsx_inner_F_vmult(nsx_handle *h, double *dst, const double *src) {
     h->inner_F_fp32_used = 0;
     nsx::spmv_F_inner(h, s.p(), d.p());
     nsx::part_to_caller(h, 0, d.p(), dst);
+  })
+}
+
+int nsx_schur_cg(nsx_handle *h, double rtol, int maxiter, double *x, const double *b, int *steps, double *last_residual, int *status) {
+  NSX_API_BODY(h, {
+    if (!x || !b || !steps || !last_residual || !status) NSX_THROW(NSX_ERR_ARG, "null argument");
+    if (!h->prec_ready) NSX_THROW(NSX_ERR_ARG, "no Schur complement and no factors: call nsx_prec_initialize first");
+    HIP_CHECK(hipSetDevice(h->prm.device));
+    nsx::Tmp xd(h, h->len_p), bd(h, h->len_p);
+    nsx::pressure_from_caller(h, xd.p(), x);
+    nsx::pressure_from_caller(h, bd.p(), b);
+    h->defer_red = false;
+    h->pending_red.clear();
+    const nsx::SolveResult r = nsx::schur_cg(h, rtol, maxiter, xd.p(), bd.p());
+    *steps = r.steps;
+    *last_residual = r.last;
+    *status = r.status;
+    nsx::pressure_to_caller(h, xd.p(), x);
+    nsx::ilu_check(h);
   })
 }
 

@@ -25,7 +25,7 @@ API = [
     "nsx_profile_enable", "nsx_profile_reset", "nsx_profile_count", "nsx_profile_get", "nsx_persistent_state", "nsx_path_info", "nsx_comm_self_halo_test", "nsx_comm_unique_id",
     "nsx_comm_init", "nsx_comm_init_callbacks", "nsx_comm_counters", "nsx_set_mesh_distributed", "nsx_set_force_faces", "nsx_compute_forces",
     "nsx_set_internal_layout", "nsx_layout_info", "nsx_layout_get", "nsx_gram_schmidt_cycle", "nsx_set_inner_precision",
-    "nsx_gram_schmidt_sweeps", "nsx_compute_diagnostics", "nsx_get_cell_diagnostic",
+    "nsx_gram_schmidt_sweeps", "nsx_compute_diagnostics", "nsx_get_cell_diagnostic", "nsx_schur_cg",
 ]
 # declared in include/nsx.h as well, but with a capital letter in its name, which the header scan of tests/test_abi.py (lower case only)
 # does not see: kept beside the list that scan is compared with; build() checks both
@@ -123,6 +123,7 @@ def lib():
     L.nsx_get_cell_diagnostic.argtypes = [vp, C.c_int, _f64p]
     L.nsx_set_inner_precision.argtypes = [vp, C.c_int]
     L.nsx_inner_F_vmult.argtypes = [vp, _f64p, _f64p]
+    L.nsx_schur_cg.argtypes = [vp, C.c_double, C.c_int, _f64p, _f64p, C.POINTER(C.c_int), _f64p, C.POINTER(C.c_int)]
     L._nsx_ready = True
     return L
 
@@ -236,7 +237,7 @@ class Nsx:
                  "sweep_entries_per_thread_max", "cus_reserved", "schur_cg_path", "schur_blocks", "neighbours", "nodes_sent_per_exchange", "ghost_nodes",
                  "schur_dense_inverses", "sweep_off", "fallbacks", "rccl_sweep_velocity_plain", "rccl_sweep_velocity_masked", "rccl_sweep_block_plain",
                  "rccl_sweep_block_masked", "schur_blocks_per_partial", "sweep_velocity_one_gpu", "owned_p2_nodes", "owned_p1_nodes", "sweep_with_ilu_inside", "fused_launches",
-                 "inner_F_fp32", "ilu_F_fp32")
+                 "inner_F_fp32", "ilu_F_fp32", "schur_cg_rows_per_lane_group", "schur_cg_operator_in_lds")
 
     def path_info(self):
         """dict: which code paths the handle's products and solves take (nsx_path_info; schur_cg_path: 1 launch per operation,
@@ -405,6 +406,22 @@ class Nsx:
         dst = np.empty_like(src)
         self._ck(self.L.nsx_ilu_apply(self._h, which, _d(dst), _d(src)))
         return dst
+
+    def schur_cg(self, b, x0=None, rtol=1e-2, maxiter=100000):
+        """nsx_schur_cg: one CG solve of negative_S_tilde x = b from the guess x0 (default 0) with tolerance rtol * |b|, by the function
+        the preconditioners call (after prec_initialize).  Returns (x, steps, last_residual, status); status 0 converged, 1 not.
+        Vectors of length n_p in the caller's numbering; in a multi-process run globally indexed, every rank calls, and the entries of x
+        this rank does not own come back as 0 (sum over the ranks for the whole vector)."""
+        b = _cd(b)
+        x = np.zeros_like(b) if x0 is None else _cd(x0).copy()
+        assert b.shape == (self.n_p,) and x.shape == (self.n_p,)
+        steps, status, last = C.c_int(), C.c_int(), C.c_double()
+        self._ck(self.L.nsx_schur_cg(self._h, float(rtol), int(maxiter), _d(x), _d(b), C.byref(steps), C.byref(last), C.byref(status)))
+        if self.world > 1:
+            lo, hi = int(self.view["gpu_p_ptr"][self.rank]), int(self.view["gpu_p_ptr"][self.rank + 1])
+            x[:lo] = 0.0
+            x[hi:] = 0.0
+        return x, steps.value, last.value, status.value
 
     def gram_schmidt_cycle(self, vectors, norm_guard=-1.0):
         """nsx_gram_schmidt_cycle: (orthonormalised vectors, coefficients [m][m], |w|^2 after each sweep)"""

@@ -71,7 +71,9 @@ def test_binding_declares_the_inner_precision_interface():
     from navierstokes_project_nm4pde_amd import nsx
     assert (nsx.INNER_FP64, nsx.INNER_FP32) == (0, 1)
     assert "nsx_set_inner_precision" in nsx.API and "nsx_inner_F_vmult" in nsx.API + nsx.API_EXTRA
-    assert nsx.Nsx.PATH_KEYS[26:28] == ("inner_F_fp32", "ilu_F_fp32") and len(nsx.Nsx.PATH_KEYS) == 28
+    assert nsx.Nsx.PATH_KEYS[26:28] == ("inner_F_fp32", "ilu_F_fp32")
+    # (slots 28 and 29 report the persistent Schur CG's variant since the hook nsx_schur_cg exists)
+    assert nsx.Nsx.PATH_KEYS[28:] == ("schur_cg_rows_per_lane_group", "schur_cg_operator_in_lds") and len(nsx.Nsx.PATH_KEYS) == 30
     for name in ("set_inner_precision", "inner_F_vmult"):
         assert callable(getattr(nsx.Nsx, name))
     hdr = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "nsx.h")).read()
