@@ -251,13 +251,27 @@ struct MultiArgs {
   double c[32];
   int k;
 };
-__global__ void k_axpy_multi(int n, int split, int gap, double *__restrict__ x, MultiArgs m) {
+// START: where the sum starts from.  AX_SELF: x itself.  AX_FROM: x0 (x is only written).  AX_ZERO: 0.0 -- what reading a zeroed x gives,
+// with the same chain of fused multiply-adds behind it.  y (AX_ZERO only, may alias x): x = -y + s, the caller's sadd(-1, s) applied to
+// the double s the plain kernel would have stored.
+enum { AX_SELF = 0, AX_FROM = 1, AX_ZERO = 2 };
+template <int START>
+__device__ __forceinline__ void axpy_multi_entries(int n, int split, int gap, double *x, const double *x0, const double *y, const MultiArgs &m) {
   for (int i0 = blockIdx.x * 256 + threadIdx.x; i0 < n; i0 += gridDim.x * 256) {
     const int i = i0 + (i0 >= split ? gap : 0);
-    double s = x[i];
+    double s = START == AX_ZERO ? 0.0 : START == AX_FROM ? x0[i] : x[i];
     for (int j = 0; j < m.k; ++j) s += m.c[j] * m.v[j][i];  // same order as the reference's x.add(h(i), tmp_vectors[i]) loop
-    x[i] = s;
+    x[i] = (START == AX_ZERO && y) ? -y[i] + s : s;
   }
+}
+__global__ void k_axpy_multi(int n, int split, int gap, double *__restrict__ x, MultiArgs m) {
+  axpy_multi_entries<AX_SELF>(n, split, gap, x, nullptr, nullptr, m);
+}
+__global__ void k_axpy_multi_from(int n, int split, int gap, double *__restrict__ x, const double *__restrict__ x0, MultiArgs m) {
+  axpy_multi_entries<AX_FROM>(n, split, gap, x, x0, nullptr, m);
+}
+__global__ void k_axpy_multi_zero(int n, int split, int gap, double *x, const double *y, MultiArgs m) {
+  axpy_multi_entries<AX_ZERO>(n, split, gap, x, nullptr, y, m);
 }
 // CG update (SolverCG): x += alpha d ; g += alpha h ; partial(g.g), alpha = value(gh) / value(dh)
 __global__ __launch_bounds__(256) void k_cg_update(int n, double *__restrict__ x, const double *__restrict__ dvec, double *__restrict__ g,
@@ -316,6 +330,22 @@ void v_axpy_multi(nsx_handle *h, Span sp, double *x, int k, double *const *vs, c
     LaunchScope ls(h, "axpy_multi", 8.0 * n * (2 + m.k));
     hipLaunchKernelGGL(k_axpy_multi, dim3(ew_blocks(n)), dim3(256), 0, h->stream, n, sp.split, sp.gap, x, m);
   }
+}
+
+// The same update when x does not hold its starting value yet (k <= 32): x = x0 + sum (x0 != nullptr), or x = sum (x0 == nullptr: the
+// starting value is zero), the latter optionally followed by x = -y + x (y may be x itself).  One launch; x is only written.
+void v_axpy_multi_into(nsx_handle *h, Span sp, double *x, const double *x0, const double *y, int k, double *const *vs, const double *coef) {
+  if (k > 32 || (x0 && y)) NSX_THROW(NSX_ERR_ARG, "internal: v_axpy_multi_into takes one launch's worth of vectors, and y only with a zero start");
+  const int n = sp.n;
+  MultiArgs m;
+  m.k = k;
+  for (int j = 0; j < k; ++j) {
+    m.v[j] = vs[j];
+    m.c[j] = coef[j];
+  }
+  LaunchScope ls(h, "axpy_multi", 8.0 * n * (1 + (x0 ? 1 : 0) + (y ? 1 : 0) + k));
+  if (x0) hipLaunchKernelGGL(k_axpy_multi_from, dim3(ew_blocks(n)), dim3(256), 0, h->stream, n, sp.split, sp.gap, x, x0, m);
+  else hipLaunchKernelGGL(k_axpy_multi_zero, dim3(ew_blocks(n)), dim3(256), 0, h->stream, n, sp.split, sp.gap, x, y, m);
 }
 
 // SolverCG helpers

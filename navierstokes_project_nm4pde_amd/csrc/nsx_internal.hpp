@@ -435,12 +435,13 @@ void diag_mesh_setup(nsx_handle *h);  // with every mesh set-up: which cells thi
 
 // sparse (nsx_sparse.hip)
 bool blocked_usable(const nsx_handle *h);                                                   // F->vmult goes through the LDS-staged SpMV
-void spmv_F(nsx_handle *h, const double *vals, const double *x, double *y, const float *vals32 = nullptr);  // y_u = A x_u   (dim comps)
+void spmv_F(nsx_handle *h, const double *vals, const double *x, double *y, const float *vals32 = nullptr, const double *rb = nullptr);  // y_u = A x_u   (dim comps); rb: y_u = rb - A x_u
 void spmv_F_inner(nsx_handle *h, const double *x, double *y);  // F->vmult inside a preconditioner's vmult: F in the handle's inner precision
+void spmv_F_inner_resid(nsx_handle *h, const double *x, const double *b, double *y);  // y = b - F x: the product with the subtraction as each row's epilogue
 void convert_F_f32(nsx_handle *h);                             // vF32 = (float)vF
 void spmv_saddle(nsx_handle *h, const double *x, double *y);                                // full block vmult
 void spmv_G(nsx_handle *h, const double *xp, double *yu, bool accumulate);                  // y_u (+)= block(0,1) x_p
-void spmv_B(nsx_handle *h, const double *xu, double *yp);                                   // y_p = block(1,0) x_u
+void spmv_B(nsx_handle *h, const double *xu, double *yp, const double *r = nullptr, int sub = 0);  // y_p = block(1,0) x_u; r: y_p = (block(1,0) x_u) - r (sub = 1) or r - (block(1,0) x_u) (sub = -1)
 void spmv_S(nsx_handle *h, const double *x, double *y);                                     // y = negative_S x
 void schur_numeric(nsx_handle *h, const double *w);                                         // S = B diag(w) G
 void ilu_factor(nsx_handle *h, const DevCsr &g, IluSchedule &s, const double *vals, double *lu, const char *name, bool f32 = false);
@@ -501,6 +502,8 @@ bool v_mgs(nsx_handle *h, Span n, double *w, int dim, double *const *vs, int slo
 // consider: also out[dim+1] = |w|^2 BEFORE the sweep (SolverGMRES' re-orthogonalisation test); a single-launch sweep then
 // normalises w only if the test does not ask for a second sweep.
 void v_axpy_multi(nsx_handle *h, Span n, double *x, int k, double *const *vs, const double *coef_host);
+// x = x0 + sum (x0 == nullptr: x = sum, then optionally x = -y + x) in one launch that only writes x; k <= 32
+void v_axpy_multi_into(nsx_handle *h, Span n, double *x, const double *x0, const double *y, int k, double *const *vs, const double *coef_host);
 void finalize_slots(nsx_handle *h, int slot0, int count);
 // for kernels that leave nb <= 512 per-workgroup partial sums of a scalar themselves: where to put them, and the
 // bookkeeping (and the all-reduce of a distributed run) once the kernel is launched
@@ -547,7 +550,7 @@ void write_scalar(nsx_handle *h, int slot, double v);
 void prec_initialize(nsx_handle *h, int type);
 void prec_confirm(nsx_handle *h);  // after the synchronisation behind prec_initialize: ilu_check + the Schur values become reusable
 void prec_vmult(nsx_handle *h, int type, double inner_rtol, int inner_maxiter, double *dst, const double *src,
-                nsx_solve_stats *st);
+                nsx_solve_stats *st, bool fused);  // fused: NSX_STEP_FUSED as the calling entry of the API read it
 void solve_time_step(nsx_handle *h, int type, double tol, double inner_rtol, int maxiter, int inner_maxiter,
                      nsx_solve_stats *st);
 

@@ -83,7 +83,24 @@ static int sc_check(int step, double value, double tol, int maxsteps) {  // Solv
 static double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 constexpr int N_TMP = 30;  // SolverGMRES::AdditionalData::max_n_tmp_vectors
-enum { S_H = 8 /* 8..8+N_TMP */, S_NRM = 40, S_H2 = 41 /* re-orthogonalisation coefficients 41..41+N_TMP */, S_DH = 2, S_GH = 3, S_RES = 4, S_GH2 = 5 /* S_RES sits between the two g.h slots: whichever is current, the pair is adjacent */, S_T = 6 };
+enum { S_H = 8 /* 8..8+N_TMP */, S_NRM = 40, S_H2 = 41 /* re-orthogonalisation coefficients 41..41+N_TMP */, S_DH = 2, S_GH = 3, S_RES = 4, S_GH2 = 5 /* S_RES sits between the two g.h slots: whichever is current, the pair is adjacent */,
+       S_T = 39 /* |b|^2 of a relative tolerance: next to S_NRM, the two travel to the host in one publication (Seams::rtol) */ };
+
+// The seams between an inner solve and the vector operations its caller wraps around it (NSX_STEP_FUSED, prec_vmult): what the solver
+// does in launches it has anyway instead of the caller in launches of its own.  Every one leaves bit for bit the doubles of the
+// separate launches: an epilogue is applied to a value only after it has been rounded to the double those store.
+using ResidOp = std::function<void(double *dst, const double *x, const double *b)>;  // dst = b - A x
+struct Seams {
+  // the tolerance is rtol * |b|: the caller has enqueued |b|^2 into S_T; it is collected together with the first residual norm,
+  // behind the first residual / preconditioner / dot of the solve, instead of in a host round trip of its own in front of them
+  double rtol = -1.0;
+  const ResidOp *A_resid = nullptr;  // the residual of a cycle from the product's own launch
+  const double *x0 = nullptr;        // x's starting value lives here (x itself is only written: by the first update, x = x0 + sum)
+  // x_is_zero solves: the caller has NOT zeroed x, the first update stores the sum alone (what adding it to a zeroed x gives).
+  double *neg_out = nullptr;         // ... and if the solve ends in its first cycle: neg_out = -neg_out + x without x ever being stored
+  bool x_written = false;            // out: an update has stored x (false: x is untouched, its value is still x0 / zero)
+  bool neg_done = false;             // out: neg_out holds -neg_out + x
+};
 
 // SolverGMRES<VectorType>::solve (left preconditioning, default residual).
 // zero_new: a freshly created Epetra vector is zero.  That only matters when the preconditioner READS its destination
@@ -99,8 +116,10 @@ enum { S_H = 8 /* 8..8+N_TMP */, S_NRM = 40, S_H2 = 41 /* re-orthogonalisation c
 // launch of the sweep that follows them (v_mgs with ilu_rhs, k_ilu_mgs) where the layout allows it -- the preconditioned vector never
 // travels through memory between the two; only the operator of the next iteration is enqueued ahead.
 static SolveResult gmres(nsx_handle *h, const Op &A, double *x, const double *b, const Op &P, Span n, int len, double tol, int maxiter,
-                         bool zero_new = false, bool x_is_zero = false, bool plain_P = false, bool P_is_ilu_F = false) {
+                         bool zero_new = false, bool x_is_zero = false, bool plain_P = false, bool P_is_ilu_F = false, Seams *sm = nullptr) {
   SolveResult res{1, 0, 0.0};
+  const bool zero_start = x_is_zero;
+  bool first_cycle = true;
   std::vector<std::unique_ptr<Tmp>> tmp(N_TMP);
   auto vec = [&](int i) -> double * {
     if (!tmp[i]) {
@@ -140,12 +159,23 @@ static SolveResult gmres(nsx_handle *h, const Op &A, double *x, const double *b,
       P(v, b);  // the residual b - A 0 is b itself: the preconditioner reads it where it is (p is only a temporary)
       x_is_zero = false;
     } else {
-      A(p, x);
-      v_sadd(h, n, p, -1., 1., b);
+      const double *xin = sm && sm->x0 && !sm->x_written ? sm->x0 : x;
+      if (sm && sm->A_resid) (*sm->A_resid)(p, xin, b);
+      else {
+        A(p, xin);
+        v_sadd(h, n, p, -1., 1., b);
+      }
       P(v, p);
     }
     v_dot(h, n, v, v, S_NRM);
-    double rho = std::sqrt(read_scalar(h, S_NRM));
+    double rho;
+    if (first_cycle && sm && sm->rtol >= 0.0) {
+      double two[2];
+      read_scalars(h, S_T, 2, two);
+      static_assert(S_NRM == S_T + 1, "one publication");
+      tol = sm->rtol * std::sqrt(two[0]);
+      rho = std::sqrt(two[1]);
+    } else rho = std::sqrt(read_scalar(h, S_NRM));
     res.last = rho;
     state = sc_check(accumulated, rho, tol, maxiter);
     if (state != 0) break;
@@ -247,7 +277,19 @@ static SolveResult gmres(nsx_handle *h, const Op &A, double *x, const double *b,
     }
     double *vs[N_TMP];
     for (int i = 0; i < dim; ++i) vs[i] = vec(i);
-    v_axpy_multi(h, n, x, dim, vs, y);
+    if (sm && zero_start && first_cycle) {  // x is zero and has not been stored: the sum alone, and the caller's sadd with it if this is the end
+      double *out = (sm->neg_out && state != 0) ? sm->neg_out : x;
+      v_axpy_multi_into(h, n, out, nullptr, out == x ? nullptr : sm->neg_out, dim, vs, y);
+      if (out == x) sm->x_written = true;
+      else sm->neg_done = true;
+    } else if (sm && sm->x0 && !sm->x_written) {
+      v_axpy_multi_into(h, n, x, sm->x0, nullptr, dim, vs, y);
+      sm->x_written = true;
+    } else {
+      v_axpy_multi(h, n, x, dim, vs, y);
+      if (sm) sm->x_written = true;
+    }
+    first_cycle = false;
   } while (state == 0);
   res.status = state == 1 ? 0 : 1;
   res.steps = accumulated;
@@ -449,7 +491,11 @@ static void count(nsx_solve_stats *st, bool F, const SolveResult &r) {
   if (r.status) st->status = 2;
 }
 
-void prec_vmult(nsx_handle *h, int type, double tol, int maxit, double *dst, const double *src, nsx_solve_stats *st) {
+// NSX_STEP_FUSED=0: the launch sequence that follows the reference statement by statement.  Read once per call of the API
+// (solve_time_step, nsx_prec_vmult) and handed down: whether new basis vectors are zeroed and what prec_vmult overwrites must agree.
+static bool step_fused() { return !(getenv("NSX_STEP_FUSED") && atoi(getenv("NSX_STEP_FUSED")) == 0); }
+
+void prec_vmult(nsx_handle *h, int type, double tol, int maxit, double *dst, const double *src, nsx_solve_stats *st, bool fused) {
   if (!h->prec_ready) NSX_THROW(NSX_ERR_ARG, "preconditioner not initialised");
   const int n_u = h->n_u, n_p = h->n_p, dim = h->dim, len_u = h->len_u, len_p = h->len_p;
   const double *src_u = src, *src_p = src + h->off_p;
@@ -463,55 +509,101 @@ void prec_vmult(nsx_handle *h, int type, double tol, int maxit, double *dst, con
     if (used) h->ilu_F_fp32_used = 1;
   };
   auto cg_S = [&](double *x, const double *b) { return schur_cg(h, tol, maxit, x, b); };  // SolverCG on negative_S_tilde with tolerance tol * |b|
+  const ResidOp Fr = [h](double *d, const double *x, const double *b) { spmv_F_inner_resid(h, x, b, d); };
+  // SolverGMRES on F with tolerance tol * |b| and the velocity ILU(0).  sm (fused): |b|^2 is enqueued here and collected with the
+  // solve's first residual norm, the residual of a cycle comes from the product's own launch, and what else the caller has set in sm
+  auto solve_F = [&](double *x, const double *b, bool x_is_zero, Seams *sm) {
+    if (!sm) return count(st, true, gmres(h, Fm, x, b, PF, n_u, len_u, tol * norm2(h, n_u, b), maxit, false, x_is_zero, true, true));
+    sm->rtol = tol;
+    sm->A_resid = &Fr;
+    v_dot(h, n_u, b, b, S_T);
+    count(st, true, gmres(h, Fm, x, b, PF, n_u, len_u, 0.0, maxit, false, x_is_zero, true, true, sm));
+  };
+  // the first velocity solve of Yosida / SIMPLE: F x = src_u from x = src_u.  Fused, x is dst_u and only written: the first product
+  // reads src_u, the first update writes dst_u = src_u + sum
+  auto solve_F_from_src = [&](double *x) {
+    if (!fused) return solve_F(x, src_u, false, nullptr);
+    Seams sm;
+    sm.x0 = src_u;
+    solve_F(x, src_u, false, &sm);
+    if (!sm.x_written) v_copy(h, n_u, x, src_u);  // converged as it stands
+  };
+  // out = block(1,0) x - r (sign 1) or r - block(1,0) x (sign -1): fused the epilogue of the product, else add / sadd behind it
+  auto B_and_sub = [&](const double *x, double *out, const double *r, int sign) {
+    if (fused) return spmv_B(h, x, out, r, sign);
+    spmv_B(h, x, out);
+    if (sign > 0) v_add(h, n_p, out, -1.0, r);
+    else v_sadd(h, n_p, out, -1.0, 1.0, r);
+  };
+  // Yosida / SIMPLE solve in temporaries and copy back; fused they solve in dst itself (the copies below then have equal arguments)
+  std::unique_ptr<Tmp> own_u, own_p;
+  double *yu = dst_u, *yp = dst_p;
+  if (!fused && (type == NSX_PREC_YOSIDA || type == NSX_PREC_SIMPLE)) {
+    own_u = std::make_unique<Tmp>(h, len_u);
+    own_p = std::make_unique<Tmp>(h, len_p);
+    yu = own_u->p();
+    yp = own_p->p();
+  }
 
   if (type == NSX_PREC_YOSIDA) {  // Prec.hpp:365-408
-    Tmp yu(h, len_u), yp(h, len_p), tmp(h, len_p), tmp2(h, len_u), res(h, len_u);
-    v_copy(h, n_u, yu.p(), src_u);                                                            // :375
-    v_copy(h, n_p, yp.p(), src_p);                                                            // :376
-    count(st, true, gmres(h, Fm, yu.p(), src_u, PF, n_u, len_u, tol * norm2(h, n_u, src_u), maxit, false, false, true, true)); // :371-382
-    spmv_B(h, yu.p(), tmp.p());                                                               // :385
-    v_add(h, n_p, tmp.p(), -1.0, src_p);                                                      // :386
-    count(st, false, cg_S(yp.p(), tmp.p()));                                                  // :388-390
-    v_copy(h, n_p, dst_p, yp.p());                                                            // :394
+    Tmp tmp(h, len_p), tmp2(h, len_u), res(h, len_u);
+    if (!fused) v_copy(h, n_u, yu, src_u);                                                    // :375
+    v_copy(h, n_p, yp, src_p);                                                                // :376
+    solve_F_from_src(yu);                                                                     // :371-382
+    B_and_sub(yu, tmp.p(), src_p, 1);                                                         // :385-386
+    count(st, false, cg_S(yp, tmp.p()));                                                      // :388-390
+    v_copy(h, n_p, dst_p, yp);                                                                // :394
     spmv_G(h, dst_p, tmp2.p(), false);                                                        // :398
-    v_zero(h, n_u, res.p());                                                                  // :401
-    v_copy(h, n_u, dst_u, yu.p());                                                            // :402
-    count(st, true, gmres(h, Fm, res.p(), tmp2.p(), PF, n_u, len_u, tol * norm2(h, n_u, tmp2.p()), maxit, false, true, true, true));  // :403-405
-    v_sadd(h, n_u, dst_u, -1., 1., res.p());  // dst.block(0).sadd(-1,res): dst = -dst + res            :406
+    Seams sm;
+    sm.neg_out = dst_u;  // fused: no fill of res, and dst_u = -dst_u + res by the solve's update if it ends in its first cycle
+    if (!fused) v_zero(h, n_u, res.p());                                                      // :401
+    v_copy(h, n_u, dst_u, yu);                                                                // :402
+    solve_F(res.p(), tmp2.p(), true, fused ? &sm : nullptr);                                  // :403-405
+    if (!sm.neg_done) {  // fused: more than one cycle (res holds the solution) or none (it is zero)
+      if (fused && !sm.x_written) v_zero(h, n_u, res.p());
+      v_sadd(h, n_u, dst_u, -1., 1., res.p());  // dst.block(0).sadd(-1,res): dst = -dst + res            :406
+    }
   } else if (type == NSX_PREC_SIMPLE) {  // Prec.hpp:151-205
-    Tmp sol1_u(h, len_u), sol1_p(h, len_p), temp_1(h, len_p), tmp(h, len_u);
-    v_copy(h, n_u, sol1_u.p(), src_u);                                                             // :168
-    v_copy(h, n_p, sol1_p.p(), src_p);                                                             // :169
-    count(st, true, gmres(h, Fm, sol1_u.p(), src_u, PF, n_u, len_u, tol * norm2(h, n_u, src_u), maxit, false, false, true, true));  // :157-173
-    spmv_B(h, sol1_u.p(), temp_1.p());                                                             // :175
-    v_add(h, n_p, temp_1.p(), -1.0, src_p);                                                        // :176
-    count(st, false, cg_S(sol1_p.p(), temp_1.p()));                                               // :179-182
-    v_copy(h, n_p, dst_p, sol1_p.p());                                                             // :194
+    Tmp temp_1(h, len_p), tmp(h, len_u);
+    if (!fused) v_copy(h, n_u, yu, src_u);                                                         // :168
+    v_copy(h, n_p, yp, src_p);                                                                     // :169
+    solve_F_from_src(yu);                                                                          // :157-173
+    B_and_sub(yu, temp_1.p(), src_p, 1);                                                           // :175-176
+    count(st, false, cg_S(yp, temp_1.p()));                                                        // :179-182
+    v_copy(h, n_p, dst_p, yp);                                                                     // :194
     v_scale(h, n_p, dst_p, 1. / 0.5);                                                              // :195, alpha = 0.5 (:207)
-    v_copy(h, n_u, dst_u, sol1_u.p());                                                             // :199
+    v_copy(h, n_u, dst_u, yu);                                                                     // :199
     spmv_G(h, dst_p, tmp.p(), false);                                                              // :201
     v_scale_vec(h, n_u, tmp.p(), h->diag_D_inv.p);                                                 // :202
     v_add(h, n_u, dst_u, -1.0, tmp.p());                                                           // :203
   } else if (type == NSX_PREC_ASIMPLE) {  // Prec.hpp:254-311 (dst is the caller's vector: its content is the initial guess)
     Tmp tmp_u(h, len_u), tmp_p(h, len_p);
-    count(st, true, gmres(h, Fm, dst_u, src_u, PF, n_u, len_u, tol * norm2(h, n_u, src_u), maxit, false, false, true, true));  // :271-273
-    spmv_B(h, dst_u, dst_p);                                                                   // :280
-    v_sadd(h, n_p, dst_p, -1.0, 1.0, src_p);                                                   // :281
+    Seams sm, ss;
+    solve_F(dst_u, src_u, false, fused ? &sm : nullptr);                                       // :271-273
+    B_and_sub(dst_u, dst_p, src_p, -1);                                                        // :280-281
     v_copy(h, n_p, tmp_p.p(), dst_p);                                                          // :282
-    count(st, false, gmres(h, Sm, dst_p, tmp_p.p(), PS, n_p, len_p, tol * norm2(h, n_p, tmp_p.p()), maxit));  // :287-289
+    if (fused) {                                                                               // :287-289
+      ss.rtol = tol;
+      v_dot(h, n_p, tmp_p.p(), tmp_p.p(), S_T);
+      count(st, false, gmres(h, Sm, dst_p, tmp_p.p(), PS, n_p, len_p, 0.0, maxit, false, false, false, false, &ss));
+    } else count(st, false, gmres(h, Sm, dst_p, tmp_p.p(), PS, n_p, len_p, tol * norm2(h, n_p, tmp_p.p()), maxit));
     v_scale_vec(h, n_u, dst_u, h->diag_D.p);                                                   // :294
     v_scale(h, n_p, dst_p, 1. / 1.0);                                                          // :298, alpha = 1 (:328)
     spmv_G(h, dst_p, tmp_u.p(), false);                                                        // :304
     v_add(h, n_u, dst_u, -1.0, tmp_u.p());                                                     // :305
     v_scale_vec(h, n_u, dst_u, h->diag_D_inv.p);                                               // :309
   } else if (type == NSX_PREC_AYOSIDA) {  // Prec.hpp:474-517
-    Tmp tmp(h, len_u), tmp2(h, len_p), yu(h, len_u), yp(h, len_p), t(h, len_u);
-    v_copy(h, n_p, yp.p(), src_p);                    // :487
+    Tmp tmp(h, len_u), yu(h, len_u), yp(h, len_p), t(h, len_u);
     v_copy(h, n_u, tmp.p(), src_u);                   // :491
     v_scale_vec(h, n_u, tmp.p(), h->diag_D_inv.p);    // :492
     v_copy(h, n_u, yu.p(), tmp.p());                  // :493
-    spmv_B(h, tmp.p(), tmp2.p());                     // :496
-    v_sadd(h, n_p, yp.p(), -1.0, 1.0, tmp2.p());      // :497
+    if (fused) spmv_B(h, tmp.p(), yp.p(), src_p, 1);  // :487, :496-497 in one launch: yp = (B tmp) - src_p
+    else {
+      Tmp tmp2(h, len_p);
+      v_copy(h, n_p, yp.p(), src_p);                  // :487
+      spmv_B(h, tmp.p(), tmp2.p());                   // :496
+      v_sadd(h, n_p, yp.p(), -1.0, 1.0, tmp2.p());    // :497
+    }
     count(st, false, cg_S(dst_p, yp.p()));          // :500-502
     v_copy(h, n_p, yp.p(), dst_p);                    // :504
     spmv_F_inner(h, yu.p(), t.p());                   // :507 F->vmult(yu,yu): Epetra multiplies out of place when the arguments alias
@@ -545,9 +637,17 @@ void solve_time_step(nsx_handle *h, int type, double tol, double inner_rtol, int
   if (trace) fprintf(stderr, "[nsx trace] rank %d: solve_time_step: outer solve\n", h->rank);
   st->t_prec = now_s() - t0;
   t0 = now_s();
+  const bool fused = step_fused();
   Op A = [h](double *d, const double *s) { spmv_saddle(h, s, d); };
-  Op P = [h, type, inner_rtol, inner_maxiter, st](double *d, const double *s) { prec_vmult(h, type, inner_rtol, inner_maxiter, d, s, st); };
-  SolveResult r = gmres(h, A, h->sol_owned.p, h->rhs.p, P, n, h->len_blk, tol, maxiter, true);  // NS3D.cpp:574
+  Op P = [h, type, inner_rtol, inner_maxiter, st, fused](double *d, const double *s) { prec_vmult(h, type, inner_rtol, inner_maxiter, d, s, st, fused); };
+  // New basis vectors are zeroed only for the preconditioners that READ their destination: aSIMPLE (the initial guess of its velocity
+  // solve, Prec.hpp:271) and aYosida (the initial guess of its Schur CG, :500).  Yosida and SIMPLE overwrite every entry that a later
+  // kernel reads: the owned velocity entries by the first solve's update (k_axpy_multi_from, or the copy of src_u when that solve
+  // converges as it stands), the owned pressure entries by the copy of src_p the Schur CG starts from; ghost entries are written by the
+  // halo exchange in front of every product that reads them, and the BLAS-1 spans skip the gap between the two owned parts.  The
+  // operator's own temporary is overwritten row by row by the block product.
+  const bool zero_new = !fused || type == NSX_PREC_ASIMPLE || type == NSX_PREC_AYOSIDA;
+  SolveResult r = gmres(h, A, h->sol_owned.p, h->rhs.p, P, n, h->len_blk, tol, maxiter, zero_new);  // NS3D.cpp:574
   v_copy(h, h->len_blk, h->sol.p, h->sol_owned.p);  // solution = solution_owned (NS3D.cpp:638): copy + ghost import
   comm_halo_u(h, h->sol.p);
   comm_halo_p(h, h->sol.p + h->off_p);
@@ -619,7 +719,7 @@ int nsx_prec_vmult(nsx_handle *h, int prec_type, double inner_rtol, int inner_ma
     h->defer_red = false;
     h->pending_red.clear();
     h->inner_F_fp32_used = h->ilu_F_fp32_used = 0;
-    nsx::prec_vmult(h, prec_type, inner_rtol, inner_maxiter, d.p(), s.p(), stats);
+    nsx::prec_vmult(h, prec_type, inner_rtol, inner_maxiter, d.p(), s.p(), stats, nsx::step_fused());
     if (stats) stats->persistent_fallbacks = h->n_persistent_fallbacks;
     nsx::vec_to_caller(h, d.p(), dst);
     nsx::ilu_check(h);

@@ -35,12 +35,14 @@ __device__ __forceinline__ double group_sum(double v) {
 
 // ------------------------------------------------------------------ SpMV
 // y[i][c] = sum_j A[i,j] x[j][c]  (+ sum_k G[i,k][c] xp[k]);  W lanes per row.
-template <int DIM, int W, bool WITH_G>
-__global__ __launch_bounds__(256) void k_spmv_vel(int n_rows, const int32_t *__restrict__ rp, const int32_t *__restrict__ ci,
-                                                  const double *__restrict__ av, const double *__restrict__ x,
-                                                  const int32_t *__restrict__ grp, const int32_t *__restrict__ gci,
-                                                  const double *__restrict__ gv, const double *__restrict__ xp,
-                                                  double *__restrict__ y, const int32_t *__restrict__ rows) {
+// RESID (the residual of a Krylov cycle): y = b - (A x), the subtraction applied to the finished row sum -- the double the plain kernel
+// stores, so the result is bit for bit that of the product followed by sadd(-1, 1, b).
+template <int DIM, int W, bool WITH_G, bool RESID>
+__device__ __forceinline__ void spmv_vel_rows(int n_rows, const int32_t *__restrict__ rp, const int32_t *__restrict__ ci,
+                                              const double *__restrict__ av, const double *__restrict__ x,
+                                              const int32_t *__restrict__ grp, const int32_t *__restrict__ gci,
+                                              const double *__restrict__ gv, const double *__restrict__ xp,
+                                              double *__restrict__ y, const int32_t *__restrict__ rows, const double *__restrict__ b) {
   // rows: optional list of the rows to compute (n_rows of them): interior / interface split of a distributed product
   // XCD-aware mapping: workgroups are dealt round-robin over the 8 XCDs, so give XCD k the k-th contiguous eighth of the
   // rows: the x entries a row gathers are then shared inside one 4-MiB L2 instead of being fetched into all eight
@@ -71,8 +73,22 @@ __global__ __launch_bounds__(256) void k_spmv_vel(int n_rows, const int32_t *__r
   for (int c = 0; c < DIM; ++c) acc[c] = group_sum<W>(acc[c]);
   if (lane == 0) {
 #pragma unroll
-    for (int c = 0; c < DIM; ++c) y[(size_t)row * DIM + c] = acc[c];
+    for (int c = 0; c < DIM; ++c) y[(size_t)row * DIM + c] = RESID ? b[(size_t)row * DIM + c] - acc[c] : acc[c];
   }
+}
+template <int DIM, int W, bool WITH_G>
+__global__ __launch_bounds__(256) void k_spmv_vel(int n_rows, const int32_t *__restrict__ rp, const int32_t *__restrict__ ci,
+                                                  const double *__restrict__ av, const double *__restrict__ x,
+                                                  const int32_t *__restrict__ grp, const int32_t *__restrict__ gci,
+                                                  const double *__restrict__ gv, const double *__restrict__ xp,
+                                                  double *__restrict__ y, const int32_t *__restrict__ rows) {
+  spmv_vel_rows<DIM, W, WITH_G, false>(n_rows, rp, ci, av, x, grp, gci, gv, xp, y, rows, nullptr);
+}
+template <int DIM, int W>
+__global__ __launch_bounds__(256) void k_spmv_vel_resid(int n_rows, const int32_t *__restrict__ rp, const int32_t *__restrict__ ci,
+                                                        const double *__restrict__ av, const double *__restrict__ x, double *__restrict__ y,
+                                                        const int32_t *__restrict__ rows, const double *__restrict__ b) {
+  spmv_vel_rows<DIM, W, false, true>(n_rows, rp, ci, av, x, nullptr, nullptr, nullptr, nullptr, y, rows, b);
 }
 
 // y_u[i][c] (+)= sum_k G[i,k][c] xp[k]
@@ -104,10 +120,11 @@ __global__ __launch_bounds__(256) void k_spmv_G(int n_rows, const int32_t *__res
 }
 
 // y_p[i] = sum_j sum_c B[i,j][c] xu[j][c]
-template <int DIM, int W>
-__global__ __launch_bounds__(256) void k_spmv_B(int n_rows, const int32_t *__restrict__ rp, const int32_t *__restrict__ ci,
-                                                const double *__restrict__ bv, const double *__restrict__ xu,
-                                                double *__restrict__ y, const int32_t *__restrict__ rows) {
+// SUB: 0 the product; 1: y = (B xu) - r; -1: y = r - (B xu) -- add(-1, r) / sadd(-1, 1, r) applied to the finished row sum
+template <int DIM, int W, int SUB>
+__device__ __forceinline__ void spmv_B_rows(int n_rows, const int32_t *__restrict__ rp, const int32_t *__restrict__ ci,
+                                            const double *__restrict__ bv, const double *__restrict__ xu,
+                                            double *__restrict__ y, const int32_t *__restrict__ rows, const double *__restrict__ r) {
   const int slot = (blockIdx.x * 256 + threadIdx.x) / W, lane = threadIdx.x % W;
   if (slot >= n_rows) return;
   const int row = rows ? rows[slot] : slot;
@@ -119,7 +136,19 @@ __global__ __launch_bounds__(256) void k_spmv_B(int n_rows, const int32_t *__res
     for (int c = 0; c < DIM; ++c) acc += bv[(size_t)p * DIM + c] * xj[c];
   }
   acc = group_sum<W>(acc);
-  if (lane == 0) y[row] = acc;
+  if (lane == 0) y[row] = SUB > 0 ? acc - r[row] : SUB < 0 ? r[row] - acc : acc;
+}
+template <int DIM, int W>
+__global__ __launch_bounds__(256) void k_spmv_B(int n_rows, const int32_t *__restrict__ rp, const int32_t *__restrict__ ci,
+                                                const double *__restrict__ bv, const double *__restrict__ xu,
+                                                double *__restrict__ y, const int32_t *__restrict__ rows) {
+  spmv_B_rows<DIM, W, 0>(n_rows, rp, ci, bv, xu, y, rows, nullptr);
+}
+template <int DIM, int W, int SUB>
+__global__ __launch_bounds__(256) void k_spmv_B_sub(int n_rows, const int32_t *__restrict__ rp, const int32_t *__restrict__ ci,
+                                                    const double *__restrict__ bv, const double *__restrict__ xu,
+                                                    double *__restrict__ y, const int32_t *__restrict__ rows, const double *__restrict__ r) {
+  spmv_B_rows<DIM, W, SUB>(n_rows, rp, ci, bv, xu, y, rows, r);
 }
 
 template <int W>
@@ -158,10 +187,11 @@ __device__ int g_spmv_dbg = 0;  // what the traced launch leaves out: 1 the x ga
 // copy of F the inner solves read -- 4 B value + 2 B local column per non-zero; a value is widened to double in the register it arrives
 // in, so lanes, trips, row order and the grouping of every row's sum are those of the double kernel: the result is the double kernel's on
 // (double)(float)F up to nothing (same operations on the same operands in the same order).
-template <int DIM, int W, class VT>
+// RESID (k_spmv_blocked_resid, the residual of a Krylov cycle): y = b - (A x), the subtraction applied to the finished row sum.
+template <int DIM, int W, class VT, bool RESID = false>
 __device__ __forceinline__ void spmv_blocked_rows(int n_rows, const int32_t *__restrict__ desc, const int32_t *__restrict__ rp,
                                                   const uint16_t *__restrict__ lidx, const VT *__restrict__ av, const int32_t *__restrict__ ucols,
-                                                  const double *__restrict__ x, double *__restrict__ y) {
+                                                  const double *__restrict__ x, double *__restrict__ y, const double *__restrict__ b = nullptr) {
   extern __shared__ double xs[];
   __shared__ int rps[449];
   // launch order (SpmvBlocked::desc): workgroups are dealt round-robin over the 8 XCDs and XCD k takes a contiguous range of chunks, so
@@ -222,7 +252,7 @@ __device__ __forceinline__ void spmv_blocked_rows(int n_rows, const int32_t *__r
     for (int c = 0; c < DIM; ++c) acc[c] = group_sum<W>(acc[c]);
     if (lane == 0) {
 #pragma unroll
-      for (int c = 0; c < DIM; ++c) y[(size_t)rw * DIM + c] = acc[c];
+      for (int c = 0; c < DIM; ++c) y[(size_t)rw * DIM + c] = RESID ? b[(size_t)rw * DIM + c] - acc[c] : acc[c];
     }
   };
   // two register sets, no moves: while one row is reduced the loads of the next two are in flight
@@ -253,6 +283,12 @@ __global__ __launch_bounds__(256) void k_spmv_blocked(int n_rows, const int32_t 
                                                       double *__restrict__ y) {
   spmv_blocked_rows<DIM, W, double>(n_rows, desc, rp, lidx, av, ucols, x, y);
 }
+template <int DIM, int W>
+__global__ __launch_bounds__(256) void k_spmv_blocked_resid(int n_rows, const int32_t *__restrict__ desc, const int32_t *__restrict__ rp, const uint16_t *__restrict__ lidx,
+                                                            const double *__restrict__ av, const int32_t *__restrict__ ucols, const double *__restrict__ x,
+                                                            double *__restrict__ y, const double *__restrict__ b) {
+  spmv_blocked_rows<DIM, W, double, true>(n_rows, desc, rp, lidx, av, ucols, x, y, b);
+}
 #ifndef NSX_SPMV_F32_W
 #define NSX_SPMV_F32_W 16  // lanes per row of the float kernel (compile time; 16 = the double kernel's, the only value with its grouping of the sums)
 #endif
@@ -282,9 +318,23 @@ static double bytes_vel(nsx_handle *h, bool with_g, bool f32 = false) {
 }
 
 // ---- launches (rows == nullptr: all n rows)
-static void launch_vel(nsx_handle *h, bool with_g, const double *vals, const double *x, const double *xp, double *y, const int32_t *rows, int n) {
+// b (products without block(0,1) only): y = b - A x (k_spmv_vel_resid)
+static void launch_vel(nsx_handle *h, bool with_g, const double *vals, const double *x, const double *xp, double *y, const int32_t *rows, int n,
+                       const double *b = nullptr) {
   if (n <= 0) return;
   static const int Wsel = getenv("NSX_SPMV_W") ? atoi(getenv("NSX_SPMV_W")) : 16;
+  if (b) {
+#define NSX_SPMV_R(D, W_)                                                                                                               \
+  hipLaunchKernelGGL((k_spmv_vel_resid<D, W_>), dim3((cdiv((int64_t)n * W_, 256) + 7) & ~7), dim3(256), 0, h->stream, n, h->gA.rowptr.p, \
+                     h->gA.colind.p, vals, x, y, rows, b)
+    if (h->dim == 2) {
+      if (Wsel == 8) NSX_SPMV_R(2, 8); else if (Wsel == 32) NSX_SPMV_R(2, 32); else NSX_SPMV_R(2, 16);
+    } else {
+      if (Wsel == 8) NSX_SPMV_R(3, 8); else if (Wsel == 32) NSX_SPMV_R(3, 32); else NSX_SPMV_R(3, 16);
+    }
+#undef NSX_SPMV_R
+    return;
+  }
 #define NSX_SPMV(D, W_, G_)                                                                                                            \
   hipLaunchKernelGGL((k_spmv_vel<D, W_, G_>), dim3((cdiv((int64_t)n * W_, 256) + 7) & ~7), dim3(256), 0, h->stream, n, h->gA.rowptr.p, \
                      h->gA.colind.p, vals, x, h->gG.rowptr.p, h->gG.colind.p, h->vG.p, xp, y, rows)
@@ -297,8 +347,20 @@ static void launch_vel(nsx_handle *h, bool with_g, const double *vals, const dou
   }
 #undef NSX_SPMV
 }
-static void launch_B(nsx_handle *h, const double *xu, double *yp, const int32_t *rows, int n) {
+// r, sub = +-1: yp = B xu - r / r - B xu (k_spmv_B_sub)
+static void launch_B(nsx_handle *h, const double *xu, double *yp, const int32_t *rows, int n, const double *r = nullptr, int sub = 0) {
   if (n <= 0) return;
+  if (r) {
+#define NSX_B_SUB(D, W_, S_) \
+  hipLaunchKernelGGL((k_spmv_B_sub<D, W_, S_>), dim3(cdiv((int64_t)n * W_, 256)), dim3(256), 0, h->stream, n, h->gB.rowptr.p, h->gB.colind.p, h->vB.p, xu, yp, rows, r)
+    if (h->dim == 2) {
+      if (sub > 0) NSX_B_SUB(2, 32, 1); else NSX_B_SUB(2, 32, -1);
+    } else {
+      if (sub > 0) NSX_B_SUB(3, 64, 1); else NSX_B_SUB(3, 64, -1);
+    }
+#undef NSX_B_SUB
+    return;
+  }
   if (h->dim == 2)
     hipLaunchKernelGGL((k_spmv_B<2, 32>), dim3(cdiv((int64_t)n * 32, 256)), dim3(256), 0, h->stream, n, h->gB.rowptr.p, h->gB.colind.p, h->vB.p, xu, yp, rows);
   else
@@ -329,7 +391,8 @@ bool blocked_usable(const nsx_handle *h) {
 }
 // part 0: the table of a one-GPU handle / the chunks of a distributed handle whose staged columns are all owned; part 1: the chunks that
 // stage a ghost column (distributed handles only; an empty table launches nothing)
-static bool launch_blocked(nsx_handle *h, const double *vals, const double *x, double *y, int part = 0, const float *vals32 = nullptr) {
+// rb (double values only): y = rb - A x (k_spmv_blocked_resid)
+static bool launch_blocked(nsx_handle *h, const double *vals, const double *x, double *y, int part = 0, const float *vals32 = nullptr, const double *rb = nullptr) {
   const SpmvBlocked &b = h->blkA;
   if (!blocked_usable(h)) return false;
   const size_t shm = (size_t)b.max_ucols * h->dim * sizeof(double);
@@ -338,6 +401,13 @@ static bool launch_blocked(nsx_handle *h, const double *vals, const double *x, d
   if (grid == 0) return true;
 #define NSX_BLK(D) \
   hipLaunchKernelGGL((k_spmv_blocked<D, 16>), dim3(grid), dim3(256), shm, h->stream, h->N2, desc, h->gA.rowptr.p, b.lidx.p, vals, b.ucols.p, x, y)
+  if (rb) {
+    if (h->dim == 2)
+      hipLaunchKernelGGL((k_spmv_blocked_resid<2, 16>), dim3(grid), dim3(256), shm, h->stream, h->N2, desc, h->gA.rowptr.p, b.lidx.p, vals, b.ucols.p, x, y, rb);
+    else
+      hipLaunchKernelGGL((k_spmv_blocked_resid<3, 16>), dim3(grid), dim3(256), shm, h->stream, h->N2, desc, h->gA.rowptr.p, b.lidx.p, vals, b.ucols.p, x, y, rb);
+    return true;
+  }
   if (vals32) {  // the float stream: same chunks, same launch tables
     // NSX_SPMV_F32_W = 16 lanes per row as in the double kernel: the same lanes take the same entries, so every row's sum is grouped as
     // there.  -DNSX_SPMV_F32_W=32 / 8 (compile time, measurements only: another grouping of the sums) lets a lane group read 128 / 32
@@ -392,8 +462,10 @@ static double bytes_halo(const HaloPlan &p, int ncomp) {
 
 // vals32: the float copy of vals (the inner products of a handle in NSX_INNER_FP32).  Only the LDS-staged kernel has a float twin: where
 // it cannot be used the plain kernel reads the double values, and the handle does not report a float product (nsx_path_info [26]).
-void spmv_F(nsx_handle *h, const double *vals, const double *x, double *y, const float *vals32) {
+// rb: y = rb - A x in the same launches (double values only: the caller checks spmv_F_resid_fused)
+void spmv_F(nsx_handle *h, const double *vals, const double *x, double *y, const float *vals32, const double *rb) {
   if (vals32 && !blocked_usable(h)) vals32 = nullptr;
+  if (rb && vals32) NSX_THROW(NSX_ERR_ARG, "internal: the residual product has no float twin");
   const bool f32 = vals32 != nullptr;
   if (f32) h->inner_F_fp32_used = 1;
   if (h->dist) {
@@ -409,8 +481,8 @@ void spmv_F(nsx_handle *h, const double *vals, const double *x, double *y, const
     comm_halo_begin(h, h->haloU, xx, h->dim);
     {
       LaunchScope ls(h, "spmv_F", bytes_vel(h, false, f32) * (1.0 - frac_if));
-      if (blk) launch_blocked(h, vals, x, y, 0, vals32);
-      else launch_vel(h, false, vals, x, nullptr, y, h->splitA.interior.p, h->splitA.n_interior);
+      if (blk) launch_blocked(h, vals, x, y, 0, vals32, rb);
+      else launch_vel(h, false, vals, x, nullptr, y, h->splitA.interior.p, h->splitA.n_interior, rb);
     }
     {
       LaunchScope ls(h, "halo_u_wait", bytes_halo(h->haloU, h->dim));
@@ -418,32 +490,42 @@ void spmv_F(nsx_handle *h, const double *vals, const double *x, double *y, const
     }
     {
       LaunchScope ls(h, "spmv_F_if", bytes_vel(h, false, f32) * frac_if);
-      if (blk) launch_blocked(h, vals, x, y, 1, vals32);
-      else launch_vel(h, false, vals, x, nullptr, y, h->splitA.interface.p, h->splitA.n_interface);
+      if (blk) launch_blocked(h, vals, x, y, 1, vals32, rb);
+      else launch_vel(h, false, vals, x, nullptr, y, h->splitA.interface.p, h->splitA.n_interface, rb);
     }
     return;
   }
   LaunchScope ls(h, "spmv_F", bytes_vel(h, false, f32));
-  if (!launch_blocked(h, vals, x, y, 0, vals32)) launch_vel(h, false, vals, x, nullptr, y, nullptr, h->N2);
+  if (!launch_blocked(h, vals, x, y, 0, vals32, rb)) launch_vel(h, false, vals, x, nullptr, y, nullptr, h->N2, rb);
 }
 
 // F->vmult inside a preconditioner's vmult (the operator of the inner GMRES, Preconditioners.hpp:173,273,382,405; aYosida's :507)
 void spmv_F_inner(nsx_handle *h, const double *x, double *y) {
   spmv_F(h, h->vF.p, x, y, h->inner_precision == NSX_INNER_FP32 ? h->vF32.p : nullptr);
 }
+// y = b - F x, the residual of an inner solve's cycle, in the launches of the product.  Where the product streams the float copy of F
+// (no residual twin of that kernel) it is the product followed by the subtraction, as the solver does it on its own.
+void spmv_F_inner_resid(nsx_handle *h, const double *x, const double *b, double *y) {
+  if (h->inner_precision == NSX_INNER_FP32 && blocked_usable(h)) {
+    spmv_F_inner(h, x, y);
+    v_sadd(h, Span(h->n_u), y, -1., 1., b);
+    return;
+  }
+  spmv_F(h, h->vF.p, x, y, nullptr, b);
+}
 
 static double bytes_B(nsx_handle *h) { return (4.0 + 8.0 * h->dim) * h->gB.nnz() + 12.0 * h->NP + 8.0 * h->dim * h->N2; }
-void spmv_B(nsx_handle *h, const double *xu, double *yp) {
-  LaunchScope ls(h, "spmv_B", bytes_B(h));
+void spmv_B(nsx_handle *h, const double *xu, double *yp, const double *r, int sub) {
+  LaunchScope ls(h, "spmv_B", bytes_B(h) + (r ? 8.0 * h->NP : 0.0));
   if (h->dist) {
     double *xx = const_cast<double *>(xu);
     comm_halo_begin(h, h->haloU, xx, h->dim);
-    launch_B(h, xu, yp, h->splitB.interior.p, h->splitB.n_interior);
+    launch_B(h, xu, yp, h->splitB.interior.p, h->splitB.n_interior, r, sub);
     comm_halo_finish(h, h->haloU, xx, h->dim);
-    launch_B(h, xu, yp, h->splitB.interface.p, h->splitB.n_interface);
+    launch_B(h, xu, yp, h->splitB.interface.p, h->splitB.n_interface, r, sub);
     return;
   }
-  launch_B(h, xu, yp, nullptr, h->NP);
+  launch_B(h, xu, yp, nullptr, h->NP, r, sub);
 }
 
 void spmv_G(nsx_handle *h, const double *xp, double *yu, bool accumulate) {
