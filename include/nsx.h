@@ -266,6 +266,45 @@ int nsx_compute_diagnostics(nsx_handle *h, nsx_flow_diag *out);
  * NSX_ERR_ARG before any nsx_compute_diagnostics on the current mesh and for a `which` outside [0, NSX_DIAG_COUNT). */
 int nsx_get_cell_diagnostic(nsx_handle *h, int which, double *values);
 
+/* ---- point probes ---- */
+/* The finite-element solution at given points: NavierStokes::compute_pressure_difference (reference NavierStokes3D.cpp:849-923) is
+ * VectorTools::point_value on every rank -- a search of the mesh per call -- followed by a reduce.  Here the search is set-up and the per-step
+ * call gathers on the device; nothing is downloaded but the values.
+ * Containment: a point lies in a cell when all dim+1 barycentric coordinates are >= -tol, the coordinates being defined by x = X0 + J lambda
+ * with lambda_0 = 1 - sum_k lambda_k.  tol < 0: the library's own value, 1e-12 (the one nsxh_pressure_difference uses); 0 <= tol < 1 is taken
+ * as given.
+ * Ties: a point on a face, an edge or a vertex lies in several cells; the probe takes the one with the lowest position in the caller's cell
+ * list (the first hit in cell order, as nsxh_pressure_difference).  The choice depends on the mesh and the point only, not on
+ * nsx_set_ranks / nsx_set_internal_layout or on how the search is scheduled (an integer minimum: csrc/nsx_probe.hip).
+ * Not found: found = 0, cells = owners = -1 and all values exactly 0.0 -- the reference's rank that does not hold the point contributes 0.
+ * Lifetime: the set survives nsx_set_ranks and nsx_set_internal_layout (cells stay in the caller's order, the geometry is the same); a new
+ * nsx_set_mesh(_distributed) drops it; n_points = 0 clears it.
+ * Errors: NSX_ERR_ARG for a probe call before the mesh is set, a get / eval call without a probe set, n_points < 0, null points with
+ * n_points > 0, tol >= 1 and any coordinate that is not finite; NSX_ERR_UNSUPPORTED for n_points > 65536 and for a (dim, n_p2) other than
+ * (2, 6) / (3, 10).
+ * Distributed handles: all ranks call together, with the same points.  A rank searches only the cells it counts for the flow diagnostics, so a
+ * point inside a cell has exactly one finder; a point on a face shared by cells of two ranks goes to the lowest rank that found it.  Every rank
+ * receives the same owners and found, and BITWISE the same values: the owner's travel through the SUM collective with exact zeros from
+ * everybody else.  nsx_set_probes costs exactly one all-reduce, nsx_eval_probes exactly one, neither a ghost exchange (nsx_comm_counters). */
+
+/* Locate n_points points (points[n][dim]) in the mesh of nsx_set_mesh(_distributed) and keep them as the handle's probe set: the search
+ * VectorTools::point_value repeats at every call (reference NavierStokes3D.cpp:862-881), done once. */
+int nsx_set_probes(nsx_handle *h, int n_points, const double *points, double tol);
+/* cells[n]: position of the probe's cell in the caller's cell list (-1: not found, or another rank owns the probe).
+ * owners[n]: rank that evaluates it (-1: in no cell).  lambda[n][dim+1]: barycentric coordinates in that cell (0 where cells is -1).
+ * Any pointer may be NULL.  (The cell and the point on the reference cell that point_value works out inside: reference NavierStokes3D.cpp:864-865, 875-876.) */
+int nsx_get_probe_cells(nsx_handle *h, int32_t *cells, int32_t *owners, double *lambda);
+/* velocity[n][dim], pressure[n], gradient[n][dim][dim] (d_j u_i; may be NULL), found[n] (0/1) of the ghosted `solution` (current after
+ * nsx_set_solution and after nsx_solve_time_step): the point values and the reduce of reference NavierStokes3D.cpp:862-899.
+ * u_h = sum_a N_a(lambda) U_a with the P2 shape functions in barycentric form (vertices lambda (2 lambda - 1), lines 4 lambda_i lambda_j in the
+ * local line order {0,1},{1,2},{2,0}[,{0,3},{1,3},{2,3}]), p_h = sum_v lambda_v P_v, gradient = (sum_a U_a (x) grad_lambda N_a) J^-1 taken in
+ * the probe's own cell.  Velocity and pressure are continuous across cells; the gradient is NOT: on a face it is the value from the side of the
+ * cell the tie rule chose.  Any output pointer may be NULL.  A state value that is not finite propagates into the outputs of the probes whose
+ * cell holds it; the call still returns NSX_OK.
+ * Reads state only, like nsx_compute_diagnostics: no vector, matrix or solver state changes, a following solve computes what it would have
+ * computed without the call, and two calls give bitwise equal results. */
+int nsx_eval_probes(nsx_handle *h, double *velocity, double *pressure, double *gradient, int32_t *found);
+
 /* ---- measurement ---- */
 /* Per-kernel HIP-event timing of the hot path (bench.py roofline): enable, run, then read name/count/total-ms. */
 int nsx_profile_enable(nsx_handle *h, int on);

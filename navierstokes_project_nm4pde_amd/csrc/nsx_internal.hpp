@@ -10,6 +10,7 @@
 //   B-graph        P1 x P2 CSR, dim values per entry: block (1,0) = +int psi_k d_c phi_j   (NS3D.cpp:261)
 //   S-graph        P1 x P1 CSR = structural product B*G: negative_S_tilde and its ILU(0)   (Prec.hpp:144,358)
 //   cell tables    SoA: cell_n2[a][cell], cell_n1[v][cell], geo[k][cell] (J^-1 row-major, then |det J|)
+//                  cell_x0[d][cell] (vertex 0: x = X0 + J lambda, the point probes' search)
 //   gather maps    per CSR entry the list of (local entry, cell) contributions -> deterministic assembly, no atomics
 #pragma once
 #include <hip/hip_runtime.h>
@@ -376,6 +377,14 @@ struct nsx_handle {
   nsx::DevBuf<double> diag_fold;      // the levels of their fold
   nsx::DevBuf<double> diag_max;       // [2 * world] the ranks' maxima on their way through the SUM collective
   bool diag_valid = false;            // diag_planes holds the values of a finished call on the current mesh
+  // ---- point probes (nsx_probe.hip)
+  nsx::DevBuf<double> cell_x0;        // SoA [dim][n_cells]: vertex 0 of every cell, beside geo (x = X0 + J lambda)
+  int probe_n = 0;                    // probes of the current set (0: none); the set outlives a new layout / rank table, not a new mesh
+  nsx::DevBuf<int32_t> probe_cell;    // [probe_n] the cell this handle evaluates the probe in (caller's cell order), -1: in no cell / another rank's
+  nsx::DevBuf<double> probe_lambda;   // SoA [dim+1][probe_n] barycentric coordinates in that cell, stored by nsx_set_probes
+  nsx::DevBuf<double> probe_out;      // SoA [dim + 1 + dim^2][probe_n] values of the last nsx_eval_probes
+  std::vector<int32_t> probe_cells_h, probe_owner_h;  // what nsx_get_probe_cells hands out
+  std::vector<double> probe_lambda_h;                 // [probe_n][dim+1]
   // ---- profiling
   bool prof_on = false;
   std::map<std::string, nsx::ProfEntry> prof;
@@ -432,6 +441,10 @@ void run_dirichlet(nsx_handle *h, int n, const int32_t *dofs, const double *vals
 
 // flow diagnostics (nsx_diag.hip)
 void diag_mesh_setup(nsx_handle *h);  // with every mesh set-up: which cells this handle counts
+
+// point probes (nsx_probe.hip)
+void probe_mesh_setup(nsx_handle *h, const double *cell_coords);  // with every mesh set-up: vertex 0 of every cell
+void probe_clear(nsx_handle *h);                                  // a new mesh drops the probe set
 
 // sparse (nsx_sparse.hip)
 bool blocked_usable(const nsx_handle *h);                                                   // F->vmult goes through the LDS-staged SpMV

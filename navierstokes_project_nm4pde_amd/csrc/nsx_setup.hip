@@ -801,6 +801,7 @@ void setup_mesh(nsx_handle *h, int n_cells, int n_cells1, const double *cell_coo
       geo[(size_t)(dim * dim) * n_cells + c] = std::fabs(det);
     }
     h->geo.upload(geo, h->stream);
+    probe_mesh_setup(h, cell_coords);
   }
   // gather maps (cell order ascending inside every list -> same summation order as the reference's cell loop)
   build_gather(h, h->gA.host, n_cells, np2, c2, np2, c2, 1, false, h->gmA);
@@ -971,6 +972,7 @@ int nsx_set_mesh(nsx_handle *h, int n_cells, int dpc, const int32_t *cell_dofs, 
   h->cell_n2_in = h->cell_n2_h;
   h->cell_n1_in = h->cell_n1_h;
   h->cell_coords_in.assign(cell_coords, cell_coords + (size_t)n_cells * nv * dim);
+  probe_clear(h);
   h->n_cells1 = n_cells;
   h->haloU.send_idx_in.clear();
   h->haloP.send_idx_in.clear();
@@ -1044,6 +1046,7 @@ int nsx_set_mesh_distributed(nsx_handle *h, int n_cells, int n_cells1, int dpc, 
   h->cell_n2_in = h->cell_n2_h;
   h->cell_n1_in = h->cell_n1_h;
   h->cell_coords_in.assign(cell_coords, cell_coords + (size_t)n_cells * nv * dim);
+  probe_clear(h);
   h->n_cells1 = n_cells1;
   default_ranks(h);
   install_mesh(h);

@@ -113,6 +113,10 @@ public:
     ck(nsx_set_mesh(h, nsxh_mesh_n_cells(mesh), nsxh_dofs_per_cell(dofs), nsxh_cell_dofs(dofs), nsxh_cell_coords(dofs), n_u, n_p));
     if (n_ranks > 1) ck(nsx_set_ranks(h, nsxh_n_subdomains(dofs), nsxh_owned_u_ptr(dofs), nsxh_owned_p_ptr(dofs)));
     setup_force_faces();
+    if (probes_csv) {  // opt-in (NSX_PROBES=1): the two pressure points of compute_pressure_difference, located once
+      const double pts3[6] = {0.45, 0.2, 0.205, 0.55, 0.2, 0.205}, pts2[4] = {0.15, 0.2, 0.25, 0.2};
+      ck(nsx_set_probes(h, 2, dim == 3 ? pts3 : pts2, -1.0));
+    }
   }
 
   void solve() {  // NavierStokes3D.cpp:687-741
@@ -132,6 +136,7 @@ public:
       solve_time_step();
       current_time = time;
       if (diagnostics_csv) write_diagnostics(time_step, time);
+      if (probes_csv) write_pressure_difference(time_step, time);
       // NavierStokes3D.cpp:725-726, as written: an EXACT floating-point comparison of the accumulated time with T - deltat (true or false
       // by the rounding of the additions; the reference's own run decides it the same way, so the mirror does not "repair" it)
       if (dim == 3 && time == T - deltat) compute_pressure_difference();
@@ -285,6 +290,18 @@ protected:
     if (numeric) throw std::runtime_error(std::string("nsx: ") + nsx_last_error(h));
   }
 
+  // opt-in series (NSX_PROBES=1): p(A), p(E) and p(A) - p(E) of every time step in pressure_difference_{2D,3D}.csv, evaluated on the device
+  // (nsx_eval_probes); compute_pressure_difference itself stays on the front-end path
+  void write_pressure_difference(const unsigned int time_step, const double time) const {
+    double p[2] = {0.0, 0.0};
+    ck(nsx_eval_probes(h, nullptr, p, nullptr, nullptr));
+    char row[256];
+    snprintf(row, sizeof(row), "%u,%.17g,%.17g,%.17g,%.17g\n", time_step, time, p[0], p[1], p[0] - p[1]);
+    std::ofstream file(dim == 3 ? "pressure_difference_3D.csv" : "pressure_difference_2D.csv", std::ios::app);
+    if (!file.is_open()) throw std::runtime_error("cannot write the pressure difference file");
+    file << row;
+  }
+
   void setup_force_faces() {  // faces with boundary id 3 and the face-quadrature tables (FEFaceValues of compute_forces)
     static const int TETF[4][3] = {{0, 1, 2}, {1, 0, 3}, {0, 2, 3}, {2, 1, 3}};
     static const int TRIF[3][2] = {{0, 1}, {1, 2}, {2, 0}};
@@ -335,6 +352,7 @@ protected:
   int n_u = 0, n_p = 0;
   double current_time = 0.0;
   const bool diagnostics_csv = std::getenv("NSX_DIAGNOSTICS") && std::string(std::getenv("NSX_DIAGNOSTICS")) == "1";
+  const bool probes_csv = std::getenv("NSX_PROBES") && std::string(std::getenv("NSX_PROBES")) == "1";
 };
 
 }  // namespace nsx

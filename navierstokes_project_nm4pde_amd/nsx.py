@@ -26,6 +26,7 @@ API = [
     "nsx_comm_init", "nsx_comm_init_callbacks", "nsx_comm_counters", "nsx_set_mesh_distributed", "nsx_set_force_faces", "nsx_compute_forces",
     "nsx_set_internal_layout", "nsx_layout_info", "nsx_layout_get", "nsx_gram_schmidt_cycle", "nsx_set_inner_precision",
     "nsx_gram_schmidt_sweeps", "nsx_compute_diagnostics", "nsx_get_cell_diagnostic", "nsx_schur_cg",
+    "nsx_set_probes", "nsx_get_probe_cells", "nsx_eval_probes",
 ]
 # declared in include/nsx.h as well, but with a capital letter in its name, which the header scan of tests/test_abi.py (lower case only)
 # does not see: kept beside the list that scan is compared with; build() checks both
@@ -121,6 +122,9 @@ def lib():
     L.nsx_compute_forces.argtypes = [vp, _f64p, _f64p]
     L.nsx_compute_diagnostics.argtypes = [vp, C.POINTER(FlowDiag)]
     L.nsx_get_cell_diagnostic.argtypes = [vp, C.c_int, _f64p]
+    L.nsx_set_probes.argtypes = [vp, C.c_int, _f64p, C.c_double]
+    L.nsx_get_probe_cells.argtypes = [vp, _i32p, _i32p, _f64p]
+    L.nsx_eval_probes.argtypes = [vp, _f64p, _f64p, _f64p, _i32p]
     L.nsx_set_inner_precision.argtypes = [vp, C.c_int]
     L.nsx_inner_F_vmult.argtypes = [vp, _f64p, _f64p]
     L.nsx_schur_cg.argtypes = [vp, C.c_double, C.c_int, _f64p, _f64p, C.POINTER(C.c_int), _f64p, C.POINTER(C.c_int)]
@@ -483,6 +487,36 @@ class Nsx:
         v = np.empty(n)
         self._ck(self.L.nsx_get_cell_diagnostic(self._h, int(which), _d(v)))
         return v
+
+    # -- point probes --------------------------------------------------------------------------
+    def set_probes(self, points, tol=-1.0):
+        """nsx_set_probes: locate points [n][dim] once and keep them as the handle's probe set (an empty list clears it); returns the
+        located `cells` (position in the cell list handed to the handle, -1: in no cell, or another rank evaluates the probe).  In a
+        multi-process run every rank passes the same points, unchanged."""
+        pts = _cd(points).reshape(-1, self.dim)
+        self._ck(self.L.nsx_set_probes(self._h, len(pts), _d(pts), float(tol)))
+        self._n_probes = len(pts)               # a refused call leaves the earlier set (and its size) in place
+        return self.probe_cells()[0] if len(pts) else np.empty(0, np.int32)
+
+    def probe_cells(self):
+        """(cells [n], owners [n], lambda [n][dim+1]) of the probe set (nsx_get_probe_cells)"""
+        n = getattr(self, "_n_probes", 0)
+        cells, owners, lam = np.empty(n, np.int32), np.empty(n, np.int32), np.empty((n, self.dim + 1))
+        self._ck(self.L.nsx_get_probe_cells(self._h, _i(cells), _i(owners), _d(lam)))
+        return cells, owners, lam
+
+    def eval_probes(self, gradient=False):
+        """nsx_eval_probes on the ghosted solution: {"velocity" [n][dim], "pressure" [n], "found" [n] (bool)} and, when asked,
+        "gradient" [n][dim][dim] (d_j u_i)"""
+        n = getattr(self, "_n_probes", 0)
+        out = {"velocity": np.empty((n, self.dim)), "pressure": np.empty(n)}
+        found = np.empty(n, np.int32)
+        grad = np.empty((n, self.dim, self.dim)) if gradient else None
+        self._ck(self.L.nsx_eval_probes(self._h, _d(out["velocity"]), _d(out["pressure"]), _d(grad) if gradient else None, _i(found)))
+        out["found"] = found.astype(bool)
+        if gradient:
+            out["gradient"] = grad
+        return out
 
     # -- export --------------------------------------------------------------------------------
     def export_block(self, which, block, graph=None):
