@@ -340,6 +340,31 @@ int nsx_persistent_state(nsx_handle *h, int state[4]);
  * [30..31] reserved (0). */
 int nsx_path_info(nsx_handle *h, int info[32]);
 
+/* Which kernels the block-Jacobi ILU(0) of F (which = 0) or of the Schur matrix (which = 1) ran -- a test hook:
+ * info[0] the factorisation kernel of the last nsx_prec_initialize / solve (NSX_ILU_FACTOR_*: one launch per level, the block staged
+ * in LDS, a dense row per wave, the general one; 0: none yet), [1] the kernel that built the explicit block inverses (NSX_ILU_INVERT_*),
+ * [2] the kernel of the LAST triangular solve on that schedule (NSX_ILU_SOLVE_*: one launch per level, the dense inverses, the
+ * lane-owner stream, a workgroup per block with its part of x in LDS / in global memory; 0: none since the schedule was built),
+ * [3] entries per lane and tick of the stream (NSX_ILU_EPT; 0: no stream), [4] slabs per register set of that solve (NSX_PF: 4 / 8; 0: not
+ * the stream), [5] its interleaved right-hand sides, [6] 1 = it read the float stream, [7] waves of the stream, [8] blocks,
+ * [9] rows of the largest block, [10] in-block entries of the largest block, [11] rows of the largest wave, [12] 1 = the schedule is
+ * levelled, [13] 1 = it has a usable lane-owner stream, [14] 1 = it has explicit inverses, [15] bytes of dynamic LDS the factorisation
+ * asked for (the LDS-staged kernel; else 0).
+ * The solves inside a fused sweep launch (k_ilu_mgs) are not recorded. */
+#define NSX_ILU_FACTOR_LEVEL 1
+#define NSX_ILU_FACTOR_LDS 2
+#define NSX_ILU_FACTOR_DENSE_ROW 3
+#define NSX_ILU_FACTOR_GENERAL 4
+#define NSX_ILU_INVERT_NONE 0
+#define NSX_ILU_INVERT_LDS 1
+#define NSX_ILU_INVERT_GLOBAL 2
+#define NSX_ILU_SOLVE_LEVELLED 1
+#define NSX_ILU_SOLVE_DENSE 2
+#define NSX_ILU_SOLVE_LANES 3
+#define NSX_ILU_SOLVE_BLOCK_LDS 4
+#define NSX_ILU_SOLVE_BLOCK_GLOBAL 5
+int nsx_ilu_path_info(nsx_handle *h, int which, int info[16]);
+
 /* SolverGMRES' orthogonalisation (deal.II's modified Gram-Schmidt add_and_dot chain inside every solver.solve of the path: reference
  * NavierStokes3D.cpp:574, Preconditioners.hpp:173,273,288,382,405) on the caller's vectors, through the very sweep kernel the solvers
  * use: vectors[m][n] (row k = vector k) -- vector 0 is normalised, vector k is orthogonalised against vectors 0..k-1 and normalised,

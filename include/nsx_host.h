@@ -179,6 +179,11 @@ int nsxh_pressure_difference(const nsxh_dofs *, const double *solution, const do
  * 0; -3 when a wave's rows do not fit 16-bit LDS addresses; -1 on bad input. */
 int nsxh_ilu_stream_stats(int n_rows, const int32_t *rowptr, const int32_t *colind, int n_blocks, const int32_t *block_ptr,
                           int blocks_per_wave, int ncomp, int gap, int entries_per_tick, int64_t out[6]);
+/* The same stream's sweep lengths: fwd[w] / bwd[w] = slabs of the forward / backward sweep of wave w (multiples of 4, 0 for a wave
+ * without in-block off-diagonal entries), n_waves entries each as nsxh_ilu_stream_stats reports them -- which exit of the kernel's
+ * sweep loop a wave takes follows from its count modulo 16.  Same return codes. */
+int nsxh_ilu_stream_slabs(int n_rows, const int32_t *rowptr, const int32_t *colind, int n_blocks, const int32_t *block_ptr,
+                          int blocks_per_wave, int ncomp, int gap, int entries_per_tick, int n_waves, int32_t *fwd, int32_t *bwd);
 /* Replay the stream on the host tick by tick exactly as the kernel consumes it (the LDS reads of a tick before the writes of the
  * tick in front of it): x = U^-1 D^-1 L^-1 b per block for factors `lu` in Ifpack's storage on the graph. */
 int nsxh_ilu_stream_apply(int n_rows, const int32_t *rowptr, const int32_t *colind, int n_blocks, const int32_t *block_ptr,

@@ -468,3 +468,29 @@ extern "C" int nsx_path_info(nsx_handle *h, int info[32]) {
   }
   return NSX_OK;
 }
+
+// Which ILU(0) kernels ran on the schedule of F (0) / of the Schur matrix (1): see include/nsx.h
+extern "C" int nsx_ilu_path_info(nsx_handle *h, int which, int info[16]) {
+  if (!h || !info || which < 0 || which > 1) return NSX_ERR_ARG;
+  for (int k = 0; k < 16; ++k) info[k] = 0;
+  if (!h->have_mesh) return NSX_OK;
+  const nsx::IluSchedule &s = which == 0 ? h->schedF : h->schedS;
+  const bool stream = s.stream_ncomp > 0 && !s.levelled;
+  info[0] = s.path.factor;
+  info[1] = s.path.invert;
+  info[2] = s.path.solve;
+  info[3] = stream ? s.stream_epl : 0;
+  info[4] = s.path.solve_pf;
+  info[5] = s.path.solve_ncomp;
+  info[6] = s.path.solve_f32;
+  info[7] = stream ? s.n_waves : 0;
+  info[8] = s.n_blocks;
+  info[9] = s.max_rows;
+  info[10] = s.max_block_nnz;
+  info[11] = stream ? s.max_wave_rows : 0;
+  info[12] = s.levelled ? 1 : 0;
+  info[13] = s.packed_ok ? 1 : 0;
+  info[14] = s.dense ? 1 : 0;
+  info[15] = s.path.factor_lds_bytes;
+  return NSX_OK;
+}

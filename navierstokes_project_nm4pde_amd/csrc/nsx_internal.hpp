@@ -154,6 +154,13 @@ struct IluSchedule {
   std::vector<int32_t> gl_f_ptr_h, gl_b_ptr_h;  // [levels+1] offsets into gl_f_rows / gl_b_rows
   DevBuf<int32_t> gl_f_rows, gl_b_rows, in_lo, in_hi;
   DevBuf<int32_t> gl_f_rec, gl_b_rec;  // [4 * rows] per row in level order: row, first entry, end of entries, diagonal (k_ilu_solve_level)
+  // ---- which kernels the last factorisation / the last solve on this schedule launched (nsx_ilu_path_info; include/nsx.h has the
+  //      codes).  Written by ilu_factor / ilu_solve, cleared when the schedule is rebuilt.
+  struct Path {
+    int factor = 0, invert = 0, factor_lds_bytes = 0;
+    int solve = 0, solve_pf = 0, solve_ncomp = 0, solve_f32 = 0;
+  };
+  mutable Path path;
 };
 
 // The ONE test for "this schedule's triangular solves with ncomp right-hand sides run the lane-owner stream": the solve reads the stream

@@ -72,6 +72,7 @@ void setup_ilu_schedule(nsx_handle *h, const Csr &g, const std::vector<int32_t> 
   s.n_blocks = nb;
   s.block_ptr_h = bptr;
   s.max_rows = 0;
+  s.path = IluSchedule::Path();
   std::vector<int32_t> lev(g.n_rows, 0);
   std::vector<int32_t> f_ptr{0}, f_rows, b_ptr{0}, b_rows, off_f(nb + 1, 0), off_b(nb + 1, 0);
   f_rows.reserve(g.n_rows);

@@ -1240,9 +1240,11 @@ void ilu_factor(nsx_handle *h, const DevCsr &g, IluSchedule &s, const double *va
   s.stream_f32 = pk32 != nullptr;
   {
     LaunchScope ls(h, name, 20.0 * g.nnz() + 12.0 * g.n_rows());
-    static const bool small_ok = !(getenv("NSX_ILU_SMALL") && atoi(getenv("NSX_ILU_SMALL")) == 0);
+    const bool small_ok = !(getenv("NSX_ILU_SMALL") && atoi(getenv("NSX_ILU_SMALL")) == 0);  // read per call, like its neighbours
     const bool lds_ok = !(getenv("NSX_ILU_FACTOR_LDS") && atoi(getenv("NSX_ILU_FACTOR_LDS")) == 0);  // read per call: the tests switch it
+    s.path.factor_lds_bytes = 0;
     if (s.levelled) {
+      s.path.factor = NSX_ILU_FACTOR_LEVEL;
       for (size_t l = 0; l + 1 < s.gl_f_ptr_h.size(); ++l) {
         const int n = s.gl_f_ptr_h[l + 1] - s.gl_f_ptr_h[l];
         if (n > 0)
@@ -1252,6 +1254,8 @@ void ilu_factor(nsx_handle *h, const DevCsr &g, IluSchedule &s, const double *va
     } else if (lds_ok && s.max_rows <= 4096 && s.max_block_nnz < 65535 && ilu_factor_lds_bytes(s.max_rows, s.max_block_nnz) <= 80 * 1024) {
       // the whole block in LDS: at most 80 KB, so that at least two workgroups share a CU
       const size_t lds = ilu_factor_lds_bytes(s.max_rows, s.max_block_nnz);
+      s.path.factor = NSX_ILU_FACTOR_LDS;
+      s.path.factor_lds_bytes = (int)lds;
       static std::atomic<size_t> lds_allowed{64 * 1024};  // per process: the attribute belongs to the function, not to a handle
       if (lds > lds_allowed.load()) {
         HIP_CHECK(hipFuncSetAttribute((const void *)k_ilu_factor_lds, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
@@ -1260,15 +1264,19 @@ void ilu_factor(nsx_handle *h, const DevCsr &g, IluSchedule &s, const double *va
       hipLaunchKernelGGL(k_ilu_factor_lds, dim3(s.n_blocks), dim3(ILU_WAVES * 64), lds, h->stream, s.fac_order.p, s.block_ptr.p, s.blk_lvl_off.p, s.fwd_lvl_ptr.p,
                          s.fwd_rows.p, g.rowptr.p, g.colind.p, g.diag.p, s.in_lo.p, s.in_cptr.p, s.in_cpos.p, vals, lu,
                          s.packed_ok ? s.pk_slot_of.p : nullptr, s.pk_val.p, s.pk_dinv.p, err, s.pk_dinv_slot.p, s.max_rows, (int)s.max_block_nnz, pk32);
-    } else if (small_ok && s.max_rows <= ILU_DENSE_ROWS)
+    } else if (small_ok && s.max_rows <= ILU_DENSE_ROWS) {
+      s.path.factor = NSX_ILU_FACTOR_DENSE_ROW;
       hipLaunchKernelGGL(k_ilu_factor_small, dim3(s.n_blocks), dim3(ILU_WAVES * 64), 0, h->stream, s.block_ptr.p, s.blk_lvl_off.p,
                          s.fwd_lvl_ptr.p, s.fwd_rows.p, g.rowptr.p, g.colind.p, g.diag.p, vals, lu, s.packed_ok ? s.pk_slot_of.p : nullptr,
                          s.pk_val.p, s.pk_dinv.p, err, s.pk_dinv_slot.p, pk32);
-    else
+    } else {
+      s.path.factor = NSX_ILU_FACTOR_GENERAL;
       hipLaunchKernelGGL(k_ilu_factor, dim3(s.n_blocks), dim3(ILU_WAVES * 64), 0, h->stream, s.block_ptr.p, s.blk_lvl_off.p, s.fwd_lvl_ptr.p,
                          s.fwd_rows.p, g.rowptr.p, g.colind.p, g.diag.p, vals, lu, s.packed_ok ? s.pk_slot_of.p : nullptr, s.pk_val.p,
                          s.pk_dinv.p, err, s.pk_dinv_slot.p, pk32);
+    }
   }
+  s.path.invert = NSX_ILU_INVERT_NONE;
   if (s.dense) {
     LaunchScope ls(h, "ilu_invert", 8.0 * (double)s.dn_entries + 12.0 * g.nnz());
     // blocks of up to 112 rows (98 KB of LDS: one workgroup per CU and half) keep the n x n matrix in LDS while it is built
@@ -1280,8 +1288,10 @@ void ilu_factor(nsx_handle *h, const DevCsr &g, IluSchedule &s, const double *va
         HIP_CHECK(hipFuncSetAttribute((const void *)k_ilu_invert_lds, hipFuncAttributeMaxDynamicSharedMemorySize, 112 * 112 * (int)sizeof(double)));
         attr_set = true;
       }
+      s.path.invert = NSX_ILU_INVERT_LDS;
       hipLaunchKernelGGL(k_ilu_invert_lds, dim3(s.n_blocks), dim3(128), shm, h->stream, s.block_ptr.p, s.dn_off.p, g.rowptr.p, g.colind.p, g.diag.p, lu, s.dn_P.p);
     } else {
+      s.path.invert = NSX_ILU_INVERT_GLOBAL;
       hipLaunchKernelGGL(k_ilu_invert, dim3(s.n_blocks), dim3(256), 0, h->stream, s.block_ptr.p, s.dn_off.p, g.rowptr.p, g.colind.p, g.diag.p, lu,
                          s.dn_P.p);
     }
@@ -1517,7 +1527,8 @@ __global__ __launch_bounds__(64) void k_ilu_solve_lanes_f32(const int32_t *__res
 template <int NCOMP>
 static void launch_lanes(nsx_handle *h, const IluSchedule &s, const double *b, double *x, double *dot_partial, bool f32) {
   const size_t shm = (size_t)(s.max_wave_rows + 64) * NCOMP * sizeof(double);
-  static const int pf = getenv("NSX_PF") ? atoi(getenv("NSX_PF")) : 8;
+  const int pf = getenv("NSX_PF") && atoi(getenv("NSX_PF")) == 4 ? 4 : 8;  // read per launch, like NSX_ILU_LDS_GUARD_TEST below (nsx_mgs.hip does the same)
+  s.path.solve_pf = pf;
   int *err = (int *)(h->pub_dev + N_SLOTS + 3);  // the mapped word ilu_check() reads
   const int force_guard = getenv("NSX_ILU_LDS_GUARD_TEST") ? atoi(getenv("NSX_ILU_LDS_GUARD_TEST")) : 0;  // fault injection (tests), read per launch
 #define NSX_GO(E_, PF_)                                                                                                                        \
@@ -1548,6 +1559,7 @@ static void launch_ilu_solve(nsx_handle *h, const DevCsr &g, const IluSchedule &
   constexpr int LW = 8;
 #define NSX_ILU_ARGS s.block_ptr.p, s.blk_lvl_off.p, s.fwd_lvl_ptr.p, s.fwd_rows.p, s.blk_lvl_off_b.p, s.bwd_lvl_ptr.p, s.bwd_rows.p, \
                      g.rowptr.p, g.colind.p, g.diag.p, lu, b, x
+  s.path.solve = shm <= 64 * 1024 ? NSX_ILU_SOLVE_BLOCK_LDS : NSX_ILU_SOLVE_BLOCK_GLOBAL;
   if (shm <= 64 * 1024)
     hipLaunchKernelGGL((k_ilu_solve<NCOMP, LW, true>), dim3(s.n_blocks), dim3(256), shm, h->stream, NSX_ILU_ARGS);
   else
@@ -1560,7 +1572,10 @@ static void launch_ilu_solve(nsx_handle *h, const DevCsr &g, const IluSchedule &
 bool ilu_solve(nsx_handle *h, const DevCsr &g, const IluSchedule &s, const double *lu, const double *b, double *x, int ncomp,
                const char *name, int dot_slot, bool f32, int *used_f32) {
   if (used_f32) *used_f32 = 0;
+  s.path.solve_ncomp = ncomp;
+  s.path.solve_pf = s.path.solve_f32 = 0;
   if (s.levelled) {
+    s.path.solve = NSX_ILU_SOLVE_LEVELLED;
     LaunchScope ls(h, name, 12.0 * (double)s.in_block_nnz + (double)g.n_rows() * (4 + 16.0 * ncomp));
     if (ncomp == 1) ilu_solve_levelled<1>(h, g, s, lu, b, x);
     else if (ncomp == 2) ilu_solve_levelled<2>(h, g, s, lu, b, x);
@@ -1570,6 +1585,7 @@ bool ilu_solve(nsx_handle *h, const DevCsr &g, const IluSchedule &s, const doubl
   const bool packed = ilu_lanes_stream(s, ncomp);  // (the schedule already checked that a wave's rows fit 64 KiB of LDS)
   if (s.dense && ncomp == 1 && (size_t)s.max_rows * sizeof(double) <= 48 * 1024) {
     LaunchScope ls(h, name, 8.0 * (double)s.dn_entries + 16.0 * g.n_rows());
+    s.path.solve = NSX_ILU_SOLVE_DENSE;
     const bool with_dot = dot_slot >= 0 && !h->comm && s.n_blocks >= 2 && s.n_blocks <= 512;  // a communicator needs equal counts on all ranks
     hipLaunchKernelGGL(k_ilu_apply_dense, dim3(s.n_blocks), dim3(DENSE_THREADS), (size_t)s.max_rows * sizeof(double), h->stream, s.block_ptr.p, s.dn_off.p,
                        s.dn_P.p, b, x, with_dot ? red_out(h, dot_slot, s.n_blocks) : nullptr);
@@ -1585,6 +1601,8 @@ bool ilu_solve(nsx_handle *h, const DevCsr &g, const IluSchedule &s, const doubl
   LaunchScope ls(h, name, 12.0 * (double)s.in_block_nnz - (lanes32 ? 4.0 * (double)(s.in_block_nnz - g.n_rows()) : 0.0) + (double)g.n_rows() * (4 + 16.0 * ncomp));
   if (packed) {
     if (used_f32) *used_f32 = lanes32 ? 1 : 0;
+    s.path.solve = NSX_ILU_SOLVE_LANES;
+    s.path.solve_f32 = lanes32 ? 1 : 0;
     const bool with_dot = dot_slot >= 0 && !h->comm && s.n_waves >= 2 && s.n_waves <= 512;  // one partial sum per wave
     double *dp = with_dot ? red_out(h, dot_slot, s.n_waves) : nullptr;
     if (ncomp == 1) launch_lanes<1>(h, s, b, x, dp, lanes32);

@@ -72,6 +72,7 @@ def _lib():
         "nsxh_tables_N1": (_f64p, [vp]),
         "nsxh_tables_dN1": (_f64p, [vp]),
         "nsxh_ilu_stream_stats": (C.c_int, [C.c_int, _i32p, _i32p, C.c_int, _i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
+        "nsxh_ilu_stream_slabs": (C.c_int, [C.c_int, _i32p, _i32p, C.c_int, _i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, _i32p]),
         "nsxh_ilu_stream_apply": (C.c_int, [C.c_int, _i32p, _i32p, C.c_int, _i32p, C.c_int, C.c_int, C.c_int, C.c_int, _f64p, _f64p, _f64p]),
         "nsxh_ilu_stream_apply_f32": (C.c_int, [C.c_int, _i32p, _i32p, C.c_int, _i32p, C.c_int, C.c_int, C.c_int, C.c_int, _f64p, _f64p, _f64p]),
         "nsxh_internal_layout": (C.c_int, [C.c_int, C.c_int, C.c_int, _i32p, _f64p, C.c_int, C.c_int, C.c_int, _i32p, _i32p, C.c_int, C.c_int, C.c_int,
@@ -298,6 +299,14 @@ def ilu_stream_stats(rowptr, colind, block_ptr, blocks_per_wave=8, ncomp=3, gap=
     d = dict(zip(keys, (int(v) for v in out)))
     d["fill"] = d["used_slots"] / max(1, 64 * d["slabs"] * int(entries_per_tick))
     d["stream_bytes"] = d["slabs"] * 64 * (8 * int(entries_per_tick) + 4 * ((int(entries_per_tick) + 2) // 2))
+    # slabs of every wave's forward / backward sweep (nsxh_ilu_stream_slabs): the sweep loop's exit follows from the count modulo 16
+    fwd, bwd = np.zeros(d["waves"], dtype=np.int32), np.zeros(d["waves"], dtype=np.int32)
+    rc = _lib().nsxh_ilu_stream_slabs(len(rp) - 1, rp.ctypes.data_as(_i32p), ci.ctypes.data_as(_i32p), len(bp) - 1, bp.ctypes.data_as(_i32p),
+                                      int(blocks_per_wave), int(ncomp), int(gap), int(entries_per_tick), d["waves"],
+                                      fwd.ctypes.data_as(_i32p), bwd.ctypes.data_as(_i32p))
+    if rc:
+        raise ValueError("nsxh_ilu_stream_slabs failed (%d)" % rc)
+    d["fwd_slabs"], d["bwd_slabs"] = fwd.tolist(), bwd.tolist()
     return d
 
 

@@ -1359,6 +1359,23 @@ extern "C" int nsxh_ilu_stream_stats(int n_rows, const int32_t *rowptr, const in
   }
 }
 
+extern "C" int nsxh_ilu_stream_slabs(int n_rows, const int32_t *rowptr, const int32_t *colind, int n_blocks, const int32_t *block_ptr,
+                                     int blocks_per_wave, int ncomp, int gap, int entries_per_tick, int n_waves, int32_t *fwd, int32_t *bwd) {
+  if (!rowptr || !colind || !block_ptr || !fwd || !bwd || n_rows < 0 || n_blocks < 1 || ncomp < 1 || gap < 1 || entries_per_tick < 1 || entries_per_tick > 4) return -1;
+  try {
+    nsx::IluStream s;
+    nsx::build_ilu_stream(csr_of(n_rows, rowptr, colind), std::vector<int32_t>(block_ptr, block_ptr + n_blocks + 1), blocks_per_wave, ncomp, gap, s, entries_per_tick);
+    if (n_waves != s.n_waves || (int)s.slab_ptr.size() != 2 * s.n_waves + 1) return -1;
+    for (int w = 0; w < s.n_waves; ++w) {
+      fwd[w] = s.slab_ptr[2 * w + 1] - s.slab_ptr[2 * w];
+      bwd[w] = s.slab_ptr[2 * w + 2] - s.slab_ptr[2 * w + 1];
+    }
+    return s.ok ? 0 : -3;
+  } catch (const std::exception &) {
+    return -1;
+  }
+}
+
 extern "C" int nsxh_ilu_stream_apply(int n_rows, const int32_t *rowptr, const int32_t *colind, int n_blocks, const int32_t *block_ptr,
                                      int blocks_per_wave, int ncomp, int gap, int entries_per_tick, const double *lu, const double *b, double *x) {
   if (!rowptr || !colind || !block_ptr || !lu || !b || !x || ncomp < 1 || gap < 1 || entries_per_tick < 1 || entries_per_tick > 4) return -1;

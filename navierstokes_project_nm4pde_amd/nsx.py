@@ -22,7 +22,7 @@ API = [
     "nsx_set_rhs", "nsx_assemble", "nsx_assemble_time_step", "nsx_add_rhs", "nsx_apply_boundary_values",
     "nsx_solve_time_step", "nsx_prec_initialize", "nsx_prec_vmult", "nsx_system_vmult", "nsx_ilu_apply",
     "nsx_export_block", "nsx_schur_nnz", "nsx_schur_get", "nsx_scalar_graph_nnz", "nsx_scalar_graph", "nsx_ilu_get",
-    "nsx_profile_enable", "nsx_profile_reset", "nsx_profile_count", "nsx_profile_get", "nsx_persistent_state", "nsx_path_info", "nsx_comm_self_halo_test", "nsx_comm_unique_id",
+    "nsx_profile_enable", "nsx_profile_reset", "nsx_profile_count", "nsx_profile_get", "nsx_persistent_state", "nsx_path_info", "nsx_ilu_path_info", "nsx_comm_self_halo_test", "nsx_comm_unique_id",
     "nsx_comm_init", "nsx_comm_init_callbacks", "nsx_comm_counters", "nsx_set_mesh_distributed", "nsx_set_force_faces", "nsx_compute_forces",
     "nsx_set_internal_layout", "nsx_layout_info", "nsx_layout_get", "nsx_gram_schmidt_cycle", "nsx_set_inner_precision",
     "nsx_gram_schmidt_sweeps", "nsx_compute_diagnostics", "nsx_get_cell_diagnostic", "nsx_schur_cg",
@@ -112,6 +112,7 @@ def lib():
     L.nsx_profile_count.argtypes = [vp]
     L.nsx_profile_get.argtypes = [vp, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), _f64p, _f64p]
     L.nsx_persistent_state.argtypes = [vp, C.POINTER(C.c_int)]
+    L.nsx_ilu_path_info.argtypes = [vp, C.c_int, C.POINTER(C.c_int)]
     L.nsx_comm_unique_id.argtypes = [C.POINTER(C.c_uint8)]
     L.nsx_comm_init.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_uint8)]
     L.nsx_comm_init_callbacks.argtypes = [vp, C.c_int, C.c_int, ALLREDUCE_FN, EXCHANGE_FN, C.c_void_p]
@@ -249,6 +250,22 @@ class Nsx:
         v = (C.c_int * 32)()
         self._ck(self.L.nsx_path_info(self._h, v))
         return {k: int(v[i]) for i, k in enumerate(self.PATH_KEYS)}
+
+    ILU_PATH_KEYS = ("factor", "invert", "solve", "entries_per_tick", "slabs_per_set", "ncomp", "float_stream", "waves", "blocks", "max_block_rows",
+                     "max_block_nnz", "max_wave_rows", "levelled", "lane_stream", "dense_inverses", "factor_lds_bytes")
+    ILU_FACTOR = {0: None, 1: "level", 2: "lds", 3: "dense_row", 4: "general"}
+    ILU_INVERT = {0: None, 1: "lds", 2: "global"}
+    ILU_SOLVE = {0: None, 1: "levelled", 2: "dense", 3: "lanes", 4: "block_lds", 5: "block_global"}
+
+    def ilu_path_info(self, which):
+        """dict: the kernels the ILU(0) of F (which = 0) / of the Schur matrix (1) ran (nsx_ilu_path_info): the factorisation and
+        inversion kernels of the last initialisation and the kernel of the last triangular solve by name, the stream's parameters and
+        the schedule's sizes"""
+        v = (C.c_int * 16)()
+        self._ck(self.L.nsx_ilu_path_info(self._h, int(which), v))
+        d = {k: int(v[i]) for i, k in enumerate(self.ILU_PATH_KEYS)}
+        d["factor"], d["invert"], d["solve"] = self.ILU_FACTOR[d["factor"]], self.ILU_INVERT[d["invert"]], self.ILU_SOLVE[d["solve"]]
+        return d
 
     def comm_counters(self):
         """(all-reduces, ghost exchanges) issued since the communicator was set"""
