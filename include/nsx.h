@@ -305,6 +305,54 @@ int nsx_get_probe_cells(nsx_handle *h, int32_t *cells, int32_t *owners, double *
  * computed without the call, and two calls give bitwise equal results. */
 int nsx_eval_probes(nsx_handle *h, double *velocity, double *pressure, double *gradient, int32_t *found);
 
+/* ---- tracer particles ---- */
+/* Massless particles carried by the finite-element velocity u_h: pathlines, streaklines and residence times need the velocity of EVERY time
+ * step, which the output files (one VTU every 20 steps) do not hold.  No counterpart in the reference.  The particles live on the device:
+ * nsx_set_tracers locates the seeds once (the probes' search), nsx_advect_tracers moves them through u_h of the state the handle holds, walking
+ * from cell to cell through a face-neighbour table, and nsx_get_tracers downloads positions, cells, statuses, exit faces and ages.
+ * The tracer set and the probe set are independent of each other.
+ * Containment and ties: as for the point probes -- all dim+1 barycentric coordinates >= -tol, tol < 0: the library's own 1e-12, 0 <= tol < 1
+ * as given; a seed on a face, an edge or a vertex starts in the lowest containing cell of the caller's cell list.  The walk uses the same tol.
+ * Face neighbours: nbr[k][cell] is the cell across the face opposite local vertex k, -1 on the boundary; built from the connectivity as
+ * handed over by the first nsx_set_tracers on a mesh (host/adjacency.hpp: sorted face keys), so the mesh set-up itself costs what it did.
+ * Status: NSX_TRACER_NOT_FOUND the seed is in no cell; the particle never moves (position = seed, cell = -1, exit face = -1, age = 0).
+ *         NSX_TRACER_ACTIVE    moves with every nsx_advect_tracers.
+ *         NSX_TRACER_EXITED    a stage point or the new position of a substep left the mesh through a boundary face; the particle stays at
+ *                              its position from the start of that substep, cells holds the cell of that face and exit_faces the deal.II
+ *                              local number of the face: 3 - k in 3D, (k + 1) % 3 in 2D for the face opposite local vertex k (the
+ *                              face -> vertex tables {0,1,2},{1,0,3},{0,2,3},{2,1,3} and {0,1},{1,2},{2,0}).  Final.
+ *         NSX_TRACER_LOST      a position that is not finite (a state value that is not finite makes the particles that meet it LOST), or
+ *                              more than 1024 cell-to-cell steps for one point; the particle stays at its position and in its cell from the
+ *                              start of that substep, exit face -1.  Final.  The walk is bounded: the call always returns.
+ * Lifetime: the set and its state (positions, ages) survive nsx_set_ranks and nsx_set_internal_layout; a new nsx_set_mesh(_distributed) drops
+ * the set and the neighbour table; n = 0 clears the set.
+ * Errors: NSX_ERR_ARG for a tracer call before the mesh is set, advect / get without a set, n < 0, null points with n > 0, tol >= 1, a seed
+ * coordinate or a dt that is not finite, n_substeps < 1, an unknown scheme or field, and a mesh in which a face belongs to more than two
+ * cells; NSX_ERR_UNSUPPORTED for n > 1048576, for a (dim, n_p2) other than (2, 6) / (3, 10), and for distributed handles with more than one
+ * process (particles that cross rank boundaries are out of scope; a 1-rank communicator works).  No call issues a collective or a ghost
+ * exchange (nsx_comm_counters does not move). */
+enum { NSX_TRACER_EULER = 1, NSX_TRACER_RK2 = 2, NSX_TRACER_RK4 = 4 };   /* scheme: explicit Euler, explicit midpoint, classical RK4 */
+enum { NSX_TRACER_FROZEN = 0, NSX_TRACER_LINEAR = 1 };                   /* field */
+enum { NSX_TRACER_NOT_FOUND = 0, NSX_TRACER_ACTIVE = 1, NSX_TRACER_EXITED = 2, NSX_TRACER_LOST = 3 };
+
+/* Locate n seeds (points[n][dim]) and make them the handle's tracer set, replacing any earlier one; ages start at 0. */
+int nsx_set_tracers(nsx_handle *h, int n, const double *points /*[n][dim]*/, double tol);
+/* Advance every ACTIVE particle by n_substeps steps of size h = dt / n_substeps (dt < 0: backward tracing), all inside one kernel launch.
+ * field NSX_TRACER_FROZEN: the velocity is u_h of the ghosted `solution`; previous_solution is not read.
+ * field NSX_TRACER_LINEAR: the velocity at stage node c (0, 1/2 or 1) of substep s is u_prev(x) + theta (u(x) - u_prev(x)) with
+ *   theta = (s + c) / n_substeps for dt > 0 and theta = 1 - (s + c) / n_substeps for dt < 0, u_prev being u_h of previous_solution: one call
+ *   with dt = the time step spans the step solved last.  previous_solution is zero before the first nsx_solve_time_step.
+ * u_h(x) is evaluated as nsx_eval_probes does (P2 shape functions in barycentric form).  Walk rule, for every stage point and for the new
+ * position: the first stage point starts from the particle's cell, each later point from the cell in which the previous point of that substep
+ * was accepted; with lambda of the point in the current cell, the cell is accepted when every lambda_k >= -tol, otherwise the walk steps to
+ * nbr[k], k the index of the smallest lambda (ties: the lowest k); nbr[k] = -1 ends it (EXITED).  age grows by h per completed substep.
+ * Reads state only: a following solve computes bitwise what it would have computed without the call.  Particles are independent of each
+ * other, so the results are bitwise reproducible and do not depend on the number of particles, nsx_set_ranks or nsx_set_internal_layout. */
+int nsx_advect_tracers(nsx_handle *h, double dt, int n_substeps, int scheme, int field);
+/* positions[n][dim], cells[n] (position in the caller's cell list), status[n] (NSX_TRACER_*), exit_faces[n] (-1 unless EXITED), age[n].
+ * Any pointer may be NULL. */
+int nsx_get_tracers(nsx_handle *h, double *positions /*[n][dim]*/, int32_t *cells, int32_t *status, int32_t *exit_faces, double *age);
+
 /* ---- measurement ---- */
 /* Per-kernel HIP-event timing of the hot path (bench.py roofline): enable, run, then read name/count/total-ms. */
 int nsx_profile_enable(nsx_handle *h, int on);

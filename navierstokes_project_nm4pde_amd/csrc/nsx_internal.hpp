@@ -11,6 +11,7 @@
 //   S-graph        P1 x P1 CSR = structural product B*G: negative_S_tilde and its ILU(0)   (Prec.hpp:144,358)
 //   cell tables    SoA: cell_n2[a][cell], cell_n1[v][cell], geo[k][cell] (J^-1 row-major, then |det J|)
 //                  cell_x0[d][cell] (vertex 0: x = X0 + J lambda, the point probes' search)
+//                  cell_nbr[k][cell] (cell across the face opposite local vertex k, -1: boundary; the tracers' walk, built on demand)
 //   gather maps    per CSR entry the list of (local entry, cell) contributions -> deterministic assembly, no atomics
 #pragma once
 #include <hip/hip_runtime.h>
@@ -392,6 +393,14 @@ struct nsx_handle {
   nsx::DevBuf<double> probe_out;      // SoA [dim + 1 + dim^2][probe_n] values of the last nsx_eval_probes
   std::vector<int32_t> probe_cells_h, probe_owner_h;  // what nsx_get_probe_cells hands out
   std::vector<double> probe_lambda_h;                 // [probe_n][dim+1]
+  // ---- tracer particles (nsx_tracer.hip)
+  nsx::DevBuf<int32_t> cell_nbr;      // SoA [dim+1][n_cells]: cell across the face opposite local vertex k, -1: boundary; built by the first nsx_set_tracers on a mesh
+  bool have_nbr = false;
+  int tracer_n = 0;                   // particles of the current set (0: none); outlives a new layout / rank table, not a new mesh
+  double tracer_tol = 0.0;            // containment tolerance of the set (nsx_set_tracers), used by every walk
+  nsx::DevBuf<double> tracer_x;       // SoA [dim][tracer_n] positions
+  nsx::DevBuf<double> tracer_age;     // [tracer_n]
+  nsx::DevBuf<int32_t> tracer_cell, tracer_status, tracer_face;  // [tracer_n] each
   // ---- profiling
   bool prof_on = false;
   std::map<std::string, nsx::ProfEntry> prof;
@@ -452,6 +461,40 @@ void diag_mesh_setup(nsx_handle *h);  // with every mesh set-up: which cells thi
 // point probes (nsx_probe.hip)
 void probe_mesh_setup(nsx_handle *h, const double *cell_coords);  // with every mesh set-up: vertex 0 of every cell
 void probe_clear(nsx_handle *h);                                  // a new mesh drops the probe set
+// the search of nsx_set_probes on n device points [n][dim]: best [n] (INT32_MAX on entry) -> cells [n] (-1: in no cell), lam SoA [dim+1][n]
+void probe_locate(nsx_handle *h, int n, const double *points, double tol, int32_t *best, int32_t *cells, double *lam);
+constexpr double PROBE_TOL = 1e-12;  // the tolerance of nsxh_pressure_difference
+// lambda[0..DIM] of x in the cell (X0, J^-1): x = X0 + J lambda[1..], lambda[0] = 1 - sum.  A coordinate that is not finite is in no cell.
+template <int DIM>
+__device__ __forceinline__ bool probe_lambda(const double (&Ji)[DIM][DIM], const double (&X0)[DIM], const double *x, double tol, double (&lam)[DIM + 1]) {
+  double l0 = 1.0;
+  bool in = true;
+#pragma unroll
+  for (int k = 0; k < DIM; ++k) {
+    double s = 0.0;
+#pragma unroll
+    for (int d = 0; d < DIM; ++d) s += Ji[k][d] * (x[d] - X0[d]);
+    lam[k + 1] = s;
+    l0 -= s;
+    in = in && s >= -tol;
+  }
+  lam[0] = l0;
+  return in && l0 >= -tol;
+}
+
+template <int DIM>
+__device__ __forceinline__ void load_cell_map(int n_cells, int cell, const double *__restrict__ geo, const double *__restrict__ x0, double (&Ji)[DIM][DIM],
+                                              double (&X0)[DIM]) {
+#pragma unroll
+  for (int k = 0; k < DIM; ++k) {
+    X0[k] = x0[(size_t)k * n_cells + cell];
+#pragma unroll
+    for (int d = 0; d < DIM; ++d) Ji[k][d] = geo[(size_t)(k * DIM + d) * n_cells + cell];
+  }
+}
+
+// tracer particles (nsx_tracer.hip)
+void tracer_clear(nsx_handle *h);  // a new mesh drops the tracer set and the face-neighbour table
 
 // sparse (nsx_sparse.hip)
 bool blocked_usable(const nsx_handle *h);                                                   // F->vmult goes through the LDS-staged SpMV

@@ -27,37 +27,7 @@ namespace nsx {
 
 constexpr int PROBE_TILE = 64;        // points staged in LDS at a time
 constexpr int PROBE_MAX = 65536;
-constexpr double PROBE_TOL = 1e-12;   // the tolerance of nsxh_pressure_difference
 constexpr int PROBE_RANK_BITS = 48;   // ranks per double of the owner collective
-
-// lambda[0..DIM] of x in the cell (X0, J^-1): x = X0 + J lambda[1..], lambda[0] = 1 - sum.  A coordinate that is not finite is in no cell.
-template <int DIM>
-__device__ __forceinline__ bool probe_lambda(const double (&Ji)[DIM][DIM], const double (&X0)[DIM], const double *x, double tol, double (&lam)[DIM + 1]) {
-  double l0 = 1.0;
-  bool in = true;
-#pragma unroll
-  for (int k = 0; k < DIM; ++k) {
-    double s = 0.0;
-#pragma unroll
-    for (int d = 0; d < DIM; ++d) s += Ji[k][d] * (x[d] - X0[d]);
-    lam[k + 1] = s;
-    l0 -= s;
-    in = in && s >= -tol;
-  }
-  lam[0] = l0;
-  return in && l0 >= -tol;
-}
-
-template <int DIM>
-__device__ __forceinline__ void load_cell_map(int n_cells, int cell, const double *__restrict__ geo, const double *__restrict__ x0, double (&Ji)[DIM][DIM],
-                                              double (&X0)[DIM]) {
-#pragma unroll
-  for (int k = 0; k < DIM; ++k) {
-    X0[k] = x0[(size_t)k * n_cells + cell];
-#pragma unroll
-    for (int d = 0; d < DIM; ++d) Ji[k][d] = geo[(size_t)(k * DIM + d) * n_cells + cell];
-  }
-}
 
 // best[p] starts at INT32_MAX.  counted: the cells this handle searches (all of them on one process; diag_counted in a distributed run).
 template <int DIM>
@@ -205,15 +175,19 @@ void probe_clear(nsx_handle *h) {
 }
 
 template <int DIM>
-static void launch_locate(nsx_handle *h, int n, const double *points, double tol, int32_t *best) {
+static void launch_locate(nsx_handle *h, int n, const double *points, double tol, int32_t *best, int32_t *cells, double *lam) {
   {
     LaunchScope ls(h, "probe_locate", 8.0 * (DIM * DIM + DIM) * h->n_cells);
     hipLaunchKernelGGL((k_probe_locate<DIM>), dim3(cdiv(h->n_cells, 64)), dim3(64), 0, h->stream, h->n_cells, h->diag_counted.p, h->geo.p, h->cell_x0.p, n,
                        points, tol, best);
   }
-  hipLaunchKernelGGL((k_probe_finish<DIM>), dim3(cdiv(n, 64)), dim3(64), 0, h->stream, h->n_cells, h->geo.p, h->cell_x0.p, n, points, best, h->probe_cell.p,
-                     h->probe_lambda.p);
+  hipLaunchKernelGGL((k_probe_finish<DIM>), dim3(cdiv(n, 64)), dim3(64), 0, h->stream, h->n_cells, h->geo.p, h->cell_x0.p, n, points, best, cells, lam);
   HIP_CHECK(hipGetLastError());
+}
+
+void probe_locate(nsx_handle *h, int n, const double *points, double tol, int32_t *best, int32_t *cells, double *lam) {
+  if (h->dim == 2) launch_locate<2>(h, n, points, tol, best, cells, lam);
+  else launch_locate<3>(h, n, points, tol, best, cells, lam);
 }
 
 static void set_probes(nsx_handle *h, int n, const double *points, double tol) {
@@ -236,8 +210,7 @@ static void set_probes(nsx_handle *h, int n, const double *points, double tol) {
   h->probe_cell.alloc(n);
   h->probe_lambda.alloc((size_t)nl * n);
   h->probe_out.alloc((size_t)(dim + 1 + dim * dim) * n);
-  if (dim == 2) launch_locate<2>(h, n, pts.p, tol, best.p);
-  else launch_locate<3>(h, n, pts.p, tol, best.p);
+  probe_locate(h, n, pts.p, tol, best.p, h->probe_cell.p, h->probe_lambda.p);
   std::vector<int32_t> cells((size_t)n), owner((size_t)n);
   std::vector<double> lam_soa((size_t)nl * n);
   h->probe_cell.download(cells.data(), cells.size(), h->stream);

@@ -974,6 +974,7 @@ int nsx_set_mesh(nsx_handle *h, int n_cells, int dpc, const int32_t *cell_dofs, 
   h->cell_n1_in = h->cell_n1_h;
   h->cell_coords_in.assign(cell_coords, cell_coords + (size_t)n_cells * nv * dim);
   probe_clear(h);
+  tracer_clear(h);
   h->n_cells1 = n_cells;
   h->haloU.send_idx_in.clear();
   h->haloP.send_idx_in.clear();
@@ -1048,6 +1049,7 @@ int nsx_set_mesh_distributed(nsx_handle *h, int n_cells, int n_cells1, int dpc, 
   h->cell_n1_in = h->cell_n1_h;
   h->cell_coords_in.assign(cell_coords, cell_coords + (size_t)n_cells * nv * dim);
   probe_clear(h);
+  tracer_clear(h);
   h->n_cells1 = n_cells1;
   default_ranks(h);
   install_mesh(h);

@@ -8,6 +8,7 @@
 // but every loop of the hot path runs in libnsx on the GPU.  Errors surface as C++ exceptions, as in the reference
 // (SolverControl::NoConvergence -> nsx::NoConvergence, std::runtime_error for everything else).
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -117,6 +118,16 @@ public:
       const double pts3[6] = {0.45, 0.2, 0.205, 0.55, 0.2, 0.205}, pts2[4] = {0.15, 0.2, 0.25, 0.2};
       ck(nsx_set_probes(h, 2, dim == 3 ? pts3 : pts2, -1.0));
     }
+    if (n_tracers > 0) {  // opt-in (NSX_TRACERS=<n>): n seeds on a line across the channel upstream of the obstacle, located once
+      std::vector<double> seeds((size_t)n_tracers * dim);
+      for (int k = 0; k < n_tracers; ++k) {
+        const double y = n_tracers > 1 ? 0.1 + 0.2 * k / (n_tracers - 1) : 0.2;  // the obstacle spans y in [0.15, 0.25]
+        seeds[(size_t)k * dim] = dim == 3 ? 0.25 : 0.1;                         // its centre is at x = 0.5 (3D) / 0.2 (2D)
+        seeds[(size_t)k * dim + 1] = y;
+        if (dim == 3) seeds[(size_t)k * dim + 2] = 0.205;
+      }
+      ck(nsx_set_tracers(h, n_tracers, seeds.data(), -1.0));
+    }
   }
 
   void solve() {  // NavierStokes3D.cpp:687-741
@@ -137,6 +148,7 @@ public:
       current_time = time;
       if (diagnostics_csv) write_diagnostics(time_step, time);
       if (probes_csv) write_pressure_difference(time_step, time);
+      if (n_tracers > 0) write_tracers(time_step, time);
       // NavierStokes3D.cpp:725-726, as written: an EXACT floating-point comparison of the accumulated time with T - deltat (true or false
       // by the rounding of the additions; the reference's own run decides it the same way, so the mirror does not "repair" it)
       if (dim == 3 && time == T - deltat) compute_pressure_difference();
@@ -302,6 +314,25 @@ protected:
     file << row;
   }
 
+  // opt-in series (NSX_TRACERS=<n>): the particles are carried through the step just solved (RK4, the field interpolated linearly in time
+  // from previous_solution to solution, 4 substeps) and one row per particle is appended to tracers_{2D,3D}.csv:
+  // step, time, particle, x, y[, z], cell, status, exit face, age
+  void write_tracers(const unsigned int time_step, const double time) const {
+    ck(nsx_advect_tracers(h, deltat, 4, NSX_TRACER_RK4, NSX_TRACER_LINEAR));
+    std::vector<double> x((size_t)n_tracers * dim), age(n_tracers);
+    std::vector<int32_t> cell(n_tracers), status(n_tracers), face(n_tracers);
+    ck(nsx_get_tracers(h, x.data(), cell.data(), status.data(), face.data(), age.data()));
+    std::ofstream file(dim == 3 ? "tracers_3D.csv" : "tracers_2D.csv", std::ios::app);
+    if (!file.is_open()) throw std::runtime_error("cannot write the tracer file");
+    char row[320];
+    for (int k = 0; k < n_tracers; ++k) {
+      int n = snprintf(row, sizeof(row), "%u,%.17g,%d", time_step, time, k);
+      for (int d = 0; d < dim; ++d) n += snprintf(row + n, sizeof(row) - n, ",%.17g", x[(size_t)k * dim + d]);
+      snprintf(row + n, sizeof(row) - n, ",%d,%d,%d,%.17g\n", cell[k], status[k], face[k], age[k]);
+      file << row;
+    }
+  }
+
   void setup_force_faces() {  // faces with boundary id 3 and the face-quadrature tables (FEFaceValues of compute_forces)
     static const int TETF[4][3] = {{0, 1, 2}, {1, 0, 3}, {0, 2, 3}, {2, 1, 3}};
     static const int TRIF[3][2] = {{0, 1}, {1, 2}, {2, 0}};
@@ -353,6 +384,7 @@ protected:
   double current_time = 0.0;
   const bool diagnostics_csv = std::getenv("NSX_DIAGNOSTICS") && std::string(std::getenv("NSX_DIAGNOSTICS")) == "1";
   const bool probes_csv = std::getenv("NSX_PROBES") && std::string(std::getenv("NSX_PROBES")) == "1";
+  const int n_tracers = std::getenv("NSX_TRACERS") ? std::max(0, std::min(1048576, std::atoi(std::getenv("NSX_TRACERS")))) : 0;
 };
 
 }  // namespace nsx

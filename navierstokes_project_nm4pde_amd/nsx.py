@@ -26,7 +26,7 @@ API = [
     "nsx_comm_init", "nsx_comm_init_callbacks", "nsx_comm_counters", "nsx_set_mesh_distributed", "nsx_set_force_faces", "nsx_compute_forces",
     "nsx_set_internal_layout", "nsx_layout_info", "nsx_layout_get", "nsx_gram_schmidt_cycle", "nsx_set_inner_precision",
     "nsx_gram_schmidt_sweeps", "nsx_compute_diagnostics", "nsx_get_cell_diagnostic", "nsx_schur_cg",
-    "nsx_set_probes", "nsx_get_probe_cells", "nsx_eval_probes",
+    "nsx_set_probes", "nsx_get_probe_cells", "nsx_eval_probes", "nsx_set_tracers", "nsx_advect_tracers", "nsx_get_tracers",
 ]
 # declared in include/nsx.h as well, but with a capital letter in its name, which the header scan of tests/test_abi.py (lower case only)
 # does not see: kept beside the list that scan is compared with; build() checks both
@@ -35,6 +35,9 @@ FIRST_TOUCH, COLOUR, COLOUR_ALL = 0, 1, 2  # node order of nsx_set_internal_layo
 INNER_FP64, INNER_FP32 = 0, 1  # nsx_set_inner_precision: how F and the ILU(0) entries of F are stored for the inner solves
 # planes of nsx_get_cell_diagnostic (NSX_DIAG_*)
 DIAG_ENERGY, DIAG_DIV2, DIAG_GRAD2, DIAG_ENSTROPHY, DIAG_CHANGE2, DIAG_VOLUME, DIAG_CFL, DIAG_SPEED, DIAG_COUNT = range(9)
+TRACER_EULER, TRACER_RK2, TRACER_RK4 = 1, 2, 4                                   # NSX_TRACER_*: scheme
+TRACER_FROZEN, TRACER_LINEAR = 0, 1                                              # field
+TRACER_NOT_FOUND, TRACER_ACTIVE, TRACER_EXITED, TRACER_LOST = 0, 1, 2, 3         # status
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, _f64p, C.c_int)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(_f64p), C.POINTER(C.c_int),
@@ -126,6 +129,9 @@ def lib():
     L.nsx_set_probes.argtypes = [vp, C.c_int, _f64p, C.c_double]
     L.nsx_get_probe_cells.argtypes = [vp, _i32p, _i32p, _f64p]
     L.nsx_eval_probes.argtypes = [vp, _f64p, _f64p, _f64p, _i32p]
+    L.nsx_set_tracers.argtypes = [vp, C.c_int, _f64p, C.c_double]
+    L.nsx_advect_tracers.argtypes = [vp, C.c_double, C.c_int, C.c_int, C.c_int]
+    L.nsx_get_tracers.argtypes = [vp, _f64p, _i32p, _i32p, _i32p, _f64p]
     L.nsx_set_inner_precision.argtypes = [vp, C.c_int]
     L.nsx_inner_F_vmult.argtypes = [vp, _f64p, _f64p]
     L.nsx_schur_cg.argtypes = [vp, C.c_double, C.c_int, _f64p, _f64p, C.POINTER(C.c_int), _f64p, C.POINTER(C.c_int)]
@@ -533,6 +539,28 @@ class Nsx:
         out["found"] = found.astype(bool)
         if gradient:
             out["gradient"] = grad
+        return out
+
+    # -- tracer particles ----------------------------------------------------------------------
+    def set_tracers(self, points, tol=-1.0):
+        """nsx_set_tracers: locate the seeds [n][dim] and make them the handle's tracer set (an empty list clears it); returns the
+        statuses (TRACER_ACTIVE, or TRACER_NOT_FOUND for a seed in no cell)"""
+        pts = _cd(points).reshape(-1, self.dim)
+        self._ck(self.L.nsx_set_tracers(self._h, len(pts), _d(pts), float(tol)))
+        self._n_tracers = len(pts)              # a refused call leaves the earlier set (and its size) in place
+        return self.get_tracers()["status"] if len(pts) else np.empty(0, np.int32)
+
+    def advect_tracers(self, dt, n_substeps=1, scheme=TRACER_RK4, field=TRACER_FROZEN):
+        """nsx_advect_tracers: n_substeps steps of size dt / n_substeps through u_h of the state the handle holds (TRACER_LINEAR: from
+        previous_solution to solution across the call); dt < 0 traces backwards"""
+        self._ck(self.L.nsx_advect_tracers(self._h, float(dt), int(n_substeps), int(scheme), int(field)))
+
+    def get_tracers(self):
+        """{"positions" [n][dim], "cells" [n], "status" [n], "exit_faces" [n], "age" [n]} of the tracer set (nsx_get_tracers)"""
+        n = getattr(self, "_n_tracers", 0)
+        out = {"positions": np.empty((n, self.dim)), "cells": np.empty(n, np.int32), "status": np.empty(n, np.int32),
+               "exit_faces": np.empty(n, np.int32), "age": np.empty(n)}
+        self._ck(self.L.nsx_get_tracers(self._h, _d(out["positions"]), _i(out["cells"]), _i(out["status"]), _i(out["exit_faces"]), _d(out["age"])))
         return out
 
     # -- export --------------------------------------------------------------------------------
