@@ -200,6 +200,29 @@ int nsx_inner_F_vmult(nsx_handle *h, double *dst, const double *src);
  * handles: length n_p of the whole mesh, globally indexed as for nsx_system_vmult; every rank calls, only the owned entries of b and x
  * are read and only the owned entries of x are written.  After nsx_prec_initialize (otherwise the usual call-order NSX_ERR_ARG). */
 int nsx_schur_cg(nsx_handle *h, double rtol, int maxiter, double *x, const double *b, int *steps, double *last_residual, int *status);
+/* Test hook: ONE sparse product of the solver on the caller's vectors, by the very function the solver calls (csrc/nsx_sparse.hip), so
+ * that each product kernel can be compared with a reference on its own (tests/test_gpu_sparse.py).  dst, src and aux are host vectors of
+ * length n_u + n_p of the whole mesh, globally indexed exactly as for nsx_system_vmult; x_u / x_p are the velocity / pressure part of src.
+ * Works on single-process and on distributed handles (every rank calls; the ghosts travel through the halo exchange of the product); a
+ * distributed handle writes only its owned entries of dst.  The entries `op` does not produce come back 0.  aux may be NULL where unused.
+ *   NSX_PROD_F          y_u = F x_u                          spmv_F on F as assembled (system_matrix.vmult's velocity block)
+ *   NSX_PROD_F_INNER    y_u = F x_u                          spmv_F_inner: F in the handle's inner precision (as nsx_inner_F_vmult)
+ *   NSX_PROD_F_RESID    y_u = aux_u - F x_u                  spmv_F_inner_resid: the residual of an inner solve's cycle
+ *   NSX_PROD_MASS       y_u = (M / deltat) x_u               spmv_F on the mass values: the product that forms every right-hand side
+ *   NSX_PROD_B          y_p = B x_u                          spmv_B
+ *   NSX_PROD_B_MINUS_R  y_p = B x_u - aux_p                  spmv_B(.., aux, +1)
+ *   NSX_PROD_R_MINUS_B  y_p = aux_p - B x_u                  spmv_B(.., aux, -1)
+ *   NSX_PROD_G          y_u = G x_p                          spmv_G, overwriting       (G = block(0,1), B = block(1,0))
+ *   NSX_PROD_G_ACC      y_u = aux_u + G x_p                  spmv_G accumulating onto a y preloaded with aux_u
+ *   NSX_PROD_S          y_p = S x_p                          spmv_S: negative_S_tilde of the last initialisation
+ *   NSX_PROD_SADDLE     as nsx_system_vmult                  spmv_saddle
+ * Documented bitwise identities (the fused epilogues act on the finished row sum): F_RESID == aux - F_INNER, B_MINUS_R == B - aux,
+ * R_MINUS_B == aux - B, G_ACC == aux + G, and where the LDS-staged kernel runs (nsx_path_info [0]) the velocity part of SADDLE == F + G.
+ * NSX_ERR_ARG: null dst / src, nothing assembled, F_INNER / F_RESID / S before nsx_prec_initialize, aux missing, unknown op.
+ * nsx_path_info [26] afterwards says whether this call streamed float values. */
+enum { NSX_PROD_F = 0, NSX_PROD_F_INNER, NSX_PROD_F_RESID, NSX_PROD_MASS, NSX_PROD_B, NSX_PROD_B_MINUS_R, NSX_PROD_R_MINUS_B, NSX_PROD_G,
+       NSX_PROD_G_ACC, NSX_PROD_S, NSX_PROD_SADDLE, NSX_PROD_COUNT };
+int nsx_sparse_product(nsx_handle *h, int op, double *dst, const double *src, const double *aux);
 
 /* ---- export in the reference's own layout (Trilinos block CSR with all velocity couplings stored) ---- */
 /* which: 0 system_matrix, 1 mass_matrix, 2 convection_matrix, 3 stiffness_matrix, 4 pressure_mass
@@ -382,10 +405,15 @@ int nsx_persistent_state(nsx_handle *h, int state[4]);
  * ILU(0) inside its launch (k_ilu_mgs: PreconditionILU::vmult + the orthogonalisation of one inner GMRES iteration, reference
  * Preconditioners.hpp:382,405, as ONE kernel), [25] such launches so far, [26] 1 = the inner F products of the last solve streamed float
  * values (NSX_INNER_FP32 through the LDS-staged SpMV), [27] 1 = its velocity triangular solves did (the lane-owner stream) -- "solve":
- * the last nsx_solve_time_step / nsx_prec_vmult, or the last call of the test hooks nsx_inner_F_vmult ([26]) / nsx_ilu_apply(0) ([27]);
+ * the last nsx_solve_time_step / nsx_prec_vmult, or the last call of the test hooks nsx_inner_F_vmult / nsx_sparse_product ([26]) /
+ * nsx_ilu_apply(0) ([27]);
  * [28] rows per lane group of the register-resident block inverses in the last Schur-complement CG (6: blocks of up to 96 rows, 8: up to
  * 128; 0: the inverses were streamed, or the persistent kernel did not run), [29] 1 = that kernel held the operator's rows in LDS;
- * [30..31] reserved (0). */
+ * [30] rows of the largest chunk of the LDS-staged SpMV, [31] staged columns of the chunk that stages most (the kernel serves chunks of
+ * up to 448 rows whose staged x entries fit 64 KiB of LDS; [0] says whether it is used).
+ * The switches of the velocity product are read once by nsx_create, like NSX_INNER_PRECISION: NSX_SPMV_W (lanes per row of the plain
+ * kernel: 8 / 32, anything else 16), NSX_SPMV_BLOCKED=0 (never the LDS-staged kernel), NSX_SPMV_ORDER=0 (its chunks in row order instead of
+ * largest first).  NSX_SPMV_R (target rows per chunk, 16..448, default 130) is read whenever the chunk table is rebuilt. */
 int nsx_path_info(nsx_handle *h, int info[32]);
 
 /* Which kernels the block-Jacobi ILU(0) of F (which = 0) or of the Schur matrix (which = 1) ran -- a test hook:

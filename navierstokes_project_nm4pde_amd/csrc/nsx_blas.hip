@@ -462,6 +462,8 @@ extern "C" int nsx_path_info(nsx_handle *h, int info[32]) {
     info[27] = h->ilu_F_fp32_used;
     info[28] = h->cg_last_rpg;
     info[29] = h->cg_last_lres;
+    info[30] = b.max_rows;
+    info[31] = b.max_ucols;
   } catch (const nsx::Error &e) {
     h->err = e.msg;
     return e.code;

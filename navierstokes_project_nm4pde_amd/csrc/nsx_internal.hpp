@@ -310,6 +310,10 @@ struct nsx_handle {
   // ---- graphs and values
   nsx::DevCsr gA, gG, gB, gS, gPM;
   nsx::SpmvBlocked blkA;
+  // the switches of the velocity product, read once by nsx_create: NSX_SPMV_W lanes per row of the plain kernel (8 / 16 / 32), NSX_SPMV_BLOCKED=0
+  // never the LDS-staged kernel, NSX_SPMV_ORDER=0 its chunks in row order instead of largest first
+  int spmv_w = 16;
+  bool spmv_blocked = true, spmv_largest_first = true;
   nsx::DevBuf<double> vS0, vMass, vStiff, vConv, vF, vG, vB, vPM, vSchur, luF, luS;
   // ---- inner precision (nsx_set_inner_precision): how F and the off-diagonal ILU(0) entries of F are STORED for the inner solves
   int inner_precision = NSX_INNER_FP64;

@@ -306,7 +306,7 @@ void build_blocked(nsx_handle *h, const Csr &g, const std::vector<int32_t> &boun
     grid = 8 * per_xcd;
     if (order) order->assign((size_t)grid, -1);
     std::vector<int32_t> desc((size_t)grid * 4, 0), list;
-    static const bool largest_first = !(getenv("NSX_SPMV_ORDER") && atoi(getenv("NSX_SPMV_ORDER")) == 0);
+    const bool largest_first = h->spmv_largest_first;
     for (int k = 0; k < 8; ++k) {
       list.assign(chunks.begin() + cut[k], chunks.begin() + cut[k + 1]);
       if (largest_first) std::stable_sort(list.begin(), list.end(), [&](int32_t a, int32_t c) { return cnnz(a) > cnnz(c); });
@@ -609,6 +609,10 @@ int nsx_create(const nsx_params *p, nsx_handle **out) {
   h->prm = *p;
   h->dim = p->dim;
   if (getenv("NSX_GX_DROP_WG")) h->gx_drop_wg = atoi(getenv("NSX_GX_DROP_WG"));  // fault injection for the tests of the time-out fallbacks
+  // the switches of the velocity product, per handle like the inner precision (defaults 16 / 1 / 1)
+  if (getenv("NSX_SPMV_W")) h->spmv_w = atoi(getenv("NSX_SPMV_W"));
+  h->spmv_blocked = !(getenv("NSX_SPMV_BLOCKED") && atoi(getenv("NSX_SPMV_BLOCKED")) == 0);
+  h->spmv_largest_first = !(getenv("NSX_SPMV_ORDER") && atoi(getenv("NSX_SPMV_ORDER")) == 0);
   if (const char *ip = getenv("NSX_INNER_PRECISION")) {  // the handle's initial inner precision (nsx_set_inner_precision)
     if (!strcmp(ip, "fp32")) h->inner_precision = NSX_INNER_FP32;
     else if (!strcmp(ip, "fp64")) h->inner_precision = NSX_INNER_FP64;

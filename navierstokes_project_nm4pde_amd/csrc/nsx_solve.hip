@@ -776,6 +776,43 @@ int nsx_inner_F_vmult(nsx_handle *h, double *dst, const double *src) {
   })
 }
 
+int nsx_sparse_product(nsx_handle *h, int op, double *dst, const double *src, const double *aux) {
+  NSX_API_BODY(h, {
+    if (!dst || !src || !h->assembled) NSX_THROW(NSX_ERR_ARG, "null vector / nothing assembled");
+    if (op < 0 || op >= NSX_PROD_COUNT) NSX_THROW(NSX_ERR_ARG, "unknown sparse product %d", op);
+    const bool inner = op == NSX_PROD_F_INNER || op == NSX_PROD_F_RESID || op == NSX_PROD_S;
+    if (inner && !h->prec_ready) NSX_THROW(NSX_ERR_ARG, "call nsx_prec_initialize first (F's copy in the inner precision and the Schur complement are its work)");
+    const bool wants_aux = op == NSX_PROD_F_RESID || op == NSX_PROD_B_MINUS_R || op == NSX_PROD_R_MINUS_B || op == NSX_PROD_G_ACC;
+    if (wants_aux && !aux) NSX_THROW(NSX_ERR_ARG, "this product reads aux");
+    HIP_CHECK(hipSetDevice(h->prm.device));
+    nsx::ensure_schedules(h);
+    nsx::Tmp d(h, h->len_blk), s(h, h->len_blk), a(h, h->len_blk);
+    nsx::vec_from_caller(h, s.p(), src, false);
+    if (wants_aux) nsx::vec_from_caller(h, a.p(), aux, false);
+    // what the product does not write comes back as 0; NSX_PROD_G_ACC accumulates onto aux_u
+    if (op == NSX_PROD_G_ACC) nsx::vec_from_caller(h, d.p(), aux, false);
+    else HIP_CHECK(hipMemsetAsync(d.p(), 0, (size_t)h->len_blk * sizeof(double), h->stream));
+    h->inner_F_fp32_used = 0;
+    const double *xu = s.p(), *xp = s.p() + h->off_p, *au = a.p(), *ap = a.p() + h->off_p;
+    double *yu = d.p(), *yp = d.p() + h->off_p;
+    switch (op) {
+      case NSX_PROD_F: nsx::spmv_F(h, h->vF.p, xu, yu); break;
+      case NSX_PROD_F_INNER: nsx::spmv_F_inner(h, xu, yu); break;
+      case NSX_PROD_F_RESID: nsx::spmv_F_inner_resid(h, xu, au, yu); break;
+      case NSX_PROD_MASS: nsx::spmv_F(h, h->vMass.p, xu, yu); break;
+      case NSX_PROD_B: nsx::spmv_B(h, xu, yp, nullptr, 0); break;
+      case NSX_PROD_B_MINUS_R: nsx::spmv_B(h, xu, yp, ap, 1); break;
+      case NSX_PROD_R_MINUS_B: nsx::spmv_B(h, xu, yp, ap, -1); break;
+      case NSX_PROD_G: nsx::spmv_G(h, xp, yu, false); break;
+      case NSX_PROD_G_ACC: nsx::spmv_G(h, xp, yu, true); break;
+      case NSX_PROD_S: nsx::spmv_S(h, xp, yp); break;
+      default: nsx::spmv_saddle(h, s.p(), d.p()); break;
+    }
+    if (op == NSX_PROD_G_ACC) HIP_CHECK(hipMemsetAsync(yp, 0, (size_t)(h->len_blk - h->off_p) * sizeof(double), h->stream));  // aux_p is no result
+    nsx::vec_to_caller(h, d.p(), dst);
+  })
+}
+
 int nsx_schur_cg(nsx_handle *h, double rtol, int maxiter, double *x, const double *b, int *steps, double *last_residual, int *status) {
   NSX_API_BODY(h, {
     if (!x || !b || !steps || !last_residual || !status) NSX_THROW(NSX_ERR_ARG, "null argument");

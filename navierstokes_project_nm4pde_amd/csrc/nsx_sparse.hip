@@ -322,7 +322,7 @@ static double bytes_vel(nsx_handle *h, bool with_g, bool f32 = false) {
 static void launch_vel(nsx_handle *h, bool with_g, const double *vals, const double *x, const double *xp, double *y, const int32_t *rows, int n,
                        const double *b = nullptr) {
   if (n <= 0) return;
-  static const int Wsel = getenv("NSX_SPMV_W") ? atoi(getenv("NSX_SPMV_W")) : 16;
+  const int Wsel = h->spmv_w;
   if (b) {
 #define NSX_SPMV_R(D, W_)                                                                                                               \
   hipLaunchKernelGGL((k_spmv_vel_resid<D, W_>), dim3((cdiv((int64_t)n * W_, 256) + 7) & ~7), dim3(256), 0, h->stream, n, h->gA.rowptr.p, \
@@ -385,9 +385,8 @@ static void launch_S(nsx_handle *h, const double *x, double *y, const int32_t *r
 // This is the Epetra_Import + local multiply of every vmult with the import hidden behind the interior rows.
 // y_u = A x_u through the LDS-staged kernel; false if the handle has no chunk table for it
 bool blocked_usable(const nsx_handle *h) {
-  static const bool blocked = !(getenv("NSX_SPMV_BLOCKED") && atoi(getenv("NSX_SPMV_BLOCKED")) == 0);
   const SpmvBlocked &b = h->blkA;
-  return blocked && b.n_chunks > 0 && b.max_rows <= 448 && (size_t)b.max_ucols * h->dim * sizeof(double) <= 64 * 1024;
+  return h->spmv_blocked && b.n_chunks > 0 && b.max_rows <= 448 && (size_t)b.max_ucols * h->dim * sizeof(double) <= 64 * 1024;
 }
 // part 0: the table of a one-GPU handle / the chunks of a distributed handle whose staged columns are all owned; part 1: the chunks that
 // stage a ghost column (distributed handles only; an empty table launches nothing)

@@ -27,6 +27,7 @@ API = [
     "nsx_set_internal_layout", "nsx_layout_info", "nsx_layout_get", "nsx_gram_schmidt_cycle", "nsx_set_inner_precision",
     "nsx_gram_schmidt_sweeps", "nsx_compute_diagnostics", "nsx_get_cell_diagnostic", "nsx_schur_cg",
     "nsx_set_probes", "nsx_get_probe_cells", "nsx_eval_probes", "nsx_set_tracers", "nsx_advect_tracers", "nsx_get_tracers",
+    "nsx_sparse_product",
 ]
 # declared in include/nsx.h as well, but with a capital letter in its name, which the header scan of tests/test_abi.py (lower case only)
 # does not see: kept beside the list that scan is compared with; build() checks both
@@ -35,6 +36,8 @@ FIRST_TOUCH, COLOUR, COLOUR_ALL = 0, 1, 2  # node order of nsx_set_internal_layo
 INNER_FP64, INNER_FP32 = 0, 1  # nsx_set_inner_precision: how F and the ILU(0) entries of F are stored for the inner solves
 # planes of nsx_get_cell_diagnostic (NSX_DIAG_*)
 DIAG_ENERGY, DIAG_DIV2, DIAG_GRAD2, DIAG_ENSTROPHY, DIAG_CHANGE2, DIAG_VOLUME, DIAG_CFL, DIAG_SPEED, DIAG_COUNT = range(9)
+# ops of nsx_sparse_product (NSX_PROD_*)
+PROD_F, PROD_F_INNER, PROD_F_RESID, PROD_MASS, PROD_B, PROD_B_MINUS_R, PROD_R_MINUS_B, PROD_G, PROD_G_ACC, PROD_S, PROD_SADDLE, PROD_COUNT = range(12)
 TRACER_EULER, TRACER_RK2, TRACER_RK4 = 1, 2, 4                                   # NSX_TRACER_*: scheme
 TRACER_FROZEN, TRACER_LINEAR = 0, 1                                              # field
 TRACER_NOT_FOUND, TRACER_ACTIVE, TRACER_EXITED, TRACER_LOST = 0, 1, 2, 3         # status
@@ -135,6 +138,7 @@ def lib():
     L.nsx_set_inner_precision.argtypes = [vp, C.c_int]
     L.nsx_inner_F_vmult.argtypes = [vp, _f64p, _f64p]
     L.nsx_schur_cg.argtypes = [vp, C.c_double, C.c_int, _f64p, _f64p, C.POINTER(C.c_int), _f64p, C.POINTER(C.c_int)]
+    L.nsx_sparse_product.argtypes = [vp, C.c_int, _f64p, _f64p, _f64p]
     L._nsx_ready = True
     return L
 
@@ -248,7 +252,8 @@ class Nsx:
                  "sweep_entries_per_thread_max", "cus_reserved", "schur_cg_path", "schur_blocks", "neighbours", "nodes_sent_per_exchange", "ghost_nodes",
                  "schur_dense_inverses", "sweep_off", "fallbacks", "rccl_sweep_velocity_plain", "rccl_sweep_velocity_masked", "rccl_sweep_block_plain",
                  "rccl_sweep_block_masked", "schur_blocks_per_partial", "sweep_velocity_one_gpu", "owned_p2_nodes", "owned_p1_nodes", "sweep_with_ilu_inside", "fused_launches",
-                 "inner_F_fp32", "ilu_F_fp32", "schur_cg_rows_per_lane_group", "schur_cg_operator_in_lds")
+                 "inner_F_fp32", "ilu_F_fp32", "schur_cg_rows_per_lane_group", "schur_cg_operator_in_lds",
+                 "spmv_max_chunk_rows", "spmv_max_staged_columns")
 
     def path_info(self):
         """dict: which code paths the handle's products and solves take (nsx_path_info; schur_cg_path: 1 launch per operation,
@@ -426,6 +431,17 @@ class Nsx:
         src = _cd(src)
         dst = np.empty_like(src)
         self._ck(self.L.nsx_inner_F_vmult(self._h, _d(dst), _d(src)))
+        return dst
+
+    def sparse_product(self, op, x, aux=None):
+        """nsx_sparse_product: one sparse product of the solver (PROD_*) on block vectors of length n_u + n_p, by the function the solver
+        calls; the entries the op does not produce are 0.  In a multi-process run the vectors are globally indexed, every rank calls, and
+        the entries this rank does not own come back as 0 (sum over the ranks for the whole vector)."""
+        x = _cd(x)
+        aux = None if aux is None else _cd(aux)
+        assert x.shape == (self.n,) and (aux is None or aux.shape == (self.n,))
+        dst = np.zeros_like(x)
+        self._ck(self.L.nsx_sparse_product(self._h, int(op), _d(dst), _d(x), None if aux is None else _d(aux)))
         return dst
 
     def ilu_apply(self, which, src):

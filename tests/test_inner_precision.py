@@ -73,7 +73,9 @@ def test_binding_declares_the_inner_precision_interface():
     assert "nsx_set_inner_precision" in nsx.API and "nsx_inner_F_vmult" in nsx.API + nsx.API_EXTRA
     assert nsx.Nsx.PATH_KEYS[26:28] == ("inner_F_fp32", "ilu_F_fp32")
     # (slots 28 and 29 report the persistent Schur CG's variant since the hook nsx_schur_cg exists)
-    assert nsx.Nsx.PATH_KEYS[28:] == ("schur_cg_rows_per_lane_group", "schur_cg_operator_in_lds") and len(nsx.Nsx.PATH_KEYS) == 30
+    # (slots 30 and 31 the largest chunk of the LDS-staged SpMV since the hook nsx_sparse_product exists: all 32 slots are named)
+    assert nsx.Nsx.PATH_KEYS[28:30] == ("schur_cg_rows_per_lane_group", "schur_cg_operator_in_lds")
+    assert nsx.Nsx.PATH_KEYS[30:] == ("spmv_max_chunk_rows", "spmv_max_staged_columns") and len(nsx.Nsx.PATH_KEYS) == 32
     for name in ("set_inner_precision", "inner_F_vmult"):
         assert callable(getattr(nsx.Nsx, name))
     hdr = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "nsx.h")).read()
