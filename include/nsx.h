@@ -376,6 +376,53 @@ int nsx_advect_tracers(nsx_handle *h, double dt, int n_substeps, int scheme, int
  * Any pointer may be NULL. */
 int nsx_get_tracers(nsx_handle *h, double *positions /*[n][dim]*/, int32_t *cells, int32_t *status, int32_t *exit_faces, double *age);
 
+/* ---- nodal fields ---- */
+/* Gradient-derived fields at the P2 nodes, on the device: vorticity, Q-criterion, strain rate -- what a contour plot or an isosurface needs.
+ * The per-cell values of nsx_get_cell_diagnostic are constants per cell and the gradient of nsx_eval_probes is taken in one cell only (it
+ * jumps across faces); this is the continuous nodal field between the two.  No counterpart in the reference (its output() writes velocity and
+ * pressure; DataPostprocessors would loop over the cells on the host).
+ * Recovered gradient.  For every P2 node n the handle owns
+ *     Gbar(n) = ( sum_c |c| grad u_h|_c(x_n) ) / ( sum_c |c| )
+ * c runs over the cells of the mesh that hold n (all cells round the vertex, or round the edge for a mid-edge node) IN ASCENDING POSITION OF
+ * THE CALLER'S CELL LIST, both sums folded left to right in double; |c| = |det J| / 2 (triangles), |det J| / 6 (tetrahedra);
+ * grad u_h|_c(x_n) is evaluated exactly as nsx_eval_probes evaluates its gradient -- the P2 shape functions in barycentric form, local line order
+ * {0,1},{1,2},{2,0}[,{0,3},{1,3},{2,3}], G_ij = d_j u_i = ((sum_a U_a (x) grad_lambda N_a) J^-1)_ij -- at the barycentric position of the node in
+ * c: the unit vector e_k for local vertex k, (e_i + e_j) / 2 for the line {i, j}.  u is the velocity part of the ghosted `solution` (current
+ * after nsx_set_solution and after nsx_solve_time_step).  An owned node that no cell holds gets exact zeros.
+ * Derived fields, all computed from Gbar (not averaged separately), S = (Gbar + Gbar^T) / 2, W = (Gbar - Gbar^T) / 2:
+ *     NSX_FIELD_GRADIENT    dim^2 components   Gbar_ij, row-major
+ *     NSX_FIELD_VORTICITY   3 in 3D, 1 in 2D   3D: (Gbar_21 - Gbar_12, Gbar_02 - Gbar_20, Gbar_10 - Gbar_01); 2D: Gbar_10 - Gbar_01
+ *     NSX_FIELD_Q           1                  (|W|_F^2 - |S|_F^2) / 2, evaluated as the algebraically equal -(sum_ij Gbar_ij Gbar_ji) / 2
+ *                                              (no difference of two large norms in a shear layer)
+ *     NSX_FIELD_STRAIN      1                  sqrt(2 S : S)
+ *     NSX_FIELD_DIVERGENCE  1                  tr Gbar
+ * Layout of values: values[n_nodes][n_components], node = P2 node in the CALLER's numbering (node i carries the velocity DoFs dim i ...
+ * dim i + dim - 1 of the velocity block); n_nodes = n_u / dim on one handle.  Distributed handles are indexed globally (n_u_glob / dim nodes)
+ * and fill only the entries this rank owns, like nsx_get_solution; the other entries are not touched.
+ * nsx_compute_nodal_fields reads state only: no vector, matrix or solver state changes, a following solve computes bitwise what it would have
+ * computed without the call, and two calls give bitwise equal results.  The results do not depend on nsx_set_ranks / nsx_set_internal_layout:
+ * the fold order is the caller's cell order and the output is in the caller's numbering.  nsx_get_nodal_field returns the values of the LAST
+ * nsx_compute_nodal_fields; it does not recompute after a later solve (like nsx_get_cell_diagnostic).  A state value that is not finite
+ * propagates to the nodes whose patch holds it; the call still returns NSX_OK, as nsx_eval_probes does.
+ * Patch table: the node -> (cell, local node) lists are built by the first nsx_compute_nodal_fields on a mesh, from the connectivity as handed
+ * over (host/nodal_patch.hpp: a counting sort over the cells in their order), so the mesh set-up itself costs what it did.  The table survives
+ * nsx_set_ranks and nsx_set_internal_layout; a new nsx_set_mesh(_distributed) drops the table and the results.
+ * Distributed handles: every owned node has its complete patch among the handle's layer-1 cells (that is how nsx_set_mesh_distributed defines
+ * them) and the ghost values are in the ghosted `solution`, so no collective and no ghost exchange is issued (nsx_comm_counters does not
+ * move) and the ranks need not call together.  The values of a node equal BITWISE those of the single-process handle on the same mesh and
+ * numbering, provided the rank's cell list keeps the cells that hold owned nodes in ascending global order (nsxh_rank_view_* does: layer-1
+ * cells ascending, then layer-2 cells ascending, and no layer-2 cell holds an owned node).
+ * Errors: NSX_ERR_ARG for a compute call before tables or mesh are set, a get / components call before any compute on the current mesh, a
+ * `which` outside [0, NSX_FIELD_COUNT), null values, null n_components and a null handle; NSX_ERR_UNSUPPORTED for a (dim, n_p2) other than
+ * (2, 6) / (3, 10).  A refused call leaves the results of an earlier compute readable. */
+enum { NSX_FIELD_GRADIENT = 0, NSX_FIELD_VORTICITY = 1, NSX_FIELD_Q = 2, NSX_FIELD_STRAIN = 3, NSX_FIELD_DIVERGENCE = 4, NSX_FIELD_COUNT = 5 };
+/* Gbar and the derived fields of the state the handle holds, at every owned P2 node, in one kernel launch (csrc/nsx_nodal.hip). */
+int nsx_compute_nodal_fields(nsx_handle *h);
+/* *n_components = components per node of field `which` (the table above). */
+int nsx_nodal_field_components(nsx_handle *h, int which, int *n_components);
+/* values[n_nodes][n_components] of field `which` as the last nsx_compute_nodal_fields left it. */
+int nsx_get_nodal_field(nsx_handle *h, int which, double *values /*[n_nodes][n_components]*/);
+
 /* ---- measurement ---- */
 /* Per-kernel HIP-event timing of the hot path (bench.py roofline): enable, run, then read name/count/total-ms. */
 int nsx_profile_enable(nsx_handle *h, int on);

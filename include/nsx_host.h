@@ -164,6 +164,13 @@ int nsxh_tables_n_qf(const nsxh_tables *);
  * directory is created if missing).  solution = ghosted solution in the global dof numbering.  0 on success. */
 int nsxh_write_vtu(const nsxh_dofs *, const double *solution, const char *directory, const char *basename, unsigned counter);
 
+/* The files of nsxh_write_vtu with two more PointData arrays behind "partitioning": "vorticity" (n_vorticity components: 3 in 3D, 1 in 2D)
+ * and "q_criterion".  vorticity[n_nodes][n_vorticity] and q_criterion[n_nodes] are indexed by P2 node in the global numbering (what
+ * nsx_get_nodal_field hands out for NSX_FIELD_VORTICITY / NSX_FIELD_Q); the files hold their values at the cell vertices.  No counterpart in
+ * the reference.  0 on success. */
+int nsxh_write_vtu_fields(const nsxh_dofs *, const double *solution, const double *vorticity, int n_vorticity, const double *q_criterion,
+                          const char *directory, const char *basename, unsigned counter);
+
 /* NavierStokes::compute_pressure_difference (reference NavierStokes3D.cpp:849-923): P1 pressure at two points
  * (VectorTools::point_value): p(a) - p(b).  A point outside the mesh contributes 0 like a rank that does not hold it.
  * Returns the number of points found (0..2). */

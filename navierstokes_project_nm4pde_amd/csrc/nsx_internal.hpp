@@ -12,6 +12,8 @@
 //   cell tables    SoA: cell_n2[a][cell], cell_n1[v][cell], geo[k][cell] (J^-1 row-major, then |det J|)
 //                  cell_x0[d][cell] (vertex 0: x = X0 + J lambda, the point probes' search)
 //                  cell_nbr[k][cell] (cell across the face opposite local vertex k, -1: boundary; the tracers' walk, built on demand)
+//   patch table    per owned P2 node the (cell, local node) pairs that hold it, ascending cell, in tiles of 64 nodes of (nearly) one
+//                  patch size (the nodal fields' gather, built on demand: host/nodal_patch.hpp)
 //   gather maps    per CSR entry the list of (local entry, cell) contributions -> deterministic assembly, no atomics
 #pragma once
 #include <hip/hip_runtime.h>
@@ -405,6 +407,14 @@ struct nsx_handle {
   nsx::DevBuf<double> tracer_x;       // SoA [dim][tracer_n] positions
   nsx::DevBuf<double> tracer_age;     // [tracer_n]
   nsx::DevBuf<int32_t> tracer_cell, tracer_status, tracer_face;  // [tracer_n] each
+  // ---- nodal fields (nsx_nodal.hip)
+  bool have_patches = false;          // the node -> (cell, local node) patch table of the current mesh is on the device; built by the first nsx_compute_nodal_fields on a mesh
+  nsx::DevBuf<int32_t> nodal_tile_ptr, nodal_ent;  // host/nodal_patch.hpp: [nodal_tiles + 1] first step of every tile of 64 slots, [steps][64] cell << 4 | local node (-1: padding)
+  std::vector<int32_t> nodal_slot_of; // [N2] caller-local owned node -> slot; outlives a new layout / rank table, not a new mesh
+  int nodal_tiles = 0;
+  int64_t nodal_entries = 0;          // entries of nodal_ent, padding included
+  nsx::DevBuf<double> nodal_out;      // SoA [dim^2 + (3 | 1) + 3][64 nodal_tiles] in slot order: Gbar, vorticity, Q, strain rate, divergence of the last nsx_compute_nodal_fields
+  bool nodal_valid = false;           // nodal_out holds the values of a finished call on the current mesh
   // ---- profiling
   bool prof_on = false;
   std::map<std::string, nsx::ProfEntry> prof;
@@ -499,6 +509,9 @@ __device__ __forceinline__ void load_cell_map(int n_cells, int cell, const doubl
 
 // tracer particles (nsx_tracer.hip)
 void tracer_clear(nsx_handle *h);  // a new mesh drops the tracer set and the face-neighbour table
+
+// nodal fields (nsx_nodal.hip)
+void nodal_clear(nsx_handle *h);  // a new mesh drops the patch table and the results
 
 // sparse (nsx_sparse.hip)
 bool blocked_usable(const nsx_handle *h);                                                   // F->vmult goes through the LDS-staged SpMV

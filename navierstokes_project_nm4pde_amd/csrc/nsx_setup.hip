@@ -979,6 +979,7 @@ int nsx_set_mesh(nsx_handle *h, int n_cells, int dpc, const int32_t *cell_dofs, 
   h->cell_coords_in.assign(cell_coords, cell_coords + (size_t)n_cells * nv * dim);
   probe_clear(h);
   tracer_clear(h);
+  nodal_clear(h);
   h->n_cells1 = n_cells;
   h->haloU.send_idx_in.clear();
   h->haloP.send_idx_in.clear();
@@ -1054,6 +1055,7 @@ int nsx_set_mesh_distributed(nsx_handle *h, int n_cells, int n_cells1, int dpc, 
   h->cell_coords_in.assign(cell_coords, cell_coords + (size_t)n_cells * nv * dim);
   probe_clear(h);
   tracer_clear(h);
+  nodal_clear(h);
   h->n_cells1 = n_cells1;
   default_ranks(h);
   install_mesh(h);

@@ -42,6 +42,8 @@ def _lib():
         "nsxh_n_colours": (C.c_int, [vp]),
         "nsxh_n_colours_p": (C.c_int, [vp]),
         "nsxh_write_vtu": (C.c_int, [vp, C.POINTER(C.c_double), C.c_char_p, C.c_char_p, C.c_uint]),
+        "nsxh_write_vtu_fields": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double), C.c_char_p, C.c_char_p,
+                                            C.c_uint]),
         "nsxh_pressure_difference": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         "nsxh_dofs_free": (None, [vp]),
         "nsxh_dofs_per_cell": (C.c_int, [vp]),
@@ -196,6 +198,19 @@ class DoFs:
         assert x.shape == (self.n_dofs,)
         if self._lib.nsxh_write_vtu(self._h, x.ctypes.data_as(C.POINTER(C.c_double)), str(directory).encode(), basename.encode(), int(counter)):
             raise OSError("nsxh_write_vtu failed for %s" % directory)
+
+    def write_vtu_fields(self, solution, vorticity, q_criterion, directory, basename, counter):
+        """write_vtu's files plus the PointData arrays "vorticity" and "q_criterion", taken at the cell vertices from the node-indexed arrays
+        vorticity [n_nodes][3 | 1] and q_criterion [n_nodes] (Nsx.nodal_field(FIELD_VORTICITY / FIELD_Q)): nsxh_write_vtu_fields."""
+        dp = C.POINTER(C.c_double)
+        x = np.ascontiguousarray(solution, dtype=np.float64)
+        n_nodes = self.n_u // self.dim
+        w = np.ascontiguousarray(vorticity, dtype=np.float64).reshape(n_nodes, -1)
+        q = np.ascontiguousarray(q_criterion, dtype=np.float64).reshape(-1)
+        assert x.shape == (self.n_dofs,) and w.shape[1] == (3 if self.dim == 3 else 1) and q.shape == (n_nodes,)
+        if self._lib.nsxh_write_vtu_fields(self._h, x.ctypes.data_as(dp), w.ctypes.data_as(dp), w.shape[1], q.ctypes.data_as(dp), str(directory).encode(),
+                                           basename.encode(), int(counter)):
+            raise OSError("nsxh_write_vtu_fields failed for %s" % directory)
 
     def pressure_difference(self, solution, point_a, point_b):
         """NavierStokes::compute_pressure_difference (reference NavierStokes3D.cpp:849-923): (p(a) - p(b), points found)."""

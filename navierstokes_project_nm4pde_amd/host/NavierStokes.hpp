@@ -203,7 +203,17 @@ public:
       out() << "===============================================" << std::endl;
       const std::string output_file_name = dim == 3 ? "output-navier-stokes-3D" : "output-navier-stokes-2D";
       const std::vector<double> x = get_solution();
-      if (nsxh_write_vtu(dofs, x.data(), dim == 3 ? "./outputConvergence/" : "./output2D_1/", output_file_name.c_str(), time_step))
+      const char *directory = dim == 3 ? "./outputConvergence/" : "./output2D_1/";
+      if (fields_vtu) {  // opt-in (NSX_FIELDS=1): the same files with the nodal vorticity and Q-criterion of this state, computed on the device
+        int n_vorticity = 0;
+        ck(nsx_compute_nodal_fields(h));
+        ck(nsx_nodal_field_components(h, NSX_FIELD_VORTICITY, &n_vorticity));
+        std::vector<double> vorticity((size_t)(n_u / dim) * n_vorticity), q((size_t)(n_u / dim));
+        ck(nsx_get_nodal_field(h, NSX_FIELD_VORTICITY, vorticity.data()));
+        ck(nsx_get_nodal_field(h, NSX_FIELD_Q, q.data()));
+        if (nsxh_write_vtu_fields(dofs, x.data(), vorticity.data(), n_vorticity, q.data(), directory, output_file_name.c_str(), time_step))
+          throw std::runtime_error("cannot write " + output_file_name);
+      } else if (nsxh_write_vtu(dofs, x.data(), directory, output_file_name.c_str(), time_step))
         throw std::runtime_error("cannot write " + output_file_name);
       out() << "Output written to " << output_file_name << std::endl;
     }
@@ -384,6 +394,7 @@ protected:
   double current_time = 0.0;
   const bool diagnostics_csv = std::getenv("NSX_DIAGNOSTICS") && std::string(std::getenv("NSX_DIAGNOSTICS")) == "1";
   const bool probes_csv = std::getenv("NSX_PROBES") && std::string(std::getenv("NSX_PROBES")) == "1";
+  const bool fields_vtu = std::getenv("NSX_FIELDS") && std::string(std::getenv("NSX_FIELDS")) == "1";
   const int n_tracers = std::getenv("NSX_TRACERS") ? std::max(0, std::min(1048576, std::atoi(std::getenv("NSX_TRACERS")))) : 0;
 };
 

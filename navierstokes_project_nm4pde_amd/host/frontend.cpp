@@ -1286,6 +1286,75 @@ int nsxh_write_vtu(const nsxh_dofs *d, const double *solution, const char *direc
   return pv ? 0 : -1;
 }
 
+// nsxh_write_vtu's files with two more PointData arrays behind "partitioning": "vorticity" and "q_criterion", taken at the cell vertices from
+// arrays indexed by P2 node (the node of a vertex is its first velocity dof / dim).  Everything in front of them is written as nsxh_write_vtu
+// writes it.
+int nsxh_write_vtu_fields(const nsxh_dofs *d, const double *solution, const double *vorticity, int n_vorticity, const double *q_criterion,
+                          const char *directory, const char *basename, unsigned counter) {
+  if (!d || !solution || !vorticity || !q_criterion || !directory || !basename || (n_vorticity != 1 && n_vorticity != 3)) return -1;
+  const int dim = d->dim, nv = dim + 1, nc = d->n_cells;
+  std::string dir(directory);
+  if (!dir.empty() && dir.back() != '/') dir += '/';
+  for (size_t pos = 1; pos < dir.size(); ++pos)  // mkdir -p
+    if (dir[pos] == '/') ::mkdir(dir.substr(0, pos).c_str(), 0777);
+  const std::string stem = std::string(basename) + "_" + std::to_string(counter);
+  const std::string piece = stem + ".0.vtu";
+  std::ofstream f(dir + piece);
+  if (!f) return -1;
+  f << std::setprecision(17);
+  const int32_t *sub = d->mesh->subdomain.empty() ? nullptr : d->mesh->subdomain.data();
+  f << "<?xml version=\"1.0\"?>\n<VTKFile type=\"UnstructuredGrid\" version=\"0.1\" byte_order=\"LittleEndian\">\n<UnstructuredGrid>\n"
+    << "<Piece NumberOfPoints=\"" << (int64_t)nc * nv << "\" NumberOfCells=\"" << nc << "\">\n";
+  f << "<Points>\n<DataArray type=\"Float64\" NumberOfComponents=\"3\" format=\"ascii\">\n";
+  for (int c = 0; c < nc; ++c)
+    for (int v = 0; v < nv; ++v) {
+      const double *x = d->cell_coords.data() + ((size_t)c * nv + v) * dim;
+      f << x[0] << ' ' << x[1] << ' ' << (dim == 3 ? x[2] : 0.0) << '\n';
+    }
+  f << "</DataArray>\n</Points>\n<Cells>\n<DataArray type=\"Int32\" Name=\"connectivity\" format=\"ascii\">\n";
+  for (int64_t k = 0; k < (int64_t)nc * nv; ++k) f << k << ((k + 1) % nv ? ' ' : '\n');
+  f << "</DataArray>\n<DataArray type=\"Int32\" Name=\"offsets\" format=\"ascii\">\n";
+  for (int c = 1; c <= nc; ++c) f << (int64_t)c * nv << (c % 16 ? ' ' : '\n');
+  f << "\n</DataArray>\n<DataArray type=\"UInt8\" Name=\"types\" format=\"ascii\">\n";
+  for (int c = 1; c <= nc; ++c) f << (dim == 3 ? 10 : 5) << (c % 32 ? ' ' : '\n');  // VTK_TETRA / VTK_TRIANGLE
+  f << "\n</DataArray>\n</Cells>\n<PointData Scalars=\"scalars\">\n";
+  f << "<DataArray type=\"Float64\" Name=\"velocity\" NumberOfComponents=\"3\" format=\"ascii\">\n";
+  for (int c = 0; c < nc; ++c)
+    for (int v = 0; v < nv; ++v) {
+      const int32_t *cd = d->cell_dofs.data() + (size_t)c * d->dpc + (size_t)(dim + 1) * v;
+      f << solution[cd[0]] << ' ' << solution[cd[1]] << ' ' << (dim == 3 ? solution[cd[2]] : 0.0) << '\n';
+    }
+  f << "</DataArray>\n<DataArray type=\"Float64\" Name=\"pressure\" format=\"ascii\">\n";
+  for (int c = 0; c < nc; ++c)
+    for (int v = 0; v < nv; ++v) f << solution[d->cell_dofs[(size_t)c * d->dpc + (size_t)(dim + 1) * v + dim]] << (v + 1 == nv ? '\n' : ' ');
+  f << "</DataArray>\n<DataArray type=\"Float64\" Name=\"partitioning\" format=\"ascii\">\n";
+  for (int c = 0; c < nc; ++c)
+    for (int v = 0; v < nv; ++v) f << (sub ? sub[c] : 0) << (v + 1 == nv ? '\n' : ' ');
+  f << "</DataArray>\n<DataArray type=\"Float64\" Name=\"vorticity\" NumberOfComponents=\"" << n_vorticity << "\" format=\"ascii\">\n";
+  for (int c = 0; c < nc; ++c)
+    for (int v = 0; v < nv; ++v) {
+      const size_t node = (size_t)(d->cell_dofs[(size_t)c * d->dpc + (size_t)(dim + 1) * v] / dim);
+      for (int k = 0; k < n_vorticity; ++k) f << vorticity[node * n_vorticity + k] << (k + 1 == n_vorticity ? '\n' : ' ');
+    }
+  f << "</DataArray>\n<DataArray type=\"Float64\" Name=\"q_criterion\" format=\"ascii\">\n";
+  for (int c = 0; c < nc; ++c)
+    for (int v = 0; v < nv; ++v) f << q_criterion[d->cell_dofs[(size_t)c * d->dpc + (size_t)(dim + 1) * v] / dim] << (v + 1 == nv ? '\n' : ' ');
+  f << "</DataArray>\n</PointData>\n</Piece>\n</UnstructuredGrid>\n</VTKFile>\n";
+  f.close();
+  std::ofstream pv(dir + stem + ".pvtu");
+  if (!pv) return -1;
+  pv << "<?xml version=\"1.0\"?>\n<VTKFile type=\"PUnstructuredGrid\" version=\"0.1\" byte_order=\"LittleEndian\">\n"
+     << "<PUnstructuredGrid GhostLevel=\"0\">\n<PPointData Scalars=\"scalars\">\n"
+     << "<PDataArray type=\"Float64\" Name=\"velocity\" NumberOfComponents=\"3\" format=\"ascii\"/>\n"
+     << "<PDataArray type=\"Float64\" Name=\"pressure\" format=\"ascii\"/>\n"
+     << "<PDataArray type=\"Float64\" Name=\"partitioning\" format=\"ascii\"/>\n"
+     << "<PDataArray type=\"Float64\" Name=\"vorticity\" NumberOfComponents=\"" << n_vorticity << "\" format=\"ascii\"/>\n"
+     << "<PDataArray type=\"Float64\" Name=\"q_criterion\" format=\"ascii\"/>\n</PPointData>\n"
+     << "<PPoints>\n<PDataArray type=\"Float64\" NumberOfComponents=\"3\"/>\n</PPoints>\n"
+     << "<Piece Source=\"" << piece << "\"/>\n</PUnstructuredGrid>\n</VTKFile>\n";
+  return pv ? 0 : -1;
+}
+
 int nsxh_pressure_difference(const nsxh_dofs *d, const double *solution, const double *pa, const double *pb, double *diff) {
   if (!d || !solution || !pa || !pb || !diff) return -1;
   const int dim = d->dim, nv = dim + 1;

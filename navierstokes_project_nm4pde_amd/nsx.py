@@ -27,7 +27,7 @@ API = [
     "nsx_set_internal_layout", "nsx_layout_info", "nsx_layout_get", "nsx_gram_schmidt_cycle", "nsx_set_inner_precision",
     "nsx_gram_schmidt_sweeps", "nsx_compute_diagnostics", "nsx_get_cell_diagnostic", "nsx_schur_cg",
     "nsx_set_probes", "nsx_get_probe_cells", "nsx_eval_probes", "nsx_set_tracers", "nsx_advect_tracers", "nsx_get_tracers",
-    "nsx_sparse_product",
+    "nsx_sparse_product", "nsx_compute_nodal_fields", "nsx_nodal_field_components", "nsx_get_nodal_field",
 ]
 # declared in include/nsx.h as well, but with a capital letter in its name, which the header scan of tests/test_abi.py (lower case only)
 # does not see: kept beside the list that scan is compared with; build() checks both
@@ -41,6 +41,8 @@ PROD_F, PROD_F_INNER, PROD_F_RESID, PROD_MASS, PROD_B, PROD_B_MINUS_R, PROD_R_MI
 TRACER_EULER, TRACER_RK2, TRACER_RK4 = 1, 2, 4                                   # NSX_TRACER_*: scheme
 TRACER_FROZEN, TRACER_LINEAR = 0, 1                                              # field
 TRACER_NOT_FOUND, TRACER_ACTIVE, TRACER_EXITED, TRACER_LOST = 0, 1, 2, 3         # status
+# fields of nsx_get_nodal_field (NSX_FIELD_*)
+FIELD_GRADIENT, FIELD_VORTICITY, FIELD_Q, FIELD_STRAIN, FIELD_DIVERGENCE, FIELD_COUNT = range(6)
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, _f64p, C.c_int)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(_f64p), C.POINTER(C.c_int),
@@ -135,6 +137,9 @@ def lib():
     L.nsx_set_tracers.argtypes = [vp, C.c_int, _f64p, C.c_double]
     L.nsx_advect_tracers.argtypes = [vp, C.c_double, C.c_int, C.c_int, C.c_int]
     L.nsx_get_tracers.argtypes = [vp, _f64p, _i32p, _i32p, _i32p, _f64p]
+    L.nsx_compute_nodal_fields.argtypes = [vp]
+    L.nsx_nodal_field_components.argtypes = [vp, C.c_int, C.POINTER(C.c_int)]
+    L.nsx_get_nodal_field.argtypes = [vp, C.c_int, _f64p]
     L.nsx_set_inner_precision.argtypes = [vp, C.c_int]
     L.nsx_inner_F_vmult.argtypes = [vp, _f64p, _f64p]
     L.nsx_schur_cg.argtypes = [vp, C.c_double, C.c_int, _f64p, _f64p, C.POINTER(C.c_int), _f64p, C.POINTER(C.c_int)]
@@ -577,6 +582,21 @@ class Nsx:
         out = {"positions": np.empty((n, self.dim)), "cells": np.empty(n, np.int32), "status": np.empty(n, np.int32),
                "exit_faces": np.empty(n, np.int32), "age": np.empty(n)}
         self._ck(self.L.nsx_get_tracers(self._h, _d(out["positions"]), _i(out["cells"]), _i(out["status"]), _i(out["exit_faces"]), _d(out["age"])))
+        return out
+
+    # -- nodal fields --------------------------------------------------------------------------
+    def compute_nodal_fields(self):
+        """nsx_compute_nodal_fields: the recovered gradient and the fields derived from it at every owned P2 node, from the state the
+        handle holds; nodal_field() hands them out"""
+        self._ck(self.L.nsx_compute_nodal_fields(self._h))
+
+    def nodal_field(self, which):
+        """[n_nodes][n_components] of field `which` (FIELD_*) as the last compute_nodal_fields() left it, nodes in the caller's numbering
+        (nsx_get_nodal_field).  Distributed handles: global-sized, the entries this rank owns filled, the rest 0."""
+        nc = C.c_int(0)
+        self._ck(self.L.nsx_nodal_field_components(self._h, int(which), C.byref(nc)))
+        out = np.zeros((self.n_u // self.dim, nc.value))
+        self._ck(self.L.nsx_get_nodal_field(self._h, int(which), _d(out)))
         return out
 
     # -- export --------------------------------------------------------------------------------
