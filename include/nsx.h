@@ -423,6 +423,83 @@ int nsx_nodal_field_components(nsx_handle *h, int which, int *n_components);
 /* values[n_nodes][n_components] of field `which` as the last nsx_compute_nodal_fields left it. */
 int nsx_get_nodal_field(nsx_handle *h, int which, double *values /*[n_nodes][n_components]*/);
 
+/* ---- isosurfaces and slices ---- */
+/* The isosurface { s = isovalue } of a nodal scalar s, extracted on the device by marching sub-simplices: what travels to the host is the
+ * surface, O(N^(2/3)) cells of the mesh, instead of one value per P2 node (nsx_get_nodal_field) that the host then has to contour.  No
+ * counterpart in the reference (its output() writes the whole volume as a VTU).
+ * Output: an unindexed soup of primitives -- triangles in 3D (3 vertices), segments in 2D (2 vertices): dim vertices of dim coordinates each.
+ * points[n][dim][dim] (primitive, vertex, coordinate), colour[n][dim] (the second scalar interpolated to every vertex), cells[n] (position of
+ * the primitive's cell in the caller's cell list).  Any pointer of nsx_get_isosurface may be NULL; a colour pointer needs an extract with one.
+ * Nodal scalar s at every P2 node of a cell, by source (nsx_iso_source; `which` and `component` are read where the table names them):
+ *     NSX_ISO_VELOCITY   component 0 .. dim-1: the velocity DoF of the node, an exact copy; component -1: sqrt(sum_i u_i^2), summed left to right
+ *     NSX_ISO_PRESSURE   the P1 value at a vertex; 0.5 (p_i + p_j) at the mid-edge node of line {i, j} -- exact for P1, so the extraction from
+ *                        the pressure is the exact level set of p_h
+ *     NSX_ISO_NODAL      component `component` of field `which` (NSX_FIELD_*) as the last nsx_compute_nodal_fields left it
+ *     NSX_ISO_PLANE      normal . x_node (left to right), x_node the vertex or 0.5 (X_i + X_j) for a mid-edge node: slices, with any other
+ *                        source as colour
+ * u and p are the ghosted `solution` (current after nsx_set_solution and after nsx_solve_time_step).
+ * Subdivision.  Every P2 cell is cut into linear sub-simplices on its own nodes (local line order {0,1},{1,2},{2,0}[,{0,3},{1,3},{2,3}]):
+ *     2D: the triangles (0,3,5) (3,1,4) (5,4,2) (3,4,5)
+ *     3D: the corner tetrahedra (0,4,6,7) (4,1,5,8) (6,5,2,9) (7,8,9,3) and the inner octahedron split along its diagonal 4-9 into
+ *         (4,9,5,6) (4,9,6,7) (4,9,7,8) (4,9,8,5)
+ * The diagonal is interior to the cell and every face is split into the canonical 4 triangles whatever the neighbour does: the surface is
+ * watertight across cells.  The surface is the level set of the piecewise LINEAR interpolant on the sub-simplices (second order, not the
+ * curved P2 level set).
+ * Classification and vertices.  A node is inside when s >= isovalue.  On an edge with a inside and b outside the vertex is
+ *     t = (s_a - iso) / (s_a - s_b),   x = x_a + t (x_b - x_a),   c = c_a + t (c_b - c_a)
+ * always from the inside end to the outside end, never by node number, without contraction into fused multiply-adds: two cells that share
+ * the edge compute BITWISE the same vertex, under every internal layout.  A sub-simplex with a nodal s that is not finite emits nothing (the
+ * call still returns NSX_OK).  Zero-area primitives (s == iso exactly at nodes) are emitted as they come.
+ * Cases, by the set of inside vertices of the sub-simplex (v0,v1,v2[,v3]); a-b is the crossing from inside vertex a to outside vertex b.
+ * Orientation: the normal (p1 - p0) x (p2 - p0) points from inside to outside; in 2D the inside lies to the left of p0 -> p1.  The table is
+ * the vertex order in a cell with det J > 0; a cell with det J < 0 swaps the last two vertices of every primitive.  A tetrahedron with two
+ * inside {i < j} and two outside {k < l} gives the quad i-k i-l j-l j-k, split along its first and third corner.
+ *     tetrahedron                                          triangle
+ *     {0}      (0-1 0-2 0-3)                               {0}    (0-1 0-2)
+ *     {1}      (1-0 1-3 1-2)                               {1}    (1-2 1-0)
+ *     {0,1}    (0-2 0-3 1-3)  (0-2 1-3 1-2)                {0,1}  (1-2 0-2)
+ *     {2}      (2-0 2-1 2-3)                               {2}    (2-0 2-1)
+ *     {0,2}    (0-1 2-3 0-3)  (0-1 2-1 2-3)                {0,2}  (0-1 2-1)
+ *     {1,2}    (1-0 1-3 2-3)  (1-0 2-3 2-0)                {1,2}  (2-0 1-0)
+ *     {0,1,2}  (0-3 1-3 2-3)
+ *     {3}      (3-0 3-2 3-1)
+ *     {0,3}    (0-1 0-2 3-2)  (0-1 3-2 3-1)
+ *     {1,3}    (1-0 3-2 1-2)  (1-0 3-0 3-2)
+ *     {0,1,3}  (0-2 3-2 1-2)
+ *     {2,3}    (2-0 2-1 3-1)  (2-0 3-1 3-0)
+ *     {0,2,3}  (0-1 2-1 3-1)
+ *     {1,2,3}  (1-0 3-0 2-0)
+ * (host/iso_tables.hpp holds the tables.)
+ * Order: ascending position in the caller's cell list, then the sub-simplex order above, then the table order.  The positions come from an
+ * exclusive prefix sum of the per-cell counts (count, scan, emit: csrc/nsx_iso.hip), not from an atomic cursor, so the result does not depend on
+ * the scheduling, nsx_set_ranks or nsx_set_internal_layout, and two calls agree bitwise.  nsx_extract_isosurface reads state only: no vector,
+ * matrix or solver state changes and a following solve computes bitwise what it would have computed without the call.  The result survives
+ * until the next extract or a new nsx_set_mesh(_distributed); nsx_get_isosurface does not recompute after a later solve.
+ * The vertex coordinates of the cells and the node maps the kernels need are uploaded by the first extract on a mesh (the mesh set-up itself costs
+ * what it did).  The workgroup width of the count / scan / emit kernels is read per call from NSX_ISO_WG (64 / 128 / 256, default 256), as
+ * NSX_SPMV_R is.
+ * Distributed handles: a rank extracts from the cells it counts for the flow diagnostics (nsx_compute_diagnostics: the owner of the cell's
+ * lowest global P2 node), so every cell has one extractor and the union over the ranks is the single-process surface, primitive by
+ * primitive bitwise.  No collective and no ghost exchange is issued (nsx_comm_counters does not move) and the ranks need not call together;
+ * *n_primitives is the rank's own count and cells index the rank's own cell list.  NSX_ISO_NODAL, as field or colour, returns
+ * NSX_ERR_UNSUPPORTED with more than one process (ghost nodes have no nodal results); a 1-rank communicator works.
+ * Errors: NSX_ERR_ARG for a null handle, field or n_primitives, a call before tables, mesh or state, an unknown kind, `which` or `component`,
+ * an isovalue that is not finite, a plane normal that is not finite or all zero, NSX_ISO_NODAL without valid nodal results on the current
+ * mesh, and a get before any extract on the current mesh; NSX_ERR_UNSUPPORTED for a (dim, n_p2) other than (2, 6) / (3, 10) and for more than
+ * 2^31 - 1 primitives.  A refused call leaves an earlier result readable. */
+enum { NSX_ISO_VELOCITY = 0, NSX_ISO_PRESSURE = 1, NSX_ISO_NODAL = 2, NSX_ISO_PLANE = 3 };
+typedef struct {
+  int kind;         /* NSX_ISO_* */
+  int which;        /* NSX_ISO_NODAL: the field, NSX_FIELD_* */
+  int component;    /* NSX_ISO_VELOCITY: 0 .. dim-1, or -1 for the magnitude; NSX_ISO_NODAL: component of the field */
+  double normal[3]; /* NSX_ISO_PLANE: s = normal . x (the first dim entries) */
+} nsx_iso_source;
+/* Extracts { field = isovalue } from the state the handle holds; *n_primitives = primitives this handle found. */
+int nsx_extract_isosurface(nsx_handle *h, const nsx_iso_source *field, double isovalue, const nsx_iso_source *colour /* NULL: none */,
+                           int64_t *n_primitives);
+/* The primitives of the last nsx_extract_isosurface. */
+int nsx_get_isosurface(nsx_handle *h, double *points /*[n][dim][dim]*/, double *colour /*[n][dim]*/, int32_t *cells /*[n]*/);
+
 /* ---- measurement ---- */
 /* Per-kernel HIP-event timing of the hot path (bench.py roofline): enable, run, then read name/count/total-ms. */
 int nsx_profile_enable(nsx_handle *h, int on);

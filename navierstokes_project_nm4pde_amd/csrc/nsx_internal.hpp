@@ -14,6 +14,8 @@
 //                  cell_nbr[k][cell] (cell across the face opposite local vertex k, -1: boundary; the tracers' walk, built on demand)
 //   patch table    per owned P2 node the (cell, local node) pairs that hold it, ascending cell, in tiles of 64 nodes of (nearly) one
 //                  patch size (the nodal fields' gather, built on demand: host/nodal_patch.hpp)
+//   iso tables     cell_x[(v dim + d)][cell] vertex coordinates, node maps in the internal numbering (P2 node -> P1 nodes, position, slot of
+//                  the nodal results), built on demand (the isosurface extraction: nsx_iso.hip)
 //   gather maps    per CSR entry the list of (local entry, cell) contributions -> deterministic assembly, no atomics
 #pragma once
 #include <hip/hip_runtime.h>
@@ -415,6 +417,23 @@ struct nsx_handle {
   int64_t nodal_entries = 0;          // entries of nodal_ent, padding included
   nsx::DevBuf<double> nodal_out;      // SoA [dim^2 + (3 | 1) + 3][64 nodal_tiles] in slot order: Gbar, vorticity, Q, strain rate, divergence of the last nsx_compute_nodal_fields
   bool nodal_valid = false;           // nodal_out holds the values of a finished call on the current mesh
+  // ---- isosurfaces and slices (nsx_iso.hip)
+  int layout_epoch = 0;               // counts the installations of a mesh / an internal layout: what is kept in the INTERNAL node numbering is rebuilt when it moves
+  bool iso_have_coords = false;       // iso_cellx / iso_flip hold the current mesh; uploaded by the first nsx_extract_isosurface on a mesh
+  nsx::DevBuf<double> iso_cellx;      // SoA [(dim+1) dim][n_cells]: the vertex coordinates of every cell
+  nsx::DevBuf<uint8_t> iso_flip;      // [n_cells] 1 = det J < 0: the primitives of the cell swap their last two vertices
+  int iso_map_epoch = -1, iso_slot_epoch = -1;  // the layout_epoch the node maps below were built in
+  nsx::DevBuf<int32_t> iso_pmap;      // [2][N2_loc] internal P2 node -> its P1 node (second entry -1), or the two P1 nodes of its line
+  nsx::DevBuf<double> iso_nodex;      // SoA [dim][N2_loc] position of every internal P2 node
+  nsx::DevBuf<int32_t> iso_slot;      // [N2_loc] internal P2 node -> slot of nodal_out (-1: a ghost)
+  nsx::DevBuf<double> iso_s;          // [2][N2_loc] nodal scalars of the last call: field plane, colour plane
+  nsx::DevBuf<int32_t> iso_pack;      // [n_cells] prefix inside the workgroup << 5 | primitives of the cell
+  nsx::DevBuf<int32_t> iso_wg_tot;    // [workgroups] primitives per workgroup of k_iso_count
+  nsx::DevBuf<long long> iso_wg_off;  // [workgroups + 1] their exclusive prefix sum; the last entry is the total
+  nsx::DevBuf<double> iso_pts, iso_col;  // SoA [dim dim][iso_cap], [dim][iso_cap]: the primitives of the last extract
+  nsx::DevBuf<int32_t> iso_cells;     // [iso_cap]
+  int64_t iso_cap = 0, iso_n = 0;     // capacity (never shrinks), primitives of the last extract
+  bool iso_valid = false, iso_has_colour = false;  // the buffers hold a finished extract on the current mesh; it had a colour source
   // ---- profiling
   bool prof_on = false;
   std::map<std::string, nsx::ProfEntry> prof;
@@ -512,6 +531,17 @@ void tracer_clear(nsx_handle *h);  // a new mesh drops the tracer set and the fa
 
 // nodal fields (nsx_nodal.hip)
 void nodal_clear(nsx_handle *h);  // a new mesh drops the patch table and the results
+// planes of nodal_out: the dim^2 entries of Gbar (row-major), then vorticity (3 / 1), Q, strain rate, divergence
+constexpr int nodal_planes(int dim) { return dim * dim + (dim == 3 ? 3 : 1) + 3; }
+inline int nodal_components(int dim, int which) { return which == NSX_FIELD_GRADIENT ? dim * dim : which == NSX_FIELD_VORTICITY ? (dim == 3 ? 3 : 1) : 1; }
+inline int nodal_first_plane(int dim, int which) {
+  int p = 0;
+  for (int f = 0; f < which; ++f) p += nodal_components(dim, f);
+  return p;
+}
+
+// isosurfaces and slices (nsx_iso.hip)
+void iso_clear(nsx_handle *h);  // a new mesh drops the coordinates, the node maps and the result
 
 // sparse (nsx_sparse.hip)
 bool blocked_usable(const nsx_handle *h);                                                   // F->vmult goes through the LDS-staged SpMV

@@ -29,15 +29,6 @@
 
 namespace nsx {
 
-// planes of nodal_out: the dim^2 entries of Gbar (row-major), then vorticity (3 / 1), Q, strain rate, divergence
-constexpr int nodal_planes(int dim) { return dim * dim + (dim == 3 ? 3 : 1) + 3; }
-static int nodal_components(int dim, int which) { return which == NSX_FIELD_GRADIENT ? dim * dim : which == NSX_FIELD_VORTICITY ? (dim == 3 ? 3 : 1) : 1; }
-static int nodal_first_plane(int dim, int which) {
-  int p = 0;
-  for (int f = 0; f < which; ++f) p += nodal_components(dim, f);
-  return p;
-}
-
 // tile_ptr [n_tiles + 1], ent [tile_ptr[n_tiles] * 64] (host/nodal_patch.hpp); out [nodal_planes(DIM)][n_slots], n_slots = 64 * gridDim.x.
 // A slot without a node, and a node in no cell, has an empty list: its planes are exact zeros.
 template <int DIM, int NP2>

@@ -856,6 +856,7 @@ void install_mesh(nsx_handle *h) {
   using namespace nsx;
   const int dim = h->dim, nv = dim + 1, np2 = h->np2, np1 = h->np1;
   const int n_cells = (int)(h->cell_n2_in.size() / np2);
+  h->layout_epoch++;
   h->cell_n2_h = h->cell_n2_in;
   h->cell_n1_h = h->cell_n1_in;
   h->layout_on = false;
@@ -980,6 +981,7 @@ int nsx_set_mesh(nsx_handle *h, int n_cells, int dpc, const int32_t *cell_dofs, 
   probe_clear(h);
   tracer_clear(h);
   nodal_clear(h);
+  iso_clear(h);
   h->n_cells1 = n_cells;
   h->haloU.send_idx_in.clear();
   h->haloP.send_idx_in.clear();
@@ -1056,6 +1058,7 @@ int nsx_set_mesh_distributed(nsx_handle *h, int n_cells, int n_cells1, int dpc, 
   probe_clear(h);
   tracer_clear(h);
   nodal_clear(h);
+  iso_clear(h);
   h->n_cells1 = n_cells1;
   default_ranks(h);
   install_mesh(h);

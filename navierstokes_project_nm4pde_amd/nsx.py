@@ -28,6 +28,7 @@ API = [
     "nsx_gram_schmidt_sweeps", "nsx_compute_diagnostics", "nsx_get_cell_diagnostic", "nsx_schur_cg",
     "nsx_set_probes", "nsx_get_probe_cells", "nsx_eval_probes", "nsx_set_tracers", "nsx_advect_tracers", "nsx_get_tracers",
     "nsx_sparse_product", "nsx_compute_nodal_fields", "nsx_nodal_field_components", "nsx_get_nodal_field",
+    "nsx_extract_isosurface", "nsx_get_isosurface",
 ]
 # declared in include/nsx.h as well, but with a capital letter in its name, which the header scan of tests/test_abi.py (lower case only)
 # does not see: kept beside the list that scan is compared with; build() checks both
@@ -43,6 +44,8 @@ TRACER_FROZEN, TRACER_LINEAR = 0, 1                                             
 TRACER_NOT_FOUND, TRACER_ACTIVE, TRACER_EXITED, TRACER_LOST = 0, 1, 2, 3         # status
 # fields of nsx_get_nodal_field (NSX_FIELD_*)
 FIELD_GRADIENT, FIELD_VORTICITY, FIELD_Q, FIELD_STRAIN, FIELD_DIVERGENCE, FIELD_COUNT = range(6)
+# source kinds of nsx_extract_isosurface (NSX_ISO_*)
+ISO_VELOCITY, ISO_PRESSURE, ISO_NODAL, ISO_PLANE = range(4)
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, _f64p, C.c_int)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(_f64p), C.POINTER(C.c_int),
@@ -70,6 +73,18 @@ class FlowDiag(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class IsoSource(C.Structure):
+    """nsx_iso_source"""
+    _fields_ = [("kind", C.c_int), ("which", C.c_int), ("component", C.c_int), ("normal", C.c_double * 3)]
+
+
+def iso_source(kind, which=0, component=0, normal=None):
+    """an nsx_iso_source: ISO_VELOCITY (component 0 .. dim-1, -1: magnitude), ISO_PRESSURE, ISO_NODAL (which = FIELD_*, component),
+    ISO_PLANE (normal)"""
+    n = list(normal) if normal is not None else []
+    return IsoSource(int(kind), int(which), int(component), (C.c_double * 3)(*(n + [0.0] * (3 - len(n)))))
 
 
 class NsxError(RuntimeError):
@@ -140,6 +155,8 @@ def lib():
     L.nsx_compute_nodal_fields.argtypes = [vp]
     L.nsx_nodal_field_components.argtypes = [vp, C.c_int, C.POINTER(C.c_int)]
     L.nsx_get_nodal_field.argtypes = [vp, C.c_int, _f64p]
+    L.nsx_extract_isosurface.argtypes = [vp, C.POINTER(IsoSource), C.c_double, C.POINTER(IsoSource), C.POINTER(C.c_int64)]
+    L.nsx_get_isosurface.argtypes = [vp, _f64p, _f64p, _i32p]
     L.nsx_set_inner_precision.argtypes = [vp, C.c_int]
     L.nsx_inner_F_vmult.argtypes = [vp, _f64p, _f64p]
     L.nsx_schur_cg.argtypes = [vp, C.c_double, C.c_int, _f64p, _f64p, C.POINTER(C.c_int), _f64p, C.POINTER(C.c_int)]
@@ -598,6 +615,18 @@ class Nsx:
         out = np.zeros((self.n_u // self.dim, nc.value))
         self._ck(self.L.nsx_get_nodal_field(self._h, int(which), _d(out)))
         return out
+
+    # -- isosurfaces and slices ----------------------------------------------------------------
+    def extract_isosurface(self, field, isovalue, colour=None):
+        """nsx_extract_isosurface + nsx_get_isosurface: the primitives of { field = isovalue } (segments in 2D, triangles in 3D) as
+        (points [n][dim][dim], colour [n][dim] or None, cells [n]); field / colour: iso_source(...).  Distributed handles: this rank's
+        primitives, cells in the rank's own cell list."""
+        n = C.c_int64(0)
+        self._ck(self.L.nsx_extract_isosurface(self._h, C.byref(field), float(isovalue), C.byref(colour) if colour is not None else None, C.byref(n)))
+        pts, cells = np.empty((n.value, self.dim, self.dim)), np.empty(n.value, np.int32)
+        col = np.empty((n.value, self.dim)) if colour is not None else None
+        self._ck(self.L.nsx_get_isosurface(self._h, _d(pts), _d(col) if col is not None else None, _i(cells)))
+        return pts, col, cells
 
     # -- export --------------------------------------------------------------------------------
     def export_block(self, which, block, graph=None):
