@@ -426,59 +426,52 @@ void run_dirichlet(nsx_handle *h, int n_in, const int32_t *dofs_in, const double
 
 extern "C" {
 
-#define NSX_API_BODY(h_, ...)                  \
-  if (!(h_)) return NSX_ERR_ARG;               \
-  try {                                        \
-    __VA_ARGS__;                               \
-  } catch (const nsx::Error &e) {              \
-    (h_)->err = e.msg;                         \
-    return e.code;                             \
-  } catch (const std::exception &e) {          \
-    (h_)->err = e.what();                      \
-    return NSX_ERR_ARG;                        \
-  }                                            \
-  return NSX_OK;
-
 int nsx_assemble(nsx_handle *h, int flags) {
   // the first assembly is the run's set-up step: the ILU schedules for the final rank tables are built here, not inside
   // the first timed preconditioner initialisation
-  NSX_API_BODY(h, {
-    if (h->have_mesh) nsx::ensure_schedules(h);
-    nsx::run_assemble(h, true, flags);
-  })
+  NSX_TRY(h)
+  if (h->have_mesh) nsx::ensure_schedules(h);
+  nsx::run_assemble(h, true, flags);
+  NSX_CATCH(h)
 }
-int nsx_assemble_time_step(nsx_handle *h, int flags) { NSX_API_BODY(h, nsx::run_assemble(h, false, flags)) }
+int nsx_assemble_time_step(nsx_handle *h, int flags) {
+  NSX_TRY(h)
+  nsx::run_assemble(h, false, flags);
+  NSX_CATCH(h)
+}
 int nsx_apply_boundary_values(nsx_handle *h, int n, const int32_t *dofs, const double *vals) {
-  NSX_API_BODY(h, nsx::run_dirichlet(h, n, dofs, vals))
+  NSX_TRY(h)
+  nsx::run_dirichlet(h, n, dofs, vals);
+  NSX_CATCH(h)
 }
 int nsx_add_rhs(nsx_handle *h, int n, const int32_t *dofs, const double *vals) {
-  NSX_API_BODY(h, {
-    if (!h->assembled) NSX_THROW(NSX_ERR_ARG, "assemble first");
-    if (n < 0 || (n && (!dofs || !vals))) NSX_THROW(NSX_ERR_ARG, "bad arrays");
-    HIP_CHECK(hipSetDevice(h->prm.device));
-    std::vector<int32_t> ld;  // global dofs -> local owned positions
-    std::vector<double> lv;
-    for (int k = 0; k < n; ++k) {
-      const int32_t g = dofs[k];
-      if (g < h->n_u_glob) {
-        if (g >= h->dim * h->goff_u && g < h->dim * h->goff_u + h->n_u) {
-          const int32_t l = g - h->dim * h->goff_u;
-          ld.push_back(h->dim * nsx::node_to_internal(h, l / h->dim) + l % h->dim);
-          lv.push_back(vals[k]);
-        }
-      } else if (g - h->n_u_glob >= h->goff_p && g - h->n_u_glob < h->goff_p + h->n_p) {
-        ld.push_back(h->off_p + nsx::pnode_to_internal(h, g - h->n_u_glob - h->goff_p));
+  NSX_TRY(h)
+  if (!h->assembled) NSX_THROW(NSX_ERR_ARG, "assemble first");
+  if (n < 0 || (n && (!dofs || !vals))) NSX_THROW(NSX_ERR_ARG, "bad arrays");
+  HIP_CHECK(hipSetDevice(h->prm.device));
+  std::vector<int32_t> ld;  // global dofs -> local owned positions
+  std::vector<double> lv;
+  for (int k = 0; k < n; ++k) {
+    const int32_t g = dofs[k];
+    if (g < h->n_u_glob) {
+      if (g >= h->dim * h->goff_u && g < h->dim * h->goff_u + h->n_u) {
+        const int32_t l = g - h->dim * h->goff_u;
+        ld.push_back(h->dim * nsx::node_to_internal(h, l / h->dim) + l % h->dim);
         lv.push_back(vals[k]);
       }
+    } else if (g - h->n_u_glob >= h->goff_p && g - h->n_u_glob < h->goff_p + h->n_p) {
+      ld.push_back(h->off_p + nsx::pnode_to_internal(h, g - h->n_u_glob - h->goff_p));
+      lv.push_back(vals[k]);
     }
-    const int m = (int)ld.size();
-    nsx::DevBuf<int32_t> d;
-    nsx::DevBuf<double> v;
-    d.upload(ld.data(), m, h->stream);
-    v.upload(lv.data(), m, h->stream);
-    if (m) hipLaunchKernelGGL(nsx::k_add_rhs, dim3(nsx::cdiv(m, 256)), dim3(256), 0, h->stream, m, d.p, v.p, h->rhs.p);
-    HIP_CHECK(hipStreamSynchronize(h->stream));
-  })
+  }
+  const int m = (int)ld.size();
+  nsx::DevBuf<int32_t> d;
+  nsx::DevBuf<double> v;
+  d.upload(ld.data(), m, h->stream);
+  v.upload(lv.data(), m, h->stream);
+  if (m) hipLaunchKernelGGL(nsx::k_add_rhs, dim3(nsx::cdiv(m, 256)), dim3(256), 0, h->stream, m, d.p, v.p, h->rhs.p);
+  HIP_CHECK(hipStreamSynchronize(h->stream));
+  NSX_CATCH(h)
 }
 
 }  // extern "C"

@@ -400,17 +400,13 @@ int cg_dirty_words(nsx_handle *h);
 
 extern "C" int nsx_persistent_state(nsx_handle *h, int state[4]) {
   if (!h || !state) return NSX_ERR_ARG;
-  try {
-    HIP_CHECK(hipSetDevice(h->prm.device));
-    state[0] = h->mgs.box.p != nullptr && !h->mgs.disabled && h->mgs.max_wg > 0;
-    state[1] = h->cg_box.p != nullptr && !h->cg_disabled && h->cg_max_wg > 0;
-    state[2] = h->n_persistent_fallbacks;
-    state[3] = nsx::mgs_dirty_words(h) + nsx::cg_dirty_words(h);
-  } catch (const nsx::Error &e) {
-    h->err = e.msg;
-    return e.code;
-  }
-  return NSX_OK;
+  NSX_TRY(h)
+  HIP_CHECK(hipSetDevice(h->prm.device));
+  state[0] = h->mgs.box.p != nullptr && !h->mgs.disabled && h->mgs.max_wg > 0;
+  state[1] = h->cg_box.p != nullptr && !h->cg_disabled && h->cg_max_wg > 0;
+  state[2] = h->n_persistent_fallbacks;
+  state[3] = nsx::mgs_dirty_words(h) + nsx::cg_dirty_words(h);
+  NSX_CATCH(h)
 }
 
 // Which code paths this handle's products and solves take (tests, bench.py's rehearsal log): see include/nsx.h
@@ -418,57 +414,53 @@ extern "C" int nsx_path_info(nsx_handle *h, int info[32]) {
   if (!h || !info) return NSX_ERR_ARG;
   for (int k = 0; k < 32; ++k) info[k] = 0;
   if (!h->have_mesh) return NSX_OK;
-  try {
-    HIP_CHECK(hipSetDevice(h->prm.device));
-    const nsx::SpmvBlocked &b = h->blkA;
-    info[0] = nsx::blocked_usable(h) ? 1 : 0;
-    info[1] = b.n_chunks;
-    info[2] = b.n_chunks_if;
-    info[3] = h->mgs.last_e;
-    info[4] = h->mgs.last_nwg;
-    info[5] = h->mgs.last_dist;
-    info[6] = h->mgs.max_e_seen;
-    info[7] = h->cu_reserved;
-    info[8] = h->cg_last_path;
-    info[9] = h->schedS.n_blocks;
-    info[10] = (int)h->haloU.nbr.size();
-    info[11] = h->haloU.nbr.empty() ? 0 : h->haloU.send_ptr[h->haloU.nbr.size()];
-    info[12] = h->N2_loc - h->N2;
-    info[13] = h->schedS.dense ? 1 : 0;
-    info[14] = h->mgs.disabled ? 1 : 0;
-    info[15] = h->n_persistent_fallbacks;
-    // what the distributed sweep WOULD run with an RCCL communicator (a rehearsal over host callbacks runs the two-pass sweep): the
-    // instantiation for the velocity and the block vector on plain streams (only the 8-entry grid leaves RCCL's kernel room) and on
-    // masked ones; 0 = the resident grid does not hold the vector
-    if (!h->mgs.disabled) {
-      nsx::mgs_setup(h);
-      const int es[3] = {8, 10, 12};
-      auto fit = [&](int n, const int *caps, int n_inst) {
-        const nsx::MgsPick p = nsx::mgs_pick(n, caps, n_inst, es);
-        return p.fits() ? p.e : 0;
-      };
-      info[16] = fit(h->n_u, h->mgs.max_wg_dist, 1);
-      info[17] = fit(h->n_u, h->mgs.dist_cap_reserved, 3);
-      info[18] = fit(h->n_u + h->n_p, h->mgs.max_wg_dist, 1);
-      info[19] = fit(h->n_u + h->n_p, h->mgs.dist_cap_reserved, 3);
-      info[21] = fit(h->n_u, h->mgs.max_wg_e, 3);  // one GPU, no communicator
-    }
-    info[20] = nsx::cdiv(std::max(1, h->schedS.n_blocks), 1024);  // Schur blocks per entry of a partial-sum array of the two-launch CG (1: no fold launch)
-    info[22] = h->N2;
-    info[23] = h->NP;
-    info[24] = h->mgs.last_fused;
-    info[25] = h->mgs.fused_launches;
-    info[26] = h->inner_F_fp32_used;
-    info[27] = h->ilu_F_fp32_used;
-    info[28] = h->cg_last_rpg;
-    info[29] = h->cg_last_lres;
-    info[30] = b.max_rows;
-    info[31] = b.max_ucols;
-  } catch (const nsx::Error &e) {
-    h->err = e.msg;
-    return e.code;
+  NSX_TRY(h)
+  HIP_CHECK(hipSetDevice(h->prm.device));
+  const nsx::SpmvBlocked &b = h->blkA;
+  info[0] = nsx::blocked_usable(h) ? 1 : 0;
+  info[1] = b.n_chunks;
+  info[2] = b.n_chunks_if;
+  info[3] = h->mgs.last_e;
+  info[4] = h->mgs.last_nwg;
+  info[5] = h->mgs.last_dist;
+  info[6] = h->mgs.max_e_seen;
+  info[7] = h->cu_reserved;
+  info[8] = h->cg_last_path;
+  info[9] = h->schedS.n_blocks;
+  info[10] = (int)h->haloU.nbr.size();
+  info[11] = h->haloU.nbr.empty() ? 0 : h->haloU.send_ptr[h->haloU.nbr.size()];
+  info[12] = h->N2_loc - h->N2;
+  info[13] = h->schedS.dense ? 1 : 0;
+  info[14] = h->mgs.disabled ? 1 : 0;
+  info[15] = h->n_persistent_fallbacks;
+  // what the distributed sweep WOULD run with an RCCL communicator (a rehearsal over host callbacks runs the two-pass sweep): the
+  // instantiation for the velocity and the block vector on plain streams (only the 8-entry grid leaves RCCL's kernel room) and on
+  // masked ones; 0 = the resident grid does not hold the vector
+  if (!h->mgs.disabled) {
+    nsx::mgs_setup(h);
+    const int es[3] = {8, 10, 12};
+    auto fit = [&](int n, const int *caps, int n_inst) {
+      const nsx::MgsPick p = nsx::mgs_pick(n, caps, n_inst, es);
+      return p.fits() ? p.e : 0;
+    };
+    info[16] = fit(h->n_u, h->mgs.max_wg_dist, 1);
+    info[17] = fit(h->n_u, h->mgs.dist_cap_reserved, 3);
+    info[18] = fit(h->n_u + h->n_p, h->mgs.max_wg_dist, 1);
+    info[19] = fit(h->n_u + h->n_p, h->mgs.dist_cap_reserved, 3);
+    info[21] = fit(h->n_u, h->mgs.max_wg_e, 3);  // one GPU, no communicator
   }
-  return NSX_OK;
+  info[20] = nsx::cdiv(std::max(1, h->schedS.n_blocks), 1024);  // Schur blocks per entry of a partial-sum array of the two-launch CG (1: no fold launch)
+  info[22] = h->N2;
+  info[23] = h->NP;
+  info[24] = h->mgs.last_fused;
+  info[25] = h->mgs.fused_launches;
+  info[26] = h->inner_F_fp32_used;
+  info[27] = h->ilu_F_fp32_used;
+  info[28] = h->cg_last_rpg;
+  info[29] = h->cg_last_lres;
+  info[30] = b.max_rows;
+  info[31] = b.max_ucols;
+  NSX_CATCH(h)
 }
 
 // Which ILU(0) kernels ran on the schedule of F (0) / of the Schur matrix (1): see include/nsx.h

@@ -443,25 +443,21 @@ int nsx_comm_unique_id(uint8_t id[128]) {
 
 int nsx_comm_init(nsx_handle *h, int rank, int world, const uint8_t id[128]) {
   if (!h || !id || world < 1 || rank < 0 || rank >= world) return NSX_ERR_ARG;
-  try {
-    HIP_CHECK(hipSetDevice(h->prm.device));
-    nsx::comm_destroy(h);
-    h->comm = new nsx::Comm;
-    h->comm->rank = rank;
-    h->comm->world = world;
-    ncclUniqueId u;
-    memcpy(&u, id, 128);
-    NCCL_CHECK(ncclCommInitRank(&h->comm->comm, world, u, rank));
-    h->self_p2p = getenv("NSX_EXT_SELF_P2P") ? atoi(getenv("NSX_EXT_SELF_P2P")) : 0;
-    nsx::comm_prepare_streams(h);
-    h->mgs.dist_state = -1;  // a new communicator: the paths the ranks choose together are chosen again
-    h->mgs.dist_fit.clear();
-    h->cgd_agreed = -1;
-  } catch (const nsx::Error &e) {
-    h->err = e.msg;
-    return e.code;
-  }
-  return NSX_OK;
+  NSX_TRY(h)
+  HIP_CHECK(hipSetDevice(h->prm.device));
+  nsx::comm_destroy(h);
+  h->comm = new nsx::Comm;
+  h->comm->rank = rank;
+  h->comm->world = world;
+  ncclUniqueId u;
+  memcpy(&u, id, 128);
+  NCCL_CHECK(ncclCommInitRank(&h->comm->comm, world, u, rank));
+  h->self_p2p = getenv("NSX_EXT_SELF_P2P") ? atoi(getenv("NSX_EXT_SELF_P2P")) : 0;
+  nsx::comm_prepare_streams(h);
+  h->mgs.dist_state = -1;  // a new communicator: the paths the ranks choose together are chosen again
+  h->mgs.dist_fit.clear();
+  h->cgd_agreed = -1;
+  NSX_CATCH(h)
 }
 
 // Test hook (tests/test_gpu_distributed.py): the RCCL branch of the ghost exchange -- pack kernel, grouped ncclSend / ncclRecv straight
@@ -470,38 +466,34 @@ int nsx_comm_init(nsx_handle *h, int rank, int world, const uint8_t id[128]) {
 // nodes with ncomp values each; ghost k must receive the values of owned node (7 k + 3) % n_own.  max_err = largest deviation.
 int nsx_comm_self_halo_test(nsx_handle *h, int n_own, int n_ghost, int ncomp, double *max_err) {
   if (!h || !max_err || n_own < 1 || n_ghost < 1 || ncomp < 1 || ncomp > 3) return NSX_ERR_ARG;
-  try {
-    HIP_CHECK(hipSetDevice(h->prm.device));
-    if (!h->comm || !h->comm->comm || h->comm->world != 1) NSX_THROW(NSX_ERR_ARG, "nsx_comm_self_halo_test needs a 1-rank RCCL communicator (nsx_comm_init)");
-    nsx::HaloPlan p;
-    p.self_test = true;
-    p.n_own = n_own;
-    p.nbr = {0};
-    p.send_ptr = {0, n_ghost};
-    p.recv_ptr = {0, n_ghost};
-    std::vector<int32_t> idx(n_ghost);
-    for (int k = 0; k < n_ghost; ++k) idx[k] = (int32_t)((7ll * k + 3) % n_own);
-    p.send_idx.upload(idx, h->stream);
-    p.sendbuf.alloc((size_t)n_ghost * ncomp);
-    std::vector<double> x((size_t)(n_own + n_ghost) * ncomp, -1.0);
-    for (size_t i = 0; i < (size_t)n_own * ncomp; ++i) x[i] = 0.5 + (double)i;
-    nsx::DevBuf<double> xd;
-    xd.upload(x, h->stream);
-    for (int rep = 0; rep < 3; ++rep) {  // several exchanges in a row: the event and the buffers are reused
-      nsx::comm_halo_begin(h, p, xd.p, ncomp);
-      nsx::comm_halo_finish(h, p, xd.p, ncomp);
-    }
-    xd.download(x.data(), x.size(), h->stream);
-    double e = 0.0;
-    for (int k = 0; k < n_ghost; ++k)
-      for (int c = 0; c < ncomp; ++c) e = std::max(e, std::fabs(x[((size_t)n_own + k) * ncomp + c] - (0.5 + (double)((size_t)idx[k] * ncomp + c))));
-    *max_err = e;
-    if (p.ev_done) (void)hipEventDestroy(p.ev_done);
-  } catch (const nsx::Error &e) {
-    h->err = e.msg;
-    return e.code;
+  NSX_TRY(h)
+  HIP_CHECK(hipSetDevice(h->prm.device));
+  if (!h->comm || !h->comm->comm || h->comm->world != 1) NSX_THROW(NSX_ERR_ARG, "nsx_comm_self_halo_test needs a 1-rank RCCL communicator (nsx_comm_init)");
+  nsx::HaloPlan p;
+  p.self_test = true;
+  p.n_own = n_own;
+  p.nbr = {0};
+  p.send_ptr = {0, n_ghost};
+  p.recv_ptr = {0, n_ghost};
+  std::vector<int32_t> idx(n_ghost);
+  for (int k = 0; k < n_ghost; ++k) idx[k] = (int32_t)((7ll * k + 3) % n_own);
+  p.send_idx.upload(idx, h->stream);
+  p.sendbuf.alloc((size_t)n_ghost * ncomp);
+  std::vector<double> x((size_t)(n_own + n_ghost) * ncomp, -1.0);
+  for (size_t i = 0; i < (size_t)n_own * ncomp; ++i) x[i] = 0.5 + (double)i;
+  nsx::DevBuf<double> xd;
+  xd.upload(x, h->stream);
+  for (int rep = 0; rep < 3; ++rep) {  // several exchanges in a row: the event and the buffers are reused
+    nsx::comm_halo_begin(h, p, xd.p, ncomp);
+    nsx::comm_halo_finish(h, p, xd.p, ncomp);
   }
-  return NSX_OK;
+  xd.download(x.data(), x.size(), h->stream);
+  double e = 0.0;
+  for (int k = 0; k < n_ghost; ++k)
+    for (int c = 0; c < ncomp; ++c) e = std::max(e, std::fabs(x[((size_t)n_own + k) * ncomp + c] - (0.5 + (double)((size_t)idx[k] * ncomp + c))));
+  *max_err = e;
+  if (p.ev_done) (void)hipEventDestroy(p.ev_done);
+  NSX_CATCH(h)
 }
 
 int nsx_comm_counters(const nsx_handle *h, long long counts[2]) {
@@ -513,6 +505,7 @@ int nsx_comm_counters(const nsx_handle *h, long long counts[2]) {
 
 int nsx_comm_init_callbacks(nsx_handle *h, int rank, int world, nsx_allreduce_fn allreduce, nsx_exchange_fn exchange, void *ctx) {
   if (!h || world < 1 || rank < 0 || rank >= world || !allreduce || !exchange) return NSX_ERR_ARG;
+  NSX_TRY(h)
   nsx::comm_destroy(h);
   h->comm = new nsx::Comm;
   h->comm->rank = rank;
@@ -523,7 +516,7 @@ int nsx_comm_init_callbacks(nsx_handle *h, int rank, int world, nsx_allreduce_fn
   h->mgs.dist_state = -1;
   h->mgs.dist_fit.clear();
   h->cgd_agreed = -1;
-  return NSX_OK;
+  NSX_CATCH(h)
 }
 
 }  // extern "C"

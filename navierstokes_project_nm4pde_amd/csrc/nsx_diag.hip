@@ -14,7 +14,7 @@
 #include <algorithm>
 #include <cmath>
 
-#include "nsx_internal.hpp"
+#include "nsx_post.hpp"
 
 namespace nsx {
 
@@ -190,10 +190,10 @@ __global__ __launch_bounds__(256) void k_diag_reduce(int n, int stride_in, const
 // ------------------------------------------------------------------ host drivers
 template <int DIM, int NP2, int NQ>
 static void launch_diag(nsx_handle *h) {
-  const double bytes = (double)h->diag_n_counted * (4.0 * NP2 + 8.0 * (DIM * DIM + 1) + 2.0 * 8.0 * DIM * NP2) + 8.0 * NSX_DIAG_COUNT * h->n_cells;
+  const double bytes = (double)h->diag.n_counted * (4.0 * NP2 + 8.0 * (DIM * DIM + 1) + 2.0 * 8.0 * DIM * NP2) + 8.0 * NSX_DIAG_COUNT * h->n_cells;
   LaunchScope ls(h, "diag_cells", bytes);
-  hipLaunchKernelGGL((k_cell_diag<DIM, NP2, NQ>), dim3(cdiv(h->n_cells, 64)), dim3(64), 0, h->stream, h->n_cells, h->diag_counted.p,
-                     h->cell_n2.p, h->geo.p, h->tab_N2.p, h->tab_dN2.p, h->tab_w.p, h->sol.p, h->prev_sol.p, h->prm.deltat, h->diag_planes.p);
+  hipLaunchKernelGGL((k_cell_diag<DIM, NP2, NQ>), dim3(cdiv(h->n_cells, 64)), dim3(64), 0, h->stream, h->n_cells, h->diag.counted.p,
+                     h->cell_n2.p, h->geo.p, h->tab_N2.p, h->tab_dN2.p, h->tab_w.p, h->sol.p, h->prev_sol.p, h->prm.deltat, h->diag.planes.p);
 }
 
 // the instantiation set of k_cell_convection (dispatch_conv, nsx_assemble.hip); false: none for this (dim, n_p2, n_q)
@@ -231,9 +231,9 @@ static bool dispatch_diag(nsx_handle *h, bool launch) {
 void diag_mesh_setup(nsx_handle *h) {
   const int np2 = h->np2, n_cells = h->n_cells;
   std::vector<uint8_t> counted((size_t)n_cells, 1);
-  h->diag_n_counted = n_cells;
+  h->diag.n_counted = n_cells;
   if (h->dist) {
-    h->diag_n_counted = 0;
+    h->diag.n_counted = 0;
     for (int c = 0; c < n_cells; ++c) {
       int32_t lowest = INT32_MAX;
       for (int a = 0; a < np2; ++a) {
@@ -241,11 +241,11 @@ void diag_mesh_setup(nsx_handle *h) {
         lowest = std::min(lowest, l < h->N2 ? h->goff_u + l : h->ghost_u[l - h->N2]);
       }
       counted[c] = lowest >= h->goff_u && lowest < h->goff_u + h->N2;
-      h->diag_n_counted += counted[c];
+      h->diag.n_counted += counted[c];
     }
   }
-  h->diag_counted.upload(counted, h->stream);
-  h->diag_valid = false;
+  h->diag.counted.upload(counted, h->stream);
+  h->diag.valid = false;
 }
 
 static void fold_planes(nsx_handle *h, double totals[FOLD_PLANES]) {
@@ -256,10 +256,10 @@ static void fold_planes(nsx_handle *h, double totals[FOLD_PLANES]) {
     sizes.push_back(cdiv(n, FOLD_CELLS));
     total += (size_t)FOLD_PLANES * sizes.back();
   }
-  h->diag_fold.alloc(total);
+  h->diag.fold.alloc(total);
   LaunchScope ls(h, "diag_reduce", 8.0 * NSX_DIAG_COUNT * h->n_cells);
-  const double *in = h->diag_planes.p;
-  double *out = h->diag_fold.p;
+  const double *in = h->diag.planes.p;
+  double *out = h->diag.fold.p;
   int n = h->n_cells;
   for (size_t l = 0; l < sizes.size(); ++l) {
     if (l == 0)
@@ -276,20 +276,20 @@ static void fold_planes(nsx_handle *h, double totals[FOLD_PLANES]) {
 
 // returns the number of per-cell values (of all ranks) that are not finite
 static double run_diagnostics(nsx_handle *h, nsx_flow_diag *out) {
-  if (!h->have_mesh) NSX_THROW(NSX_ERR_ARG, "nsx_set_tables and nsx_set_mesh first");
+  post_check_space(h, "nsx_compute_diagnostics");
   if (!dispatch_diag(h, false))
     NSX_THROW(NSX_ERR_UNSUPPORTED, "no diagnostics kernel instantiated for dim=%d n_p2=%d n_q=%d (see dispatch_diag in nsx_diag.hip)", h->dim, h->np2, h->n_q);
   HIP_CHECK(hipSetDevice(h->prm.device));
-  h->diag_planes.alloc((size_t)NSX_DIAG_COUNT * h->n_cells);
-  h->diag_valid = false;
+  h->diag.planes.alloc((size_t)NSX_DIAG_COUNT * h->n_cells);
+  h->diag.valid = false;
   dispatch_diag(h, true);
   double t[FOLD_PLANES];
   fold_planes(h, t);
   HIP_CHECK(hipStreamSynchronize(h->stream));
-  h->diag_valid = true;
+  h->diag.valid = true;
   // [0..4] the five sums, [5] volume, [6] cells counted, [7] values that are not finite
   double s[8] = {t[NSX_DIAG_ENERGY], t[NSX_DIAG_DIV2], t[NSX_DIAG_GRAD2], t[NSX_DIAG_ENSTROPHY], t[NSX_DIAG_CHANGE2], t[NSX_DIAG_VOLUME],
-                 (double)h->diag_n_counted, t[NSX_DIAG_COUNT]};
+                 (double)h->diag.n_counted, t[NSX_DIAG_COUNT]};
   double cfl = t[NSX_DIAG_CFL], speed = t[NSX_DIAG_SPEED];
   if (h->comm) {
     // every rank issues the same two collectives, whatever it found: an error is reported behind them, never instead of them
@@ -307,11 +307,11 @@ static double run_diagnostics(nsx_handle *h, nsx_flow_diag *out) {
     std::vector<double> m((size_t)2 * w, 0.0);
     m[h->rank] = cfl;
     m[w + h->rank] = speed;
-    h->diag_max.alloc(m.size());
-    HIP_CHECK(hipMemcpyAsync(h->diag_max.p, m.data(), m.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    h->diag.max.alloc(m.size());
+    HIP_CHECK(hipMemcpyAsync(h->diag.max.p, m.data(), m.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIP_CHECK(hipStreamSynchronize(h->stream));
-    comm_allreduce_partials(h, h->diag_max.p, 2 * w);
-    h->diag_max.download(m.data(), m.size(), h->stream);
+    comm_allreduce_partials(h, h->diag.max.p, 2 * w);
+    h->diag.max.download(m.data(), m.size(), h->stream);
     cfl = speed = 0.0;
     for (int r = 0; r < w; ++r) {
       cfl = nan_max(cfl, m[r]);
@@ -335,31 +335,21 @@ static double run_diagnostics(nsx_handle *h, nsx_flow_diag *out) {
 extern "C" {
 
 int nsx_compute_diagnostics(nsx_handle *h, nsx_flow_diag *out) {
-  if (!h) return NSX_ERR_ARG;
-  try {
-    if (!out) NSX_THROW(NSX_ERR_ARG, "null output");
-    const double bad = nsx::run_diagnostics(h, out);
-    if (!(bad == 0.0)) NSX_THROW(NSX_ERR_NUMERIC, "flow diagnostics: %.0f per-cell values are not finite (speed_max = %g)", bad, out->speed_max);
-  } catch (const nsx::Error &e) {
-    h->err = e.msg;
-    return e.code;
-  }
-  return NSX_OK;
+  NSX_TRY(h)
+  if (!out) NSX_THROW(NSX_ERR_ARG, "null output");
+  const double bad = nsx::run_diagnostics(h, out);
+  if (!(bad == 0.0)) NSX_THROW(NSX_ERR_NUMERIC, "flow diagnostics: %.0f per-cell values are not finite (speed_max = %g)", bad, out->speed_max);
+  NSX_CATCH(h)
 }
 
 int nsx_get_cell_diagnostic(nsx_handle *h, int which, double *values) {
-  if (!h) return NSX_ERR_ARG;
-  try {
-    if (!values || which < 0 || which >= NSX_DIAG_COUNT) NSX_THROW(NSX_ERR_ARG, "bad diagnostic %d / null output", which);
-    if (!h->have_mesh || !h->diag_valid) NSX_THROW(NSX_ERR_ARG, "nsx_compute_diagnostics first");
-    HIP_CHECK(hipSetDevice(h->prm.device));
-    HIP_CHECK(hipMemcpyAsync(values, h->diag_planes.p + (size_t)which * h->n_cells, (size_t)h->n_cells * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_CHECK(hipStreamSynchronize(h->stream));
-  } catch (const nsx::Error &e) {
-    h->err = e.msg;
-    return e.code;
-  }
-  return NSX_OK;
+  NSX_TRY(h)
+  if (!values || which < 0 || which >= NSX_DIAG_COUNT) NSX_THROW(NSX_ERR_ARG, "bad diagnostic %d / null output", which);
+  if (!h->have_mesh || !h->diag.valid) NSX_THROW(NSX_ERR_ARG, "nsx_compute_diagnostics first");
+  HIP_CHECK(hipSetDevice(h->prm.device));
+  HIP_CHECK(hipMemcpyAsync(values, h->diag.planes.p + (size_t)which * h->n_cells, (size_t)h->n_cells * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIP_CHECK(hipStreamSynchronize(h->stream));
+  NSX_CATCH(h)
 }
 
 }  // extern "C"

@@ -90,69 +90,60 @@ extern "C" {
 
 int nsx_set_force_faces(nsx_handle *h, int n_faces, const int32_t *cells, const int32_t *local_faces, int n_qf, const double *N2f,
                         const double *dN2f, const double *N1f, const double *wf) {
-  if (!h) return NSX_ERR_ARG;
-  try {
-    if (!h->have_mesh) NSX_THROW(NSX_ERR_ARG, "nsx_set_mesh first");
-    if (n_faces < 0 || n_qf < 1 || (n_faces && (!cells || !local_faces)) || !N2f || !dN2f || !N1f || !wf) NSX_THROW(NSX_ERR_ARG, "bad face tables");
-    HIP_CHECK(hipSetDevice(h->prm.device));
-    const int nfr = h->dim + 1;
-    for (int f = 0; f < n_faces; ++f)
-      if (cells[f] < 0 || cells[f] >= h->n_cells || local_faces[f] < 0 || local_faces[f] >= nfr) NSX_THROW(NSX_ERR_ARG, "face %d: bad cell / local face", f);
-    h->ff_n = n_faces;
-    h->ff_nq = n_qf;
-    h->ff_cells.upload(cells, n_faces, h->stream);
-    h->ff_lf.upload(local_faces, n_faces, h->stream);
-    h->ff_N2.upload(N2f, (size_t)nfr * n_qf * h->np2, h->stream);
-    h->ff_dN2.upload(dN2f, (size_t)nfr * n_qf * h->np2 * h->dim, h->stream);
-    h->ff_N1.upload(N1f, (size_t)nfr * n_qf * h->np1, h->stream);
-    h->ff_w.upload(wf, n_qf, h->stream);
-    h->ff_out.alloc((size_t)2 * std::max(1, n_faces * n_qf));
-  } catch (const nsx::Error &e) {
-    h->err = e.msg;
-    return e.code;
-  }
-  return NSX_OK;
+  NSX_TRY(h)
+  if (!h->have_mesh) NSX_THROW(NSX_ERR_ARG, "nsx_set_mesh first");
+  if (n_faces < 0 || n_qf < 1 || (n_faces && (!cells || !local_faces)) || !N2f || !dN2f || !N1f || !wf) NSX_THROW(NSX_ERR_ARG, "bad face tables");
+  HIP_CHECK(hipSetDevice(h->prm.device));
+  const int nfr = h->dim + 1;
+  for (int f = 0; f < n_faces; ++f)
+    if (cells[f] < 0 || cells[f] >= h->n_cells || local_faces[f] < 0 || local_faces[f] >= nfr) NSX_THROW(NSX_ERR_ARG, "face %d: bad cell / local face", f);
+  h->ff.n = n_faces;
+  h->ff.nq = n_qf;
+  h->ff.cells.upload(cells, n_faces, h->stream);
+  h->ff.lf.upload(local_faces, n_faces, h->stream);
+  h->ff.N2.upload(N2f, (size_t)nfr * n_qf * h->np2, h->stream);
+  h->ff.dN2.upload(dN2f, (size_t)nfr * n_qf * h->np2 * h->dim, h->stream);
+  h->ff.N1.upload(N1f, (size_t)nfr * n_qf * h->np1, h->stream);
+  h->ff.w.upload(wf, n_qf, h->stream);
+  h->ff.out.alloc((size_t)2 * std::max(1, n_faces * n_qf));
+  NSX_CATCH(h)
 }
 
 int nsx_compute_forces(nsx_handle *h, double *drag, double *lift) {
   if (!h || !drag || !lift) return NSX_ERR_ARG;
-  try {
-    if (h->ff_nq == 0) NSX_THROW(NSX_ERR_ARG, "nsx_set_force_faces first");
-    HIP_CHECK(hipSetDevice(h->prm.device));
-    const int n = h->ff_n * h->ff_nq;
-    double sums[2] = {0.0, 0.0};
-    if (n) {
-      nsx::LaunchScope ls(h, "forces", 0);
-      if (h->dim == 2)
-        hipLaunchKernelGGL((nsx::k_forces<2>), dim3(nsx::cdiv(n, 128)), dim3(128), 0, h->stream, h->ff_n, h->ff_nq, h->ff_cells.p, h->ff_lf.p,
-                           h->n_cells, h->np2, h->np1, h->cell_n2.p, h->cell_n1.p, h->geo.p, h->ff_N2.p, h->ff_dN2.p, h->ff_N1.p, h->ff_w.p,
-                           h->sol.p, h->off_p, h->prm.nu, 1.0, h->ff_out.p);
-      else
-        hipLaunchKernelGGL((nsx::k_forces<3>), dim3(nsx::cdiv(n, 128)), dim3(128), 0, h->stream, h->ff_n, h->ff_nq, h->ff_cells.p, h->ff_lf.p,
-                           h->n_cells, h->np2, h->np1, h->cell_n2.p, h->cell_n1.p, h->geo.p, h->ff_N2.p, h->ff_dN2.p, h->ff_N1.p, h->ff_w.p,
-                           h->sol.p, h->off_p, h->prm.nu, 1.0, h->ff_out.p);
-      std::vector<double> buf((size_t)2 * n);
-      h->ff_out.download(buf.data(), buf.size(), h->stream);
-      for (int t = 0; t < n; ++t) {  // fixed order: face by face, point by point
-        sums[0] += buf[2 * t];
-        sums[1] += buf[2 * t + 1];
-      }
+  NSX_TRY(h)
+  if (h->ff.nq == 0) NSX_THROW(NSX_ERR_ARG, "nsx_set_force_faces first");
+  HIP_CHECK(hipSetDevice(h->prm.device));
+  const int n = h->ff.n * h->ff.nq;
+  double sums[2] = {0.0, 0.0};
+  if (n) {
+    nsx::LaunchScope ls(h, "forces", 0);
+    if (h->dim == 2)
+      hipLaunchKernelGGL((nsx::k_forces<2>), dim3(nsx::cdiv(n, 128)), dim3(128), 0, h->stream, h->ff.n, h->ff.nq, h->ff.cells.p, h->ff.lf.p,
+                         h->n_cells, h->np2, h->np1, h->cell_n2.p, h->cell_n1.p, h->geo.p, h->ff.N2.p, h->ff.dN2.p, h->ff.N1.p, h->ff.w.p,
+                         h->sol.p, h->off_p, h->prm.nu, 1.0, h->ff.out.p);
+    else
+      hipLaunchKernelGGL((nsx::k_forces<3>), dim3(nsx::cdiv(n, 128)), dim3(128), 0, h->stream, h->ff.n, h->ff.nq, h->ff.cells.p, h->ff.lf.p,
+                         h->n_cells, h->np2, h->np1, h->cell_n2.p, h->cell_n1.p, h->geo.p, h->ff.N2.p, h->ff.dN2.p, h->ff.N1.p, h->ff.w.p,
+                         h->sol.p, h->off_p, h->prm.nu, 1.0, h->ff.out.p);
+    std::vector<double> buf((size_t)2 * n);
+    h->ff.out.download(buf.data(), buf.size(), h->stream);
+    for (int t = 0; t < n; ++t) {  // fixed order: face by face, point by point
+      sums[0] += buf[2 * t];
+      sums[1] += buf[2 * t + 1];
     }
-    if (h->comm) {  // Utilities::MPI::sum (NS3D.cpp:830-831)
-      h->scal_host[0] = sums[0];
-      h->scal_host[1] = sums[1];
-      HIP_CHECK(hipMemcpyAsync(h->scal.p, h->scal_host, 2 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-      h->slot_nb[0] = h->slot_nb[1] = 0;
-      nsx::comm_allreduce_scalars(h, 0, 2);
-      nsx::read_scalars(h, 0, 2, sums);
-    }
-    *drag = sums[0];
-    *lift = sums[1];
-  } catch (const nsx::Error &e) {
-    h->err = e.msg;
-    return e.code;
   }
-  return NSX_OK;
+  if (h->comm) {  // Utilities::MPI::sum (NS3D.cpp:830-831)
+    h->scal_host[0] = sums[0];
+    h->scal_host[1] = sums[1];
+    HIP_CHECK(hipMemcpyAsync(h->scal.p, h->scal_host, 2 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    h->slot_nb[0] = h->slot_nb[1] = 0;
+    nsx::comm_allreduce_scalars(h, 0, 2);
+    nsx::read_scalars(h, 0, 2, sums);
+  }
+  *drag = sums[0];
+  *lift = sums[1];
+  NSX_CATCH(h)
 }
 
 }  // extern "C"

@@ -10,12 +10,12 @@
 //   B-graph        P1 x P2 CSR, dim values per entry: block (1,0) = +int psi_k d_c phi_j   (NS3D.cpp:261)
 //   S-graph        P1 x P1 CSR = structural product B*G: negative_S_tilde and its ILU(0)   (Prec.hpp:144,358)
 //   cell tables    SoA: cell_n2[a][cell], cell_n1[v][cell], geo[k][cell] (J^-1 row-major, then |det J|)
-//                  cell_x0[d][cell] (vertex 0: x = X0 + J lambda, the point probes' search)
-//                  cell_nbr[k][cell] (cell across the face opposite local vertex k, -1: boundary; the tracers' walk, built on demand)
+//                  probe.cell_x0[d][cell] (vertex 0: x = X0 + J lambda, the point probes' search; ProbeState)
+//                  tracer.cell_nbr[k][cell] (cell across the face opposite local vertex k, -1: boundary; the tracers' walk, built on demand; TracerState)
 //   patch table    per owned P2 node the (cell, local node) pairs that hold it, ascending cell, in tiles of 64 nodes of (nearly) one
-//                  patch size (the nodal fields' gather, built on demand: host/nodal_patch.hpp)
-//   iso tables     cell_x[(v dim + d)][cell] vertex coordinates, node maps in the internal numbering (P2 node -> P1 nodes, position, slot of
-//                  the nodal results), built on demand (the isosurface extraction: nsx_iso.hip)
+//                  patch size (the nodal fields' gather, built on demand: host/nodal_patch.hpp; NodalState)
+//   iso tables     iso.cellx[(v dim + d)][cell] vertex coordinates, node maps in the internal numbering (P2 node -> P1 nodes, position, slot of
+//                  the nodal results), built on demand (the isosurface extraction: nsx_iso.hip; IsoState)
 //   gather maps    per CSR entry the list of (local entry, cell) contributions -> deterministic assembly, no atomics
 #pragma once
 #include <hip/hip_runtime.h>
@@ -23,6 +23,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <exception>
 #include <map>
 #include <string>
 #include <functional>
@@ -59,6 +60,27 @@ struct Error {
     snprintf(buf_, sizeof(buf_), __VA_ARGS__);             \
     throw ::nsx::Error{(code_), std::string(buf_)};        \
   } while (0)
+
+// THE guard of every extern "C" entry that takes a handle: NSX_TRY(h) <body> NSX_CATCH(h).  A null handle is NSX_ERR_ARG; nsx::Error becomes
+// its code, any other std::exception (bad_alloc / length_error of a vector sized by the caller) NSX_ERR_ARG with what() as the message;
+// nothing unwinds through the C frame.  NSX_CATCH_TO is the same pair of handlers for an entry that has no handle yet (nsx_create) or has
+// work to do behind them: the message goes to err_, the optional statements run before the return.
+#define NSX_TRY(h_)              \
+  if (!(h_)) return NSX_ERR_ARG; \
+  try {
+#define NSX_CATCH_TO(err_, ...)       \
+  }                                   \
+  catch (const nsx::Error &e) {       \
+    err_ = e.msg;                     \
+    __VA_ARGS__;                      \
+    return e.code;                    \
+  }                                   \
+  catch (const std::exception &e) {   \
+    err_ = e.what();                  \
+    __VA_ARGS__;                      \
+    return NSX_ERR_ARG;               \
+  }
+#define NSX_CATCH(h_) NSX_CATCH_TO((h_)->err) return NSX_OK;
 
 #define HIP_CHECK(expr)                                                                                   \
   do {                                                                                                    \
@@ -268,6 +290,102 @@ struct MgsState {
   int last_fused = 0, fused_launches = 0;  // the last persistent sweep had the velocity triangular solves inside (k_ilu_mgs)
 };
 
+// ---- State of the post-processing features, one block per feature.  Each block says what a new mesh drops (mesh_changed, called by
+//      post_mesh_changed below); whatever it does not reset there survives a new internal layout / rank table as well, because the cells
+//      and the caller's node numbering do not move with them.  What is kept in the INTERNAL node numbering follows nsx_handle::layout_epoch.
+
+// Force evaluation (nsx_forces.hip): obstacle faces + face-quadrature tables.  Replaced as a whole by nsx_set_force_faces.
+struct ForceState {
+  int n = 0, nq = 0;
+  DevBuf<int32_t> cells, lf;
+  DevBuf<double> N2, dN2, N1, w, out;
+};
+
+// Flow diagnostics (nsx_diag.hip).  diag_mesh_setup refills counted / n_counted and drops the results with EVERY mesh installation
+// (a new mesh, a new layout, new rank tables of a handle with a layout).
+struct DiagState {
+  DevBuf<uint8_t> counted;  // [n_cells] 1 = this handle counts the cell (distributed: the owner of its lowest global P2 node does)
+  int n_counted = 0;
+  DevBuf<double> planes;    // [NSX_DIAG_COUNT][n_cells] per-cell values of the last nsx_compute_diagnostics (allocated by the first one)
+  DevBuf<double> fold;      // the levels of their fold
+  DevBuf<double> max;       // [2 * world] the ranks' maxima on their way through the SUM collective
+  bool valid = false;       // planes holds the values of a finished call on the current mesh
+};
+
+// Point probes (nsx_probe.hip).  The set outlives a new layout / rank table, not a new mesh.
+struct ProbeState {
+  DevBuf<double> cell_x0;   // SoA [dim][n_cells]: vertex 0 of every cell, beside geo (x = X0 + J lambda); probe_mesh_setup, with every mesh installation
+  int n = 0;                // probes of the current set (0: none)
+  DevBuf<int32_t> cell;     // [n] the cell this handle evaluates the probe in (caller's cell order), -1: in no cell / another rank's
+  DevBuf<double> lambda;    // SoA [dim+1][n] barycentric coordinates in that cell, stored by nsx_set_probes
+  DevBuf<double> out;       // SoA [dim + 1 + dim^2][n] values of the last nsx_eval_probes
+  std::vector<int32_t> cells_h, owner_h;  // what nsx_get_probe_cells hands out
+  std::vector<double> lambda_h;           // [n][dim+1]
+  void mesh_changed() {     // a new mesh drops the probe set
+    n = 0;
+    cells_h.clear();
+    owner_h.clear();
+    lambda_h.clear();
+  }
+};
+
+// Tracer particles (nsx_tracer.hip).  The set outlives a new layout / rank table, not a new mesh.
+struct TracerState {
+  DevBuf<int32_t> cell_nbr;  // SoA [dim+1][n_cells]: cell across the face opposite local vertex k, -1: boundary; built by the first nsx_set_tracers on a mesh
+  bool have_nbr = false;
+  int n = 0;                 // particles of the current set (0: none)
+  double tol = 0.0;          // containment tolerance of the set (nsx_set_tracers), used by every walk
+  DevBuf<double> x;          // SoA [dim][n] positions
+  DevBuf<double> age;        // [n]
+  DevBuf<int32_t> cell, status, face;  // [n] each
+  void mesh_changed() {      // a new mesh drops the tracer set and the face-neighbour table
+    n = 0;
+    have_nbr = false;
+  }
+};
+
+// Nodal fields (nsx_nodal.hip).  The patch table is in the caller's node and cell numbering: it outlives a new layout / rank table, not a new mesh.
+struct NodalState {
+  bool have_patches = false;        // the node -> (cell, local node) patch table of the current mesh is on the device; built by the first nsx_compute_nodal_fields on a mesh
+  DevBuf<int32_t> tile_ptr, ent;    // host/nodal_patch.hpp: [tiles + 1] first step of every tile of 64 slots, [steps][64] cell << 4 | local node (-1: padding)
+  std::vector<int32_t> slot_of;     // [N2] caller-local owned node -> slot
+  int tiles = 0;
+  int64_t entries = 0;              // entries of ent, padding included
+  DevBuf<double> out;               // SoA [dim^2 + (3 | 1) + 3][64 tiles] in slot order: Gbar, vorticity, Q, strain rate, divergence of the last nsx_compute_nodal_fields
+  bool valid = false;               // out holds the values of a finished call on the current mesh
+  void mesh_changed() {             // a new mesh drops the patch table and the results
+    have_patches = false;
+    valid = false;
+    slot_of.clear();
+  }
+};
+
+// Isosurfaces and slices (nsx_iso.hip).  Coordinates and orientation are per cell and survive a new layout / rank table; the node maps are
+// in the INTERNAL numbering and are rebuilt when nsx_handle::layout_epoch has moved past the epoch they were built in.
+struct IsoState {
+  bool have_coords = false;         // cellx / flip hold the current mesh; uploaded by the first nsx_extract_isosurface on a mesh
+  DevBuf<double> cellx;             // SoA [(dim+1) dim][n_cells]: the vertex coordinates of every cell
+  DevBuf<uint8_t> flip;             // [n_cells] 1 = det J < 0: the primitives of the cell swap their last two vertices
+  int map_epoch = -1, slot_epoch = -1;  // the layout_epoch the node maps below were built in
+  DevBuf<int32_t> pmap;             // [2][N2_loc] internal P2 node -> its P1 node (second entry -1), or the two P1 nodes of its line
+  DevBuf<double> nodex;             // SoA [dim][N2_loc] position of every internal P2 node
+  DevBuf<int32_t> slot;             // [N2_loc] internal P2 node -> slot of nodal.out (-1: a ghost)
+  DevBuf<double> s;                 // [2][N2_loc] nodal scalars of the last call: field plane, colour plane
+  DevBuf<int32_t> pack;             // [n_cells] prefix inside the workgroup << 5 | primitives of the cell
+  DevBuf<int32_t> wg_tot;           // [workgroups] primitives per workgroup of k_iso_count
+  DevBuf<long long> wg_off;         // [workgroups + 1] their exclusive prefix sum; the last entry is the total
+  DevBuf<double> pts, col;          // SoA [dim dim][cap], [dim][cap]: the primitives of the last extract
+  DevBuf<int32_t> cells;            // [cap]
+  int64_t cap = 0, n = 0;           // capacity (never shrinks), primitives of the last extract
+  bool valid = false, has_colour = false;  // the buffers hold a finished extract on the current mesh; it had a colour source
+  void mesh_changed() {             // a new mesh drops the coordinates, the node maps and the result
+    have_coords = false;
+    valid = false;
+    n = 0;
+    map_epoch = slot_epoch = -1;
+  }
+};
+
 struct Comm;  // RCCL state (nsx_comm.hip)
 
 enum { N_SLOTS = 128 };  // device scalar slots (reduction results)
@@ -382,58 +500,14 @@ struct nsx_handle {
   int cg_last_path = 0;                     // the last Schur CG: 0 none yet, 1 one launch per operation, 2 one persistent launch, 3 two launches per iteration
   int cg_last_rpg = 0, cg_last_lres = 0;    // ... its persistent kernel's rows per lane group (0, 6, 8) and whether the operator sat in LDS (nsx_path_info [28], [29]); 0 when it did not run
   nsx::DevBuf<double> cgd_vec, cgd_parts;   // distributed Schur CG in two launches per iteration (cg_schur_fused): g, h, S d, d (double-buffered, with ghosts); partial sums
-  // ---- force evaluation (compute_forces): obstacle faces + face-quadrature tables
-  int ff_n = 0, ff_nq = 0;
-  nsx::DevBuf<int32_t> ff_cells, ff_lf;
-  nsx::DevBuf<double> ff_N2, ff_dN2, ff_N1, ff_w, ff_out;
-  // ---- flow diagnostics (nsx_diag.hip)
-  nsx::DevBuf<uint8_t> diag_counted;  // [n_cells] 1 = this handle counts the cell (distributed: the owner of its lowest global P2 node does)
-  int diag_n_counted = 0;
-  nsx::DevBuf<double> diag_planes;    // [NSX_DIAG_COUNT][n_cells] per-cell values of the last nsx_compute_diagnostics (allocated by the first one)
-  nsx::DevBuf<double> diag_fold;      // the levels of their fold
-  nsx::DevBuf<double> diag_max;       // [2 * world] the ranks' maxima on their way through the SUM collective
-  bool diag_valid = false;            // diag_planes holds the values of a finished call on the current mesh
-  // ---- point probes (nsx_probe.hip)
-  nsx::DevBuf<double> cell_x0;        // SoA [dim][n_cells]: vertex 0 of every cell, beside geo (x = X0 + J lambda)
-  int probe_n = 0;                    // probes of the current set (0: none); the set outlives a new layout / rank table, not a new mesh
-  nsx::DevBuf<int32_t> probe_cell;    // [probe_n] the cell this handle evaluates the probe in (caller's cell order), -1: in no cell / another rank's
-  nsx::DevBuf<double> probe_lambda;   // SoA [dim+1][probe_n] barycentric coordinates in that cell, stored by nsx_set_probes
-  nsx::DevBuf<double> probe_out;      // SoA [dim + 1 + dim^2][probe_n] values of the last nsx_eval_probes
-  std::vector<int32_t> probe_cells_h, probe_owner_h;  // what nsx_get_probe_cells hands out
-  std::vector<double> probe_lambda_h;                 // [probe_n][dim+1]
-  // ---- tracer particles (nsx_tracer.hip)
-  nsx::DevBuf<int32_t> cell_nbr;      // SoA [dim+1][n_cells]: cell across the face opposite local vertex k, -1: boundary; built by the first nsx_set_tracers on a mesh
-  bool have_nbr = false;
-  int tracer_n = 0;                   // particles of the current set (0: none); outlives a new layout / rank table, not a new mesh
-  double tracer_tol = 0.0;            // containment tolerance of the set (nsx_set_tracers), used by every walk
-  nsx::DevBuf<double> tracer_x;       // SoA [dim][tracer_n] positions
-  nsx::DevBuf<double> tracer_age;     // [tracer_n]
-  nsx::DevBuf<int32_t> tracer_cell, tracer_status, tracer_face;  // [tracer_n] each
-  // ---- nodal fields (nsx_nodal.hip)
-  bool have_patches = false;          // the node -> (cell, local node) patch table of the current mesh is on the device; built by the first nsx_compute_nodal_fields on a mesh
-  nsx::DevBuf<int32_t> nodal_tile_ptr, nodal_ent;  // host/nodal_patch.hpp: [nodal_tiles + 1] first step of every tile of 64 slots, [steps][64] cell << 4 | local node (-1: padding)
-  std::vector<int32_t> nodal_slot_of; // [N2] caller-local owned node -> slot; outlives a new layout / rank table, not a new mesh
-  int nodal_tiles = 0;
-  int64_t nodal_entries = 0;          // entries of nodal_ent, padding included
-  nsx::DevBuf<double> nodal_out;      // SoA [dim^2 + (3 | 1) + 3][64 nodal_tiles] in slot order: Gbar, vorticity, Q, strain rate, divergence of the last nsx_compute_nodal_fields
-  bool nodal_valid = false;           // nodal_out holds the values of a finished call on the current mesh
-  // ---- isosurfaces and slices (nsx_iso.hip)
-  int layout_epoch = 0;               // counts the installations of a mesh / an internal layout: what is kept in the INTERNAL node numbering is rebuilt when it moves
-  bool iso_have_coords = false;       // iso_cellx / iso_flip hold the current mesh; uploaded by the first nsx_extract_isosurface on a mesh
-  nsx::DevBuf<double> iso_cellx;      // SoA [(dim+1) dim][n_cells]: the vertex coordinates of every cell
-  nsx::DevBuf<uint8_t> iso_flip;      // [n_cells] 1 = det J < 0: the primitives of the cell swap their last two vertices
-  int iso_map_epoch = -1, iso_slot_epoch = -1;  // the layout_epoch the node maps below were built in
-  nsx::DevBuf<int32_t> iso_pmap;      // [2][N2_loc] internal P2 node -> its P1 node (second entry -1), or the two P1 nodes of its line
-  nsx::DevBuf<double> iso_nodex;      // SoA [dim][N2_loc] position of every internal P2 node
-  nsx::DevBuf<int32_t> iso_slot;      // [N2_loc] internal P2 node -> slot of nodal_out (-1: a ghost)
-  nsx::DevBuf<double> iso_s;          // [2][N2_loc] nodal scalars of the last call: field plane, colour plane
-  nsx::DevBuf<int32_t> iso_pack;      // [n_cells] prefix inside the workgroup << 5 | primitives of the cell
-  nsx::DevBuf<int32_t> iso_wg_tot;    // [workgroups] primitives per workgroup of k_iso_count
-  nsx::DevBuf<long long> iso_wg_off;  // [workgroups + 1] their exclusive prefix sum; the last entry is the total
-  nsx::DevBuf<double> iso_pts, iso_col;  // SoA [dim dim][iso_cap], [dim][iso_cap]: the primitives of the last extract
-  nsx::DevBuf<int32_t> iso_cells;     // [iso_cap]
-  int64_t iso_cap = 0, iso_n = 0;     // capacity (never shrinks), primitives of the last extract
-  bool iso_valid = false, iso_has_colour = false;  // the buffers hold a finished extract on the current mesh; it had a colour source
+  // ---- post-processing: one state block per feature (above)
+  int layout_epoch = 0;     // counts the installations of a mesh / an internal layout: what is kept in the INTERNAL node numbering is rebuilt when it moves
+  nsx::ForceState ff;       // nsx_forces.hip
+  nsx::DiagState diag;      // nsx_diag.hip
+  nsx::ProbeState probe;    // nsx_probe.hip
+  nsx::TracerState tracer;  // nsx_tracer.hip
+  nsx::NodalState nodal;    // nsx_nodal.hip
+  nsx::IsoState iso;        // nsx_iso.hip
   // ---- profiling
   bool prof_on = false;
   std::map<std::string, nsx::ProfEntry> prof;
@@ -488,60 +562,16 @@ void ensure_schedules(nsx_handle *h);  // (re)build the ILU schedules if the ran
 void run_assemble(nsx_handle *h, bool first, int flags);
 void run_dirichlet(nsx_handle *h, int n, const int32_t *dofs, const double *vals);
 
-// flow diagnostics (nsx_diag.hip)
-void diag_mesh_setup(nsx_handle *h);  // with every mesh set-up: which cells this handle counts
-
-// point probes (nsx_probe.hip)
+// post-processing (nsx_diag.hip, nsx_probe.hip; everything else of the family: nsx_post.hpp)
+void diag_mesh_setup(nsx_handle *h);                              // with every mesh set-up: which cells this handle counts
 void probe_mesh_setup(nsx_handle *h, const double *cell_coords);  // with every mesh set-up: vertex 0 of every cell
-void probe_clear(nsx_handle *h);                                  // a new mesh drops the probe set
-// the search of nsx_set_probes on n device points [n][dim]: best [n] (INT32_MAX on entry) -> cells [n] (-1: in no cell), lam SoA [dim+1][n]
-void probe_locate(nsx_handle *h, int n, const double *points, double tol, int32_t *best, int32_t *cells, double *lam);
-constexpr double PROBE_TOL = 1e-12;  // the tolerance of nsxh_pressure_difference
-// lambda[0..DIM] of x in the cell (X0, J^-1): x = X0 + J lambda[1..], lambda[0] = 1 - sum.  A coordinate that is not finite is in no cell.
-template <int DIM>
-__device__ __forceinline__ bool probe_lambda(const double (&Ji)[DIM][DIM], const double (&X0)[DIM], const double *x, double tol, double (&lam)[DIM + 1]) {
-  double l0 = 1.0;
-  bool in = true;
-#pragma unroll
-  for (int k = 0; k < DIM; ++k) {
-    double s = 0.0;
-#pragma unroll
-    for (int d = 0; d < DIM; ++d) s += Ji[k][d] * (x[d] - X0[d]);
-    lam[k + 1] = s;
-    l0 -= s;
-    in = in && s >= -tol;
-  }
-  lam[0] = l0;
-  return in && l0 >= -tol;
+// a new mesh (nsx_set_mesh / nsx_set_mesh_distributed, not a new layout or rank table): every feature drops what its state block says
+inline void post_mesh_changed(nsx_handle *h) {
+  h->probe.mesh_changed();
+  h->tracer.mesh_changed();
+  h->nodal.mesh_changed();
+  h->iso.mesh_changed();
 }
-
-template <int DIM>
-__device__ __forceinline__ void load_cell_map(int n_cells, int cell, const double *__restrict__ geo, const double *__restrict__ x0, double (&Ji)[DIM][DIM],
-                                              double (&X0)[DIM]) {
-#pragma unroll
-  for (int k = 0; k < DIM; ++k) {
-    X0[k] = x0[(size_t)k * n_cells + cell];
-#pragma unroll
-    for (int d = 0; d < DIM; ++d) Ji[k][d] = geo[(size_t)(k * DIM + d) * n_cells + cell];
-  }
-}
-
-// tracer particles (nsx_tracer.hip)
-void tracer_clear(nsx_handle *h);  // a new mesh drops the tracer set and the face-neighbour table
-
-// nodal fields (nsx_nodal.hip)
-void nodal_clear(nsx_handle *h);  // a new mesh drops the patch table and the results
-// planes of nodal_out: the dim^2 entries of Gbar (row-major), then vorticity (3 / 1), Q, strain rate, divergence
-constexpr int nodal_planes(int dim) { return dim * dim + (dim == 3 ? 3 : 1) + 3; }
-inline int nodal_components(int dim, int which) { return which == NSX_FIELD_GRADIENT ? dim * dim : which == NSX_FIELD_VORTICITY ? (dim == 3 ? 3 : 1) : 1; }
-inline int nodal_first_plane(int dim, int which) {
-  int p = 0;
-  for (int f = 0; f < which; ++f) p += nodal_components(dim, f);
-  return p;
-}
-
-// isosurfaces and slices (nsx_iso.hip)
-void iso_clear(nsx_handle *h);  // a new mesh drops the coordinates, the node maps and the result
 
 // sparse (nsx_sparse.hip)
 bool blocked_usable(const nsx_handle *h);                                                   // F->vmult goes through the LDS-staged SpMV

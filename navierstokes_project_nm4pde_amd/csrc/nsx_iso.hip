@@ -13,7 +13,7 @@
 //                 the cell's primitive count (0..4 / 0..16) packed with its exclusive prefix inside the workgroup (prefix << 5 | count: one
 //                 load tells k_iso_emit everything about an empty cell), and the workgroup total.  The counts are small integers, so the
 //                 wave-level prefix is five __ballot masks (one per bit of the count) and popcounts of the lanes below; the waves of a
-//                 workgroup meet in LDS.  Cells the handle does not count (diag_counted == 0: another rank's) count 0.
+//                 workgroup meet in LDS.  Cells the handle does not count (diag.counted == 0: another rank's) count 0.
 //                 Algorithmic bytes: n_cells (1 + 4) + counted cells (4 NP2 + 8 NP2) + 4 workgroups.
 //   k_iso_scan    exclusive prefix sum of the workgroup totals into 64-bit offsets; ONE workgroup that loops over the totals (the bench mesh
 //                 has 963 of them at 256 lanes), shuffle scan inside a wave, LDS across the waves, a 64-bit carry from pass to pass.  Integer
@@ -33,7 +33,7 @@
 
 #include "../host/iso_tables.hpp"
 #include "../host/nodal_patch.hpp"
-#include "nsx_internal.hpp"
+#include "nsx_post.hpp"
 
 #pragma clang fp contract(off)
 
@@ -41,7 +41,7 @@ namespace nsx {
 
 // one nodal scalar source as the kernels see it; kind < 0: none (the colour of a call without one)
 struct IsoSrc {
-  int kind, component, plane;  // plane: NSX_ISO_NODAL: first plane of the field in nodal_out + component
+  int kind, component, plane;  // plane: NSX_ISO_NODAL: first plane of the field in nodal.out + component
   double normal[3];
 };
 
@@ -240,19 +240,6 @@ __global__ __launch_bounds__(256) void k_iso_emit(int n_cells, const int32_t *__
 }
 
 // ------------------------------------------------------------------ host drivers
-void iso_clear(nsx_handle *h) {
-  h->iso_have_coords = false;
-  h->iso_valid = false;
-  h->iso_n = 0;
-  h->iso_map_epoch = h->iso_slot_epoch = -1;
-}
-
-static void iso_check_space(nsx_handle *h, const char *who) {
-  if (!h->have_mesh) NSX_THROW(NSX_ERR_ARG, "%s: nsx_set_tables and nsx_set_mesh first", who);
-  if (!((h->dim == 2 && h->np2 == 6) || (h->dim == 3 && h->np2 == 10)))
-    NSX_THROW(NSX_ERR_UNSUPPORTED, "%s: no isosurface kernel instantiated for dim=%d n_p2=%d (P2/P1 on simplices only)", who, h->dim, h->np2);
-}
-
 // validates one source and translates it for the kernels
 static IsoSrc iso_source(nsx_handle *h, const nsx_iso_source *q, const char *role) {
   IsoSrc r{};
@@ -272,7 +259,7 @@ static IsoSrc iso_source(nsx_handle *h, const nsx_iso_source *q, const char *rol
         NSX_THROW(NSX_ERR_ARG, "nsx_extract_isosurface: %s: nodal field %d (NSX_FIELD_GRADIENT ... NSX_FIELD_DIVERGENCE)", role, q->which);
       if (q->component < 0 || q->component >= nodal_components(dim, q->which))
         NSX_THROW(NSX_ERR_ARG, "nsx_extract_isosurface: %s: component %d of a nodal field with %d", role, q->component, nodal_components(dim, q->which));
-      if (!h->have_patches || !h->nodal_valid) NSX_THROW(NSX_ERR_ARG, "nsx_extract_isosurface: %s: NSX_ISO_NODAL needs nsx_compute_nodal_fields first", role);
+      if (!h->nodal.have_patches || !h->nodal.valid) NSX_THROW(NSX_ERR_ARG, "nsx_extract_isosurface: %s: NSX_ISO_NODAL needs nsx_compute_nodal_fields first", role);
       r.plane = nodal_first_plane(dim, q->which) + q->component;
       break;
     case NSX_ISO_PLANE: {
@@ -303,7 +290,7 @@ static double iso_source_bytes(const IsoSrc &q, int dim) {
 
 // vertex coordinates of the cells, SoA, and the orientation of every cell: by the first extract on a mesh (cells are never renumbered)
 static void iso_ensure_coords(nsx_handle *h) {
-  if (h->iso_have_coords) return;
+  if (h->iso.have_coords) return;
   const int dim = h->dim, nv = dim + 1, nc = h->n_cells;
   if (h->cell_coords_in.size() != (size_t)nc * nv * dim) NSX_THROW(NSX_ERR_ARG, "nsx_extract_isosurface: the handle holds no cell coordinates");
   std::vector<double> x((size_t)nv * dim * nc);
@@ -322,16 +309,15 @@ static void iso_ensure_coords(nsx_handle *h) {
             J[0][2] * (J[1][0] * J[2][1] - J[1][1] * J[2][0]);  // the expression of setup_mesh
     flip[c] = det < 0.0;
   }
-  h->iso_cellx.upload(x, h->stream);
-  h->iso_flip.upload(flip, h->stream);
-  h->iso_have_coords = true;
+  h->iso.cellx.upload(x, h->stream);
+  h->iso.flip.upload(flip, h->stream);
+  h->iso.have_coords = true;
 }
 
 // the maps over the LOCAL nodes in the INTERNAL numbering (cell_n2_h / cell_n1_h): rebuilt when a layout moves the nodes
 static void iso_ensure_maps(nsx_handle *h) {
-  if (h->iso_map_epoch == h->layout_epoch) return;
+  if (h->iso.map_epoch == h->layout_epoch) return;
   const int dim = h->dim, nv = dim + 1, np2 = h->np2, np1 = h->np1, nc = h->n_cells, n_loc = h->N2_loc;
-  constexpr int LI[6] = {0, 1, 2, 0, 1, 2}, LJ[6] = {1, 2, 0, 3, 3, 3};
   std::vector<int32_t> pmap((size_t)2 * n_loc, 0);
   std::vector<double> nx((size_t)dim * n_loc, 0.0);
   for (int n = 0; n < n_loc; ++n) pmap[(size_t)n_loc + n] = -1;
@@ -346,7 +332,7 @@ static void iso_ensure_maps(nsx_handle *h) {
         pmap[(size_t)n_loc + n] = -1;
         for (int d = 0; d < dim; ++d) nx[(size_t)d * n_loc + n] = X[a * dim + d];
       } else {
-        const int i = LI[a - nv], j = LJ[a - nv];
+        const int i = P2_LI[a - nv], j = P2_LJ[a - nv];
         pmap[n] = c1[i];
         pmap[(size_t)n_loc + n] = c1[j];
         for (int d = 0; d < dim; ++d) nx[(size_t)d * n_loc + n] = 0.5 * (X[i * dim + d] + X[j * dim + d]);
@@ -355,24 +341,24 @@ static void iso_ensure_maps(nsx_handle *h) {
   }
   for (size_t k = 0; k < pmap.size(); ++k)
     if (pmap[k] < -1 || pmap[k] >= h->NP_loc) NSX_THROW(NSX_ERR_ARG, "nsx_extract_isosurface: the node map names pressure node %d", pmap[k]);
-  h->iso_pmap.upload(pmap, h->stream);
-  h->iso_nodex.upload(nx, h->stream);
-  h->iso_map_epoch = h->layout_epoch;
+  h->iso.pmap.upload(pmap, h->stream);
+  h->iso.nodex.upload(nx, h->stream);
+  h->iso.map_epoch = h->layout_epoch;
 }
 
-// internal node -> slot of nodal_out, from the layout's node permutation and nodal_slot_of (caller-local owned node -> slot)
+// internal node -> slot of nodal.out, from the layout's node permutation and nodal.slot_of (caller-local owned node -> slot)
 static void iso_ensure_slots(nsx_handle *h) {
-  if (h->iso_slot_epoch == h->layout_epoch) return;
-  const size_t n_slots = (size_t)h->nodal_tiles * NODAL_TILE;
+  if (h->iso.slot_epoch == h->layout_epoch) return;
+  const size_t n_slots = (size_t)h->nodal.tiles * NODAL_TILE;
   std::vector<int32_t> slot((size_t)h->N2_loc, -1);
   for (int n = 0; n < h->N2; ++n) {
     const int32_t caller = h->layout_on ? h->iperm2_h[n] : n;
-    const int32_t s = h->nodal_slot_of[caller];
+    const int32_t s = h->nodal.slot_of[caller];
     if (s < 0 || (size_t)s >= n_slots) NSX_THROW(NSX_ERR_ARG, "nsx_extract_isosurface: node %d has slot %d of the nodal results", caller, s);
     slot[n] = s;
   }
-  h->iso_slot.upload(slot, h->stream);
-  h->iso_slot_epoch = h->layout_epoch;
+  h->iso.slot.upload(slot, h->stream);
+  h->iso.slot_epoch = h->layout_epoch;
 }
 
 static int iso_wg_width() {
@@ -384,34 +370,34 @@ static int iso_wg_width() {
 template <int DIM, int NP2>
 static void launch_iso_front(nsx_handle *h, const IsoSrc &f, const IsoSrc &c, double iso, int wg, int n_wg) {
   const int n_loc = h->N2_loc, nc = h->n_cells;
-  const size_t n_slots = (size_t)h->nodal_tiles * NODAL_TILE;
+  const size_t n_slots = (size_t)h->nodal.tiles * NODAL_TILE;
   {
     LaunchScope ls(h, "iso_scalar", (double)n_loc * (16.0 + iso_source_bytes(f, DIM) + iso_source_bytes(c, DIM)));
-    hipLaunchKernelGGL((k_iso_scalar<DIM>), dim3(cdiv(n_loc, 256)), dim3(256), 0, h->stream, n_loc, f, c, h->sol.p, h->off_p, h->iso_pmap.p, h->iso_nodex.p,
-                       h->iso_slot.p, h->nodal_out.p, n_slots, h->iso_s.p);
+    hipLaunchKernelGGL((k_iso_scalar<DIM>), dim3(cdiv(n_loc, 256)), dim3(256), 0, h->stream, n_loc, f, c, h->sol.p, h->off_p, h->iso.pmap.p, h->iso.nodex.p,
+                       h->iso.slot.p, h->nodal.out.p, n_slots, h->iso.s.p);
   }
   {
-    LaunchScope ls(h, "iso_count", 5.0 * nc + (double)h->diag_n_counted * 12.0 * NP2 + 4.0 * n_wg);
-    hipLaunchKernelGGL((k_iso_count<DIM, NP2>), dim3(n_wg), dim3(wg), 0, h->stream, nc, h->diag_counted.p, h->cell_n2.p, h->iso_s.p, iso, h->iso_pack.p,
-                       h->iso_wg_tot.p);
+    LaunchScope ls(h, "iso_count", 5.0 * nc + (double)h->diag.n_counted * 12.0 * NP2 + 4.0 * n_wg);
+    hipLaunchKernelGGL((k_iso_count<DIM, NP2>), dim3(n_wg), dim3(wg), 0, h->stream, nc, h->diag.counted.p, h->cell_n2.p, h->iso.s.p, iso, h->iso.pack.p,
+                       h->iso.wg_tot.p);
   }
   {
     LaunchScope ls(h, "iso_scan", 4.0 * n_wg + 8.0 * (n_wg + 1));
-    hipLaunchKernelGGL(k_iso_scan, dim3(1), dim3(wg), 0, h->stream, n_wg, h->iso_wg_tot.p, h->iso_wg_off.p);
+    hipLaunchKernelGGL(k_iso_scan, dim3(1), dim3(wg), 0, h->stream, n_wg, h->iso.wg_tot.p, h->iso.wg_off.p);
   }
 }
 
 template <int DIM, int NP2>
 static void launch_iso_emit(nsx_handle *h, bool colour, double iso, int wg, int n_wg, int64_t n) {
   const int nc = h->n_cells;
-  const double active = (double)std::min<int64_t>(h->diag_n_counted, n);
+  const double active = (double)std::min<int64_t>(h->diag.n_counted, n);
   LaunchScope ls(h, "iso_emit", 4.0 * nc + 8.0 * n_wg + active * (20.0 * NP2 + 8.0 * (DIM + 1) * DIM + 1.0) + (double)n * (8.0 * DIM * DIM + 8.0 * DIM + 4.0));
-  hipLaunchKernelGGL((k_iso_emit<DIM, NP2>), dim3(n_wg), dim3(wg), 0, h->stream, nc, h->cell_n2.p, h->iso_s.p, colour ? h->iso_s.p + h->N2_loc : nullptr, iso,
-                     h->iso_pack.p, h->iso_wg_off.p, h->iso_cellx.p, h->iso_flip.p, (long long)h->iso_cap, h->iso_pts.p, h->iso_col.p, h->iso_cells.p);
+  hipLaunchKernelGGL((k_iso_emit<DIM, NP2>), dim3(n_wg), dim3(wg), 0, h->stream, nc, h->cell_n2.p, h->iso.s.p, colour ? h->iso.s.p + h->N2_loc : nullptr, iso,
+                     h->iso.pack.p, h->iso.wg_off.p, h->iso.cellx.p, h->iso.flip.p, (long long)h->iso.cap, h->iso.pts.p, h->iso.col.p, h->iso.cells.p);
 }
 
 static void extract_isosurface(nsx_handle *h, const nsx_iso_source *field, double isovalue, const nsx_iso_source *colour, int64_t *n_primitives) {
-  iso_check_space(h, "nsx_extract_isosurface");
+  post_check_space(h, "nsx_extract_isosurface");
   if (!field || !n_primitives) NSX_THROW(NSX_ERR_ARG, "nsx_extract_isosurface: null field / n_primitives");
   if (!h->sol.p || h->sol.n < (size_t)h->len_blk) NSX_THROW(NSX_ERR_ARG, "nsx_extract_isosurface: the handle holds no state yet");
   if (!std::isfinite(isovalue)) NSX_THROW(NSX_ERR_ARG, "nsx_extract_isosurface: the isovalue is not finite");
@@ -424,27 +410,27 @@ static void extract_isosurface(nsx_handle *h, const nsx_iso_source *field, doubl
   iso_ensure_coords(h);
   iso_ensure_maps(h);
   if (f.kind == NSX_ISO_NODAL || c.kind == NSX_ISO_NODAL) iso_ensure_slots(h);
-  if (h->iso_s.n < (size_t)2 * h->N2_loc) h->iso_s.alloc((size_t)2 * h->N2_loc);
-  if (h->iso_pack.n < (size_t)nc) h->iso_pack.alloc(nc);
-  if (h->iso_wg_tot.n < (size_t)n_wg) h->iso_wg_tot.alloc(n_wg);
-  if (h->iso_wg_off.n < (size_t)n_wg + 1) h->iso_wg_off.alloc((size_t)n_wg + 1);
+  if (h->iso.s.n < (size_t)2 * h->N2_loc) h->iso.s.alloc((size_t)2 * h->N2_loc);
+  if (h->iso.pack.n < (size_t)nc) h->iso.pack.alloc(nc);
+  if (h->iso.wg_tot.n < (size_t)n_wg) h->iso.wg_tot.alloc(n_wg);
+  if (h->iso.wg_off.n < (size_t)n_wg + 1) h->iso.wg_off.alloc((size_t)n_wg + 1);
   if (dim == 2) launch_iso_front<2, 6>(h, f, c, isovalue, wg, n_wg);
   else launch_iso_front<3, 10>(h, f, c, isovalue, wg, n_wg);
   HIP_CHECK(hipGetLastError());
   long long total = 0;
-  HIP_CHECK(hipMemcpyAsync(&total, h->iso_wg_off.p + n_wg, sizeof(total), hipMemcpyDeviceToHost, h->stream));
+  HIP_CHECK(hipMemcpyAsync(&total, h->iso.wg_off.p + n_wg, sizeof(total), hipMemcpyDeviceToHost, h->stream));
   HIP_CHECK(hipStreamSynchronize(h->stream));
   if (total < 0 || total > (long long)nc * (dim == 3 ? ISO_MAX_PRIMS_3D : ISO_MAX_PRIMS_2D))
     NSX_THROW(NSX_ERR_NUMERIC, "nsx_extract_isosurface: the scan returned %lld primitives for %d cells", total, nc);
   if (total > (long long)INT32_MAX) NSX_THROW(NSX_ERR_UNSUPPORTED, "nsx_extract_isosurface: %lld primitives (more than 2^31 - 1)", total);
   // from here on the earlier result is given up
-  h->iso_valid = false;
-  if (total > h->iso_cap || !h->iso_pts.p) {  // grow, never shrink
+  h->iso.valid = false;
+  if (total > h->iso.cap || !h->iso.pts.p) {  // grow, never shrink
     const int64_t cap = std::max<int64_t>(total, 1);
-    h->iso_pts.alloc((size_t)dim * dim * cap);
-    h->iso_col.alloc((size_t)dim * cap);
-    h->iso_cells.alloc((size_t)cap);
-    h->iso_cap = cap;
+    h->iso.pts.alloc((size_t)dim * dim * cap);
+    h->iso.col.alloc((size_t)dim * cap);
+    h->iso.cells.alloc((size_t)cap);
+    h->iso.cap = cap;
   }
   if (total > 0) {
     if (dim == 2) launch_iso_emit<2, 6>(h, c.kind >= 0, isovalue, wg, n_wg, total);
@@ -452,26 +438,26 @@ static void extract_isosurface(nsx_handle *h, const nsx_iso_source *field, doubl
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(h->stream));
   }
-  h->iso_n = total;
-  h->iso_has_colour = c.kind >= 0;
-  h->iso_valid = true;
+  h->iso.n = total;
+  h->iso.has_colour = c.kind >= 0;
+  h->iso.valid = true;
   *n_primitives = total;
 }
 
 static void get_isosurface(nsx_handle *h, double *points, double *colour, int32_t *cells) {
-  iso_check_space(h, "nsx_get_isosurface");
-  if (!h->iso_valid) NSX_THROW(NSX_ERR_ARG, "nsx_get_isosurface: nsx_extract_isosurface first");
-  if (colour && !h->iso_has_colour) NSX_THROW(NSX_ERR_ARG, "nsx_get_isosurface: the last nsx_extract_isosurface had no colour source");
+  post_check_space(h, "nsx_get_isosurface");
+  if (!h->iso.valid) NSX_THROW(NSX_ERR_ARG, "nsx_get_isosurface: nsx_extract_isosurface first");
+  if (colour && !h->iso.has_colour) NSX_THROW(NSX_ERR_ARG, "nsx_get_isosurface: the last nsx_extract_isosurface had no colour source");
   const int dim = h->dim;
-  const size_t n = (size_t)h->iso_n, cap = (size_t)h->iso_cap;
+  const size_t n = (size_t)h->iso.n, cap = (size_t)h->iso.cap;
   if (n == 0) return;
   HIP_CHECK(hipSetDevice(h->prm.device));
   const int np = (points ? dim * dim : 0), ncol = (colour ? dim : 0);
   std::vector<double> v((size_t)(np + ncol) * n);
-  for (int p = 0; p < np; ++p) HIP_CHECK(hipMemcpyAsync(v.data() + (size_t)p * n, h->iso_pts.p + (size_t)p * cap, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  for (int p = 0; p < np; ++p) HIP_CHECK(hipMemcpyAsync(v.data() + (size_t)p * n, h->iso.pts.p + (size_t)p * cap, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   for (int p = 0; p < ncol; ++p)
-    HIP_CHECK(hipMemcpyAsync(v.data() + (size_t)(np + p) * n, h->iso_col.p + (size_t)p * cap, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (cells) HIP_CHECK(hipMemcpyAsync(cells, h->iso_cells.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_CHECK(hipMemcpyAsync(v.data() + (size_t)(np + p) * n, h->iso.col.p + (size_t)p * cap, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (cells) HIP_CHECK(hipMemcpyAsync(cells, h->iso.cells.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
   HIP_CHECK(hipStreamSynchronize(h->stream));
   for (size_t i = 0; i < n; ++i) {
     for (int p = 0; p < np; ++p) points[i * np + p] = v[(size_t)p * n + i];
@@ -484,25 +470,15 @@ static void get_isosurface(nsx_handle *h, double *points, double *colour, int32_
 extern "C" {
 
 int nsx_extract_isosurface(nsx_handle *h, const nsx_iso_source *field, double isovalue, const nsx_iso_source *colour, int64_t *n_primitives) {
-  if (!h) return NSX_ERR_ARG;
-  try {
-    nsx::extract_isosurface(h, field, isovalue, colour, n_primitives);
-  } catch (const nsx::Error &e) {
-    h->err = e.msg;
-    return e.code;
-  }
-  return NSX_OK;
+  NSX_TRY(h)
+  nsx::extract_isosurface(h, field, isovalue, colour, n_primitives);
+  NSX_CATCH(h)
 }
 
 int nsx_get_isosurface(nsx_handle *h, double *points, double *colour, int32_t *cells) {
-  if (!h) return NSX_ERR_ARG;
-  try {
-    nsx::get_isosurface(h, points, colour, cells);
-  } catch (const nsx::Error &e) {
-    h->err = e.msg;
-    return e.code;
-  }
-  return NSX_OK;
+  NSX_TRY(h)
+  nsx::get_isosurface(h, points, colour, cells);
+  NSX_CATCH(h)
 }
 
 }  // extern "C"

@@ -1865,43 +1865,39 @@ extern "C" int nsx_gram_schmidt_sweeps(nsx_handle *h, int n, int split, int gap,
   if (!h || !vectors || !coeffs || !norms2 || !norms2_before || !normalized || n < 1 || m < 1 || m > 30 || split < 0 || split > n || gap < 0 ||
       (flags & ~3) != 0 || (split == n && gap != 0))
     return NSX_ERR_ARG;
-  try {
-    HIP_CHECK(hipSetDevice(h->prm.device));
-    const size_t len = (size_t)n + gap;
-    std::vector<nsx::DevBuf<double>> v(m);
-    for (int k = 0; k < m; ++k) v[k].upload(vectors + (size_t)k * len, len, h->stream);
-    if (!h->mgs.ls_gram.p) {
-      h->mgs.ls_gram.alloc(4 * 1024);
-      h->mgs.ls_gram.zero(h->stream);
-    }
-    const bool consider = (flags & 1) != 0, normalize = (flags & 2) == 0;
-    const double keep = h->mgs.guard_override;
-    h->mgs.guard_override = norm_guard;
-    try {
-      const nsx::Span sp(n, split, gap);
-      nsx::v_dot(h, sp, v[0].p, v[0].p, 40);
-      norms2[0] = norms2_before[0] = nsx::read_scalar(h, 40);
-      normalized[0] = 0;
-      nsx::v_scale(h, sp, v[0].p, 1.0 / std::sqrt(norms2[0]));
-      for (int k = 1; k < m; ++k) {
-        double *vs[32], out[34];
-        for (int i = 0; i < k; ++i) vs[i] = v[i].p;
-        const bool done = nsx::v_mgs(h, sp, v[k].p, k, vs, 8, normalize, out, nullptr, consider, h->mgs.ls_gram.p);
-        for (int i = 0; i < k; ++i) coeffs[(size_t)k * m + i] = out[i];
-        norms2[k] = out[k];
-        norms2_before[k] = consider ? out[k + 1] : 0.0;
-        normalized[k] = done ? 1 : 0;
-        if (!done && out[k] > 0.0) nsx::v_scale(h, sp, v[k].p, 1.0 / std::sqrt(out[k]));
-      }
-    } catch (...) {
-      h->mgs.guard_override = keep;
-      throw;
-    }
-    h->mgs.guard_override = keep;
-    for (int k = 0; k < m; ++k) v[k].download(vectors + (size_t)k * len, len, h->stream);
-  } catch (const nsx::Error &e) {
-    h->err = e.msg;
-    return e.code;
+  NSX_TRY(h)
+  HIP_CHECK(hipSetDevice(h->prm.device));
+  const size_t len = (size_t)n + gap;
+  std::vector<nsx::DevBuf<double>> v(m);
+  for (int k = 0; k < m; ++k) v[k].upload(vectors + (size_t)k * len, len, h->stream);
+  if (!h->mgs.ls_gram.p) {
+    h->mgs.ls_gram.alloc(4 * 1024);
+    h->mgs.ls_gram.zero(h->stream);
   }
-  return NSX_OK;
+  const bool consider = (flags & 1) != 0, normalize = (flags & 2) == 0;
+  const double keep = h->mgs.guard_override;
+  h->mgs.guard_override = norm_guard;
+  try {
+    const nsx::Span sp(n, split, gap);
+    nsx::v_dot(h, sp, v[0].p, v[0].p, 40);
+    norms2[0] = norms2_before[0] = nsx::read_scalar(h, 40);
+    normalized[0] = 0;
+    nsx::v_scale(h, sp, v[0].p, 1.0 / std::sqrt(norms2[0]));
+    for (int k = 1; k < m; ++k) {
+      double *vs[32], out[34];
+      for (int i = 0; i < k; ++i) vs[i] = v[i].p;
+      const bool done = nsx::v_mgs(h, sp, v[k].p, k, vs, 8, normalize, out, nullptr, consider, h->mgs.ls_gram.p);
+      for (int i = 0; i < k; ++i) coeffs[(size_t)k * m + i] = out[i];
+      norms2[k] = out[k];
+      norms2_before[k] = consider ? out[k + 1] : 0.0;
+      normalized[k] = done ? 1 : 0;
+      if (!done && out[k] > 0.0) nsx::v_scale(h, sp, v[k].p, 1.0 / std::sqrt(out[k]));
+    }
+  } catch (...) {
+    h->mgs.guard_override = keep;
+    throw;
+  }
+  h->mgs.guard_override = keep;
+  for (int k = 0; k < m; ++k) v[k].download(vectors + (size_t)k * len, len, h->stream);
+  NSX_CATCH(h)
 }

@@ -25,7 +25,7 @@
 #include <cmath>
 
 #include "../host/nodal_patch.hpp"
-#include "nsx_internal.hpp"
+#include "nsx_post.hpp"
 
 namespace nsx {
 
@@ -36,7 +36,6 @@ __global__ __launch_bounds__(64) void k_nodal_fields(const int32_t *__restrict__
                                                      const int32_t *__restrict__ cell_n2, const double *__restrict__ geo,
                                                      const double *__restrict__ sol, double *__restrict__ out) {
   constexpr int NV = DIM + 1;
-  constexpr int LI[6] = {0, 1, 2, 0, 1, 2}, LJ[6] = {1, 2, 0, 3, 3, 3};
   constexpr double REF_VOL = DIM == 3 ? 1.0 / 6.0 : 0.5;
   const int lane = threadIdx.x;
   const size_t n_slots = (size_t)gridDim.x * 64, slot = (size_t)blockIdx.x * 64 + lane;
@@ -61,19 +60,11 @@ __global__ __launch_bounds__(64) void k_nodal_fields(const int32_t *__restrict__
     for (int i = 0; i < DIM; ++i)
 #pragma unroll
       for (int q = 0; q < DIM; ++q) H[i][q] = 0.0;
-    // as k_probe_eval: g[m] = dN_a / d lambda_m, dN_a / d xi_q = g[q + 1] - g[0], H = sum_a U_a (x) grad_ref N_a
+    // g[m] = dN_a / d lambda_m (p2_shape, nsx_post.hpp), dN_a / d xi_q = g[q + 1] - g[0], H = sum_a U_a (x) grad_ref N_a
 #pragma unroll
     for (int a = 0; a < NP2; ++a) {
-      double g[NV];
-#pragma unroll
-      for (int m = 0; m < NV; ++m) g[m] = 0.0;
-      if (a < NV) {
-        g[a] = 4.0 * lam[a] - 1.0;
-      } else {
-        const int i = LI[a - NV], j = LJ[a - NV];
-        g[i] = 4.0 * lam[j];
-        g[j] = 4.0 * lam[i];
-      }
+      double g[NV], n;  // n: not computed
+      p2_shape<DIM, false, true>(a, lam, n, g);
       const int node = cell_n2[(size_t)a * n_cells + cell];
 #pragma unroll
       for (int i = 0; i < DIM; ++i) {
@@ -84,18 +75,8 @@ __global__ __launch_bounds__(64) void k_nodal_fields(const int32_t *__restrict__
     }
     const double vol = geo[(size_t)(DIM * DIM) * n_cells + cell] * REF_VOL;
 #pragma unroll
-    for (int j = 0; j < DIM; ++j) {
-      double Jc[DIM];  // column j of J^-1
-#pragma unroll
-      for (int q = 0; q < DIM; ++q) Jc[q] = geo[(size_t)(q * DIM + j) * n_cells + cell];
-#pragma unroll
-      for (int i = 0; i < DIM; ++i) {
-        double s = 0.0;
-#pragma unroll
-        for (int q = 0; q < DIM; ++q) s += H[i][q] * Jc[q];
-        num[i][j] += vol * s;
-      }
-    }
+    for (int j = 0; j < DIM; ++j)
+      push_forward_col<DIM>(n_cells, cell, geo, H, j, [&](int i, double s) { num[i][j] += vol * s; });
     den += vol;
   }
   double G[DIM][DIM];
@@ -136,21 +117,9 @@ __global__ __launch_bounds__(64) void k_nodal_fields(const int32_t *__restrict__
 }
 
 // ------------------------------------------------------------------ host drivers
-void nodal_clear(nsx_handle *h) {
-  h->have_patches = false;
-  h->nodal_valid = false;
-  h->nodal_slot_of.clear();
-}
-
-static void nodal_check_space(nsx_handle *h, const char *who) {
-  if (!h->have_mesh) NSX_THROW(NSX_ERR_ARG, "%s: nsx_set_tables and nsx_set_mesh first", who);
-  if (!((h->dim == 2 && h->np2 == 6) || (h->dim == 3 && h->np2 == 10)))
-    NSX_THROW(NSX_ERR_UNSUPPORTED, "%s: no nodal-field kernel instantiated for dim=%d n_p2=%d (P2/P1 on simplices only)", who, h->dim, h->np2);
-}
-
 // the patch table of the current mesh, from the connectivity in the CALLER's node and cell numbering: it outlives a new layout / rank table
 static void ensure_patches(nsx_handle *h) {
-  if (h->have_patches) return;
+  if (h->nodal.have_patches) return;
   if (h->cell_n2_in.size() != (size_t)h->n_cells * h->np2) NSX_THROW(NSX_ERR_ARG, "nsx_compute_nodal_fields: the handle holds no connectivity");
   NodalPatches t;
   if (build_nodal_patches(h->n_cells, h->np2, h->cell_n2_in.data(), h->N2, t) != 0 || t.n_tiles != cdiv(h->N2, NODAL_TILE))
@@ -158,43 +127,43 @@ static void ensure_patches(nsx_handle *h) {
   for (int32_t e : t.ent)
     if (e < -1 || (e >> NODAL_LOCAL_BITS) >= h->n_cells || (e >= 0 && (e & ((1 << NODAL_LOCAL_BITS) - 1)) >= h->np2))
       NSX_THROW(NSX_ERR_ARG, "nsx_compute_nodal_fields: the node patch table names entry %d", e);
-  h->nodal_tile_ptr.upload(t.tile_ptr, h->stream);
-  h->nodal_ent.upload(t.ent, h->stream);
-  h->nodal_out.alloc((size_t)nodal_planes(h->dim) * t.n_tiles * NODAL_TILE);
-  h->nodal_slot_of = std::move(t.slot_of);
-  h->nodal_tiles = t.n_tiles;
-  h->nodal_entries = (int64_t)t.ent.size();
-  h->have_patches = true;
+  h->nodal.tile_ptr.upload(t.tile_ptr, h->stream);
+  h->nodal.ent.upload(t.ent, h->stream);
+  h->nodal.out.alloc((size_t)nodal_planes(h->dim) * t.n_tiles * NODAL_TILE);
+  h->nodal.slot_of = std::move(t.slot_of);
+  h->nodal.tiles = t.n_tiles;
+  h->nodal.entries = (int64_t)t.ent.size();
+  h->nodal.have_patches = true;
 }
 
 template <int DIM, int NP2>
 static void launch_nodal(nsx_handle *h) {
-  const double n_slots = (double)h->nodal_tiles * NODAL_TILE;
-  const double bytes = 8.0 * DIM * h->N2_loc + (double)h->n_cells * (4.0 * NP2 + 8.0 * (DIM * DIM + 1)) + 4.0 * (double)h->nodal_entries +
-                       4.0 * (h->nodal_tiles + 1) + 8.0 * nodal_planes(DIM) * n_slots;
+  const double n_slots = (double)h->nodal.tiles * NODAL_TILE;
+  const double bytes = 8.0 * DIM * h->N2_loc + (double)h->n_cells * (4.0 * NP2 + 8.0 * (DIM * DIM + 1)) + 4.0 * (double)h->nodal.entries +
+                       4.0 * (h->nodal.tiles + 1) + 8.0 * nodal_planes(DIM) * n_slots;
   LaunchScope ls(h, "nodal_fields", bytes);
-  hipLaunchKernelGGL((k_nodal_fields<DIM, NP2>), dim3(h->nodal_tiles), dim3(64), 0, h->stream, h->nodal_tile_ptr.p, h->nodal_ent.p, h->n_cells, h->cell_n2.p,
-                     h->geo.p, h->sol.p, h->nodal_out.p);
+  hipLaunchKernelGGL((k_nodal_fields<DIM, NP2>), dim3(h->nodal.tiles), dim3(64), 0, h->stream, h->nodal.tile_ptr.p, h->nodal.ent.p, h->n_cells, h->cell_n2.p,
+                     h->geo.p, h->sol.p, h->nodal.out.p);
 }
 
 static void compute_nodal_fields(nsx_handle *h) {
-  nodal_check_space(h, "nsx_compute_nodal_fields");
+  post_check_space(h, "nsx_compute_nodal_fields");
   if (!h->sol.p || h->sol.n < (size_t)h->len_blk) NSX_THROW(NSX_ERR_ARG, "nsx_compute_nodal_fields: the handle holds no state yet");
   HIP_CHECK(hipSetDevice(h->prm.device));
   ensure_patches(h);
-  h->nodal_valid = false;  // a failure below leaves no results
-  if (h->nodal_tiles > 0) {
+  h->nodal.valid = false;  // a failure below leaves no results
+  if (h->nodal.tiles > 0) {
     if (h->dim == 2) launch_nodal<2, 6>(h);
     else launch_nodal<3, 10>(h);
     HIP_CHECK(hipGetLastError());
   }
   HIP_CHECK(hipStreamSynchronize(h->stream));
-  h->nodal_valid = true;
+  h->nodal.valid = true;
 }
 
 static void nodal_check_get(nsx_handle *h, const char *who, int which) {
-  nodal_check_space(h, who);
-  if (!h->have_patches || !h->nodal_valid) NSX_THROW(NSX_ERR_ARG, "%s: nsx_compute_nodal_fields first", who);
+  post_check_space(h, who);
+  if (!h->nodal.have_patches || !h->nodal.valid) NSX_THROW(NSX_ERR_ARG, "%s: nsx_compute_nodal_fields first", who);
   if (which < 0 || which >= NSX_FIELD_COUNT) NSX_THROW(NSX_ERR_ARG, "%s: field %d (NSX_FIELD_GRADIENT ... NSX_FIELD_DIVERGENCE)", who, which);
 }
 
@@ -203,12 +172,12 @@ static void get_nodal_field(nsx_handle *h, int which, double *values) {
   if (!values) NSX_THROW(NSX_ERR_ARG, "nsx_get_nodal_field: null values");
   HIP_CHECK(hipSetDevice(h->prm.device));
   const int nc = nodal_components(h->dim, which);
-  const size_t n_slots = (size_t)h->nodal_tiles * NODAL_TILE;
+  const size_t n_slots = (size_t)h->nodal.tiles * NODAL_TILE;
   std::vector<double> v((size_t)nc * n_slots);
-  if (!v.empty()) HIP_CHECK(hipMemcpyAsync(v.data(), h->nodal_out.p + (size_t)nodal_first_plane(h->dim, which) * n_slots, v.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (!v.empty()) HIP_CHECK(hipMemcpyAsync(v.data(), h->nodal.out.p + (size_t)nodal_first_plane(h->dim, which) * n_slots, v.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIP_CHECK(hipStreamSynchronize(h->stream));
   for (int i = 0; i < h->N2; ++i) {  // caller-local node i = global node goff_u + i
-    const size_t s = (size_t)h->nodal_slot_of[i];
+    const size_t s = (size_t)h->nodal.slot_of[i];
     for (int k = 0; k < nc; ++k) values[((size_t)h->goff_u + i) * nc + k] = v[(size_t)k * n_slots + s];
   }
 }
@@ -218,38 +187,23 @@ static void get_nodal_field(nsx_handle *h, int which, double *values) {
 extern "C" {
 
 int nsx_compute_nodal_fields(nsx_handle *h) {
-  if (!h) return NSX_ERR_ARG;
-  try {
-    nsx::compute_nodal_fields(h);
-  } catch (const nsx::Error &e) {
-    h->err = e.msg;
-    return e.code;
-  }
-  return NSX_OK;
+  NSX_TRY(h)
+  nsx::compute_nodal_fields(h);
+  NSX_CATCH(h)
 }
 
 int nsx_nodal_field_components(nsx_handle *h, int which, int *n_components) {
-  if (!h) return NSX_ERR_ARG;
-  try {
-    nsx::nodal_check_get(h, "nsx_nodal_field_components", which);
-    if (!n_components) NSX_THROW(NSX_ERR_ARG, "nsx_nodal_field_components: null n_components");
-    *n_components = nsx::nodal_components(h->dim, which);
-  } catch (const nsx::Error &e) {
-    h->err = e.msg;
-    return e.code;
-  }
-  return NSX_OK;
+  NSX_TRY(h)
+  nsx::nodal_check_get(h, "nsx_nodal_field_components", which);
+  if (!n_components) NSX_THROW(NSX_ERR_ARG, "nsx_nodal_field_components: null n_components");
+  *n_components = nsx::nodal_components(h->dim, which);
+  NSX_CATCH(h)
 }
 
 int nsx_get_nodal_field(nsx_handle *h, int which, double *values) {
-  if (!h) return NSX_ERR_ARG;
-  try {
-    nsx::get_nodal_field(h, which, values);
-  } catch (const nsx::Error &e) {
-    h->err = e.msg;
-    return e.code;
-  }
-  return NSX_OK;
+  NSX_TRY(h)
+  nsx::get_nodal_field(h, which, values);
+  NSX_CATCH(h)
 }
 
 }  // extern "C"

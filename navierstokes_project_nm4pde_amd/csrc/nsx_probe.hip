@@ -4,7 +4,7 @@
 //                                               rank, then a reduce); the host restatement is nsxh_pressure_difference (host/frontend.cpp)
 // The reference searches the mesh at every call.  Here the search is set-up (nsx_set_probes) and the per-step call (nsx_eval_probes) only
 // gathers: everything it needs already sits on the device -- cell_n2, cell_n1, geo (J^-1) and the ghosted `solution`; the mesh set-up adds
-// vertex 0 of every cell (cell_x0).
+// vertex 0 of every cell (probe.cell_x0).
 //
 //   k_probe_locate  one CELL PER LANE, one wave per workgroup, as the cell kernels: a lane loads X0 and J^-1 of its cell once and walks ALL
 //                   points, staged in LDS in tiles of PROBE_TILE, so one pass over the cells serves every point.  A point lies in a cell
@@ -21,7 +21,7 @@
 #include <algorithm>
 #include <cmath>
 
-#include "nsx_internal.hpp"
+#include "nsx_post.hpp"
 
 namespace nsx {
 
@@ -29,7 +29,7 @@ constexpr int PROBE_TILE = 64;        // points staged in LDS at a time
 constexpr int PROBE_MAX = 65536;
 constexpr int PROBE_RANK_BITS = 48;   // ranks per double of the owner collective
 
-// best[p] starts at INT32_MAX.  counted: the cells this handle searches (all of them on one process; diag_counted in a distributed run).
+// best[p] starts at INT32_MAX.  counted: the cells this handle searches (all of them on one process; diag.counted in a distributed run).
 template <int DIM>
 __global__ __launch_bounds__(64) void k_probe_locate(int n_cells, const uint8_t *__restrict__ counted, const double *__restrict__ geo,
                                                      const double *__restrict__ x0, int n_points, const double *__restrict__ points, double tol,
@@ -78,10 +78,8 @@ __global__ __launch_bounds__(64) void k_probe_finish(int n_cells, const double *
   for (int k = 0; k <= DIM; ++k) lam_out[(size_t)k * n_points + p] = lam[k];
 }
 
-// P2 shape functions in barycentric form, FESystem's local order: vertices lambda_a (2 lambda_a - 1), then the lines 4 lambda_i lambda_j in the
-// front-end's line order {0,1},{1,2},{2,0}[,{0,3},{1,3},{2,3}].  g[m] = dN_a / d lambda_m; the reference coordinates are xi_k = lambda_k
-// (k = 1..DIM) with lambda_0 = 1 - sum xi, so dN_a / d xi_k = g[k] - g[0].  Everything is unrolled: lam, g, u and H are indexed statically
-// and stay in registers; no table is read, so nothing is hoisted into SGPRs (the trap described above k_cell_diag does not arise).
+// The shape functions and the push-forward are p2_shape / push_forward_col (nsx_post.hpp).  Everything is unrolled: lam, g, u and H are
+// indexed statically and stay in registers.
 // out planes: [0, DIM) velocity, [DIM] pressure, [DIM + 1 + i * DIM + j] d_j u_i.
 template <int DIM, int NP2>
 __global__ __launch_bounds__(64) void k_probe_eval(int n_points, const int32_t *__restrict__ cells, const double *__restrict__ lam_in, int n_cells,
@@ -89,7 +87,6 @@ __global__ __launch_bounds__(64) void k_probe_eval(int n_points, const int32_t *
                                                    const double *__restrict__ geo, const double *__restrict__ sol, int off_p,
                                                    double *__restrict__ out) {
   constexpr int NV = DIM + 1, NOUT = DIM + 1 + DIM * DIM;
-  constexpr int LI[6] = {0, 1, 2, 0, 1, 2}, LJ[6] = {1, 2, 0, 3, 3, 3};
   const int p = blockIdx.x * 64 + threadIdx.x;
   if (p >= n_points) return;
   const int cell = cells[p];
@@ -113,17 +110,7 @@ __global__ __launch_bounds__(64) void k_probe_eval(int n_points, const int32_t *
 #pragma unroll
   for (int a = 0; a < NP2; ++a) {
     double g[NV], n;
-#pragma unroll
-    for (int m = 0; m < NV; ++m) g[m] = 0.0;
-    if (a < NV) {
-      n = lam[a] * (2.0 * lam[a] - 1.0);
-      g[a] = 4.0 * lam[a] - 1.0;
-    } else {
-      const int i = LI[a - NV], j = LJ[a - NV];
-      n = 4.0 * lam[i] * lam[j];
-      g[i] = 4.0 * lam[j];
-      g[j] = 4.0 * lam[i];
-    }
+    p2_shape<DIM, true, true>(a, lam, n, g);
     const int node = cell_n2[(size_t)a * n_cells + cell];
 #pragma unroll
     for (int i = 0; i < DIM; ++i) {
@@ -138,50 +125,27 @@ __global__ __launch_bounds__(64) void k_probe_eval(int n_points, const int32_t *
   for (int i = 0; i < DIM; ++i) o[(size_t)i * n_points] = u[i];
   o[(size_t)DIM * n_points] = pr;
 #pragma unroll
-  for (int j = 0; j < DIM; ++j) {
-    double Jc[DIM];  // column j of J^-1
-#pragma unroll
-    for (int k = 0; k < DIM; ++k) Jc[k] = geo[(size_t)(k * DIM + j) * n_cells + cell];
-#pragma unroll
-    for (int i = 0; i < DIM; ++i) {
-      double s = 0.0;
-#pragma unroll
-      for (int k = 0; k < DIM; ++k) s += H[i][k] * Jc[k];
-      o[(size_t)(DIM + 1 + i * DIM + j) * n_points] = s;
-    }
-  }
+  for (int j = 0; j < DIM; ++j)
+    push_forward_col<DIM>(n_cells, cell, geo, H, j, [&](int i, double s) { o[(size_t)(DIM + 1 + i * DIM + j) * n_points] = s; });
 }
 
 // ------------------------------------------------------------------ host drivers
-static void probe_check_space(nsx_handle *h) {
-  if (!h->have_mesh) NSX_THROW(NSX_ERR_ARG, "nsx_set_tables and nsx_set_mesh first");
-  if (!((h->dim == 2 && h->np2 == 6) || (h->dim == 3 && h->np2 == 10)))
-    NSX_THROW(NSX_ERR_UNSUPPORTED, "no probe kernel instantiated for dim=%d n_p2=%d (P2/P1 on simplices only)", h->dim, h->np2);
-}
-
 void probe_mesh_setup(nsx_handle *h, const double *cell_coords) {
   const int dim = h->dim, nv = dim + 1, n_cells = h->n_cells;
   std::vector<double> x0((size_t)dim * n_cells);
   for (int c = 0; c < n_cells; ++c)
     for (int d = 0; d < dim; ++d) x0[(size_t)d * n_cells + c] = cell_coords[(size_t)c * nv * dim + d];
-  h->cell_x0.upload(x0, h->stream);
-}
-
-void probe_clear(nsx_handle *h) {
-  h->probe_n = 0;
-  h->probe_cells_h.clear();
-  h->probe_owner_h.clear();
-  h->probe_lambda_h.clear();
+  h->probe.cell_x0.upload(x0, h->stream);
 }
 
 template <int DIM>
 static void launch_locate(nsx_handle *h, int n, const double *points, double tol, int32_t *best, int32_t *cells, double *lam) {
   {
     LaunchScope ls(h, "probe_locate", 8.0 * (DIM * DIM + DIM) * h->n_cells);
-    hipLaunchKernelGGL((k_probe_locate<DIM>), dim3(cdiv(h->n_cells, 64)), dim3(64), 0, h->stream, h->n_cells, h->diag_counted.p, h->geo.p, h->cell_x0.p, n,
+    hipLaunchKernelGGL((k_probe_locate<DIM>), dim3(cdiv(h->n_cells, 64)), dim3(64), 0, h->stream, h->n_cells, h->diag.counted.p, h->geo.p, h->probe.cell_x0.p, n,
                        points, tol, best);
   }
-  hipLaunchKernelGGL((k_probe_finish<DIM>), dim3(cdiv(n, 64)), dim3(64), 0, h->stream, h->n_cells, h->geo.p, h->cell_x0.p, n, points, best, cells, lam);
+  hipLaunchKernelGGL((k_probe_finish<DIM>), dim3(cdiv(n, 64)), dim3(64), 0, h->stream, h->n_cells, h->geo.p, h->probe.cell_x0.p, n, points, best, cells, lam);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -191,7 +155,7 @@ void probe_locate(nsx_handle *h, int n, const double *points, double tol, int32_
 }
 
 static void set_probes(nsx_handle *h, int n, const double *points, double tol) {
-  probe_check_space(h);
+  post_check_space(h, "nsx_set_probes");
   if (n < 0) NSX_THROW(NSX_ERR_ARG, "n_points = %d", n);
   if (n > PROBE_MAX) NSX_THROW(NSX_ERR_UNSUPPORTED, "%d probes: at most %d per handle", n, PROBE_MAX);
   if (n > 0 && !points) NSX_THROW(NSX_ERR_ARG, "null points");
@@ -199,7 +163,7 @@ static void set_probes(nsx_handle *h, int n, const double *points, double tol) {
   const int dim = h->dim, nl = dim + 1;
   for (size_t i = 0; i < (size_t)n * dim; ++i)
     if (!std::isfinite(points[i])) NSX_THROW(NSX_ERR_ARG, "probe %zu: coordinate %zu is not finite", i / dim, i % dim);
-  probe_clear(h);
+  h->probe.mesh_changed();  // the earlier set is given up, as by a new mesh
   if (n == 0) return;
   if (tol < 0.0) tol = PROBE_TOL;
   HIP_CHECK(hipSetDevice(h->prm.device));
@@ -207,14 +171,14 @@ static void set_probes(nsx_handle *h, int n, const double *points, double tol) {
   DevBuf<int32_t> best;
   pts.upload(points, (size_t)n * dim, h->stream);
   best.upload(std::vector<int32_t>((size_t)n, INT32_MAX), h->stream);
-  h->probe_cell.alloc(n);
-  h->probe_lambda.alloc((size_t)nl * n);
-  h->probe_out.alloc((size_t)(dim + 1 + dim * dim) * n);
-  probe_locate(h, n, pts.p, tol, best.p, h->probe_cell.p, h->probe_lambda.p);
+  h->probe.cell.alloc(n);
+  h->probe.lambda.alloc((size_t)nl * n);
+  h->probe.out.alloc((size_t)(dim + 1 + dim * dim) * n);
+  probe_locate(h, n, pts.p, tol, best.p, h->probe.cell.p, h->probe.lambda.p);
   std::vector<int32_t> cells((size_t)n), owner((size_t)n);
   std::vector<double> lam_soa((size_t)nl * n);
-  h->probe_cell.download(cells.data(), cells.size(), h->stream);
-  h->probe_lambda.download(lam_soa.data(), lam_soa.size(), h->stream);
+  h->probe.cell.download(cells.data(), cells.size(), h->stream);
+  h->probe.lambda.download(lam_soa.data(), lam_soa.size(), h->stream);
   for (int p = 0; p < n; ++p) owner[p] = cells[p] >= 0 ? h->rank : -1;
   if (h->comm && h->world > 1) {
     // who found what, through the SUM collective: rank r adds bit r % 48 of double r / 48 of every point it found -- distinct powers of two below
@@ -240,46 +204,46 @@ static void set_probes(nsx_handle *h, int n, const double *points, double tol) {
         changed = true;
       }
     }
-    if (changed) h->probe_cell.upload(cells, h->stream);
+    if (changed) h->probe.cell.upload(cells, h->stream);
   }
-  h->probe_lambda_h.resize((size_t)n * nl);
+  h->probe.lambda_h.resize((size_t)n * nl);
   for (int p = 0; p < n; ++p)
-    for (int k = 0; k < nl; ++k) h->probe_lambda_h[(size_t)p * nl + k] = lam_soa[(size_t)k * n + p];
-  h->probe_cells_h = std::move(cells);
-  h->probe_owner_h = std::move(owner);
-  h->probe_n = n;
+    for (int k = 0; k < nl; ++k) h->probe.lambda_h[(size_t)p * nl + k] = lam_soa[(size_t)k * n + p];
+  h->probe.cells_h = std::move(cells);
+  h->probe.owner_h = std::move(owner);
+  h->probe.n = n;
 }
 
 template <int DIM, int NP2>
 static void launch_eval(nsx_handle *h) {
   int mine = 0;
-  for (int32_t c : h->probe_cells_h) mine += c >= 0;
+  for (int32_t c : h->probe.cells_h) mine += c >= 0;
   constexpr int NOUT = DIM + 1 + DIM * DIM;
-  const double bytes = 4.0 * h->probe_n + (double)mine * (8.0 * (DIM + 1) + 4.0 * (NP2 + DIM + 1) + 8.0 * (NP2 * DIM + DIM + 1) + 8.0 * DIM * DIM) + 8.0 * NOUT * h->probe_n;
+  const double bytes = 4.0 * h->probe.n + (double)mine * (8.0 * (DIM + 1) + 4.0 * (NP2 + DIM + 1) + 8.0 * (NP2 * DIM + DIM + 1) + 8.0 * DIM * DIM) + 8.0 * NOUT * h->probe.n;
   LaunchScope ls(h, "probe_eval", bytes);
-  hipLaunchKernelGGL((k_probe_eval<DIM, NP2>), dim3(cdiv(h->probe_n, 64)), dim3(64), 0, h->stream, h->probe_n, h->probe_cell.p, h->probe_lambda.p, h->n_cells,
-                     h->cell_n2.p, h->cell_n1.p, h->geo.p, h->sol.p, h->off_p, h->probe_out.p);
+  hipLaunchKernelGGL((k_probe_eval<DIM, NP2>), dim3(cdiv(h->probe.n, 64)), dim3(64), 0, h->stream, h->probe.n, h->probe.cell.p, h->probe.lambda.p, h->n_cells,
+                     h->cell_n2.p, h->cell_n1.p, h->geo.p, h->sol.p, h->off_p, h->probe.out.p);
 }
 
 static void eval_probes(nsx_handle *h, double *velocity, double *pressure, double *gradient, int32_t *found) {
-  probe_check_space(h);
-  if (h->probe_n == 0) NSX_THROW(NSX_ERR_ARG, "nsx_set_probes first");
+  post_check_space(h, "nsx_eval_probes");
+  if (h->probe.n == 0) NSX_THROW(NSX_ERR_ARG, "nsx_set_probes first");
   HIP_CHECK(hipSetDevice(h->prm.device));
-  const int dim = h->dim, n = h->probe_n, nout = dim + 1 + dim * dim;
+  const int dim = h->dim, n = h->probe.n, nout = dim + 1 + dim * dim;
   if (dim == 2) launch_eval<2, 6>(h);
   else launch_eval<3, 10>(h);
   HIP_CHECK(hipGetLastError());
   // the owner's values and exact zeros from everybody else (x + 0 is exact, NaN and inf survive): every rank gets the same bits
-  if (h->comm && h->world > 1) comm_allreduce_partials(h, h->probe_out.p, nout * n);
+  if (h->comm && h->world > 1) comm_allreduce_partials(h, h->probe.out.p, nout * n);
   std::vector<double> v((size_t)nout * n);
-  h->probe_out.download(v.data(), v.size(), h->stream);
+  h->probe.out.download(v.data(), v.size(), h->stream);
   for (int p = 0; p < n; ++p) {
     if (velocity)
       for (int i = 0; i < dim; ++i) velocity[(size_t)p * dim + i] = v[(size_t)i * n + p];
     if (pressure) pressure[p] = v[(size_t)dim * n + p];
     if (gradient)
       for (int k = 0; k < dim * dim; ++k) gradient[(size_t)p * dim * dim + k] = v[(size_t)(dim + 1 + k) * n + p];
-    if (found) found[p] = h->probe_owner_h[p] >= 0;
+    if (found) found[p] = h->probe.owner_h[p] >= 0;
   }
 }
 
@@ -288,40 +252,25 @@ static void eval_probes(nsx_handle *h, double *velocity, double *pressure, doubl
 extern "C" {
 
 int nsx_set_probes(nsx_handle *h, int n_points, const double *points, double tol) {
-  if (!h) return NSX_ERR_ARG;
-  try {
-    nsx::set_probes(h, n_points, points, tol);
-  } catch (const nsx::Error &e) {
-    h->err = e.msg;
-    return e.code;
-  }
-  return NSX_OK;
+  NSX_TRY(h)
+  nsx::set_probes(h, n_points, points, tol);
+  NSX_CATCH(h)
 }
 
 int nsx_get_probe_cells(nsx_handle *h, int32_t *cells, int32_t *owners, double *lambda) {
-  if (!h) return NSX_ERR_ARG;
-  try {
-    nsx::probe_check_space(h);
-    if (h->probe_n == 0) NSX_THROW(NSX_ERR_ARG, "nsx_set_probes first");
-    if (cells) std::copy(h->probe_cells_h.begin(), h->probe_cells_h.end(), cells);
-    if (owners) std::copy(h->probe_owner_h.begin(), h->probe_owner_h.end(), owners);
-    if (lambda) std::copy(h->probe_lambda_h.begin(), h->probe_lambda_h.end(), lambda);
-  } catch (const nsx::Error &e) {
-    h->err = e.msg;
-    return e.code;
-  }
-  return NSX_OK;
+  NSX_TRY(h)
+  nsx::post_check_space(h, "nsx_get_probe_cells");
+  if (h->probe.n == 0) NSX_THROW(NSX_ERR_ARG, "nsx_set_probes first");
+  if (cells) std::copy(h->probe.cells_h.begin(), h->probe.cells_h.end(), cells);
+  if (owners) std::copy(h->probe.owner_h.begin(), h->probe.owner_h.end(), owners);
+  if (lambda) std::copy(h->probe.lambda_h.begin(), h->probe.lambda_h.end(), lambda);
+  NSX_CATCH(h)
 }
 
 int nsx_eval_probes(nsx_handle *h, double *velocity, double *pressure, double *gradient, int32_t *found) {
-  if (!h) return NSX_ERR_ARG;
-  try {
-    nsx::eval_probes(h, velocity, pressure, gradient, found);
-  } catch (const nsx::Error &e) {
-    h->err = e.msg;
-    return e.code;
-  }
-  return NSX_OK;
+  NSX_TRY(h)
+  nsx::eval_probes(h, velocity, pressure, gradient, found);
+  NSX_CATCH(h)
 }
 
 }  // extern "C"

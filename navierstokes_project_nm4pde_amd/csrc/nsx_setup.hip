@@ -573,21 +573,6 @@ void vec_to_caller(nsx_handle *h, const double *dev, double *host) {
 
 }  // namespace nsx
 
-#define NSX_TRY(h_)                 \
-  if (!(h_)) return NSX_ERR_ARG;    \
-  try {
-#define NSX_CATCH(h_)                                      \
-  }                                                        \
-  catch (const nsx::Error &e) {                            \
-    (h_)->err = e.msg;                                     \
-    return e.code;                                         \
-  }                                                        \
-  catch (const std::exception &e) {                        \
-    (h_)->err = e.what();                                  \
-    return NSX_ERR_ARG;                                    \
-  }                                                        \
-  return NSX_OK;
-
 extern "C" {
 
 const char *nsx_version(void) { return "nsx 0.1 (gfx950)"; }
@@ -638,11 +623,7 @@ int nsx_create(const nsx_params *p, nsx_handle **out) {
     HIP_CHECK(hipHostGetDevicePointer((void **)&h->pub_dev, h->pub_host, 0));
     h->pub_counter.alloc(1);
     h->pub_counter.zero(h->stream);
-  } catch (const nsx::Error &e) {
-    g_create_error = e.msg;
-    delete h;
-    return e.code;
-  }
+  NSX_CATCH_TO(g_create_error, delete h)
   *out = h;
   return NSX_OK;
 }
@@ -921,6 +902,19 @@ void install_mesh(nsx_handle *h) {
             (int)h->in_rank_u_h.size() - 1, (int)(h->sblk_h.empty() ? h->rank_p_h.size() : h->sblk_h.size()) - 1, h->layout_colours, h->layout_colours_p);
 }
 
+// The tail of nsx_set_mesh / nsx_set_mesh_distributed, behind connectivity(): keep what was handed over (a new layout reruns the set-up
+// products from it), let the post-processing features drop what belonged to the old mesh, and install the mesh with the default rank tables.
+void adopt_mesh(nsx_handle *h, int n_cells, int n_cells1, const double *cell_coords) {
+  const int dim = h->dim, nv = dim + 1;
+  h->cell_n2_in = h->cell_n2_h;
+  h->cell_n1_in = h->cell_n1_h;
+  h->cell_coords_in.assign(cell_coords, cell_coords + (size_t)n_cells * nv * dim);
+  post_mesh_changed(h);
+  h->n_cells1 = n_cells1;
+  default_ranks(h);
+  install_mesh(h);
+}
+
 void halo_plan(nsx_handle *h, nsx::HaloPlan &p, int n_own, int goff, const std::vector<int32_t> &ghosts, const int32_t *gpu_ptr,
                int n_nbr, const int32_t *nbr, const int32_t *send_ptr, const int32_t *send_nodes, int ncomp) {
   p.n_own = n_own;
@@ -975,18 +969,9 @@ int nsx_set_mesh(nsx_handle *h, int n_cells, int dpc, const int32_t *cell_dofs, 
   h->ghost_u.clear();
   h->ghost_p.clear();
   connectivity(h, n_cells, dpc, cell_dofs, n_u, n_p, [](int32_t g) { return g; }, [](int32_t g) { return g; });
-  h->cell_n2_in = h->cell_n2_h;
-  h->cell_n1_in = h->cell_n1_h;
-  h->cell_coords_in.assign(cell_coords, cell_coords + (size_t)n_cells * nv * dim);
-  probe_clear(h);
-  tracer_clear(h);
-  nodal_clear(h);
-  iso_clear(h);
-  h->n_cells1 = n_cells;
-  h->haloU.send_idx_in.clear();
+  h->haloU.send_idx_in.clear();  // one process: no halo plan to carry through install_mesh
   h->haloP.send_idx_in.clear();
-  default_ranks(h);
-  install_mesh(h);
+  adopt_mesh(h, n_cells, n_cells, cell_coords);
   NSX_CATCH(h)
 }
 
@@ -1052,16 +1037,7 @@ int nsx_set_mesh_distributed(nsx_handle *h, int n_cells, int n_cells1, int dpc, 
   }
   halo_plan(h, h->haloU, h->N2, h->goff_u, h->ghost_u, gpu_u_ptr, n_nbr, nbr, send_u_ptr, send_u_nodes, dim);
   halo_plan(h, h->haloP, h->NP, h->goff_p, h->ghost_p, gpu_p_ptr, n_nbr, nbr, send_p_ptr, send_p_nodes, 1);
-  h->cell_n2_in = h->cell_n2_h;
-  h->cell_n1_in = h->cell_n1_h;
-  h->cell_coords_in.assign(cell_coords, cell_coords + (size_t)n_cells * nv * dim);
-  probe_clear(h);
-  tracer_clear(h);
-  nodal_clear(h);
-  iso_clear(h);
-  h->n_cells1 = n_cells1;
-  default_ranks(h);
-  install_mesh(h);
+  adopt_mesh(h, n_cells, n_cells1, cell_coords);
   NSX_CATCH(h)
 }
 
@@ -1182,10 +1158,11 @@ int nsx_scalar_graph_nnz(nsx_handle *h, int which, int64_t *nnz) {
 }
 int nsx_scalar_graph(nsx_handle *h, int which, int32_t *rowptr, int32_t *colind) {
   if (!h || !rowptr || !colind || !h->have_mesh || which < 0 || which > 1) return NSX_ERR_ARG;
+  NSX_TRY(h)
   const nsx::Csr &g = caller_graph(h, which);
   std::copy(g.rowptr.begin(), g.rowptr.end(), rowptr);
   std::copy(g.colind.begin(), g.colind.end(), colind);
-  return NSX_OK;
+  NSX_CATCH(h)
 }
 int nsx_ilu_get(nsx_handle *h, int which, double *values) {
   NSX_TRY(h)
@@ -1328,26 +1305,28 @@ static void prof_collect(nsx_handle *h) {
   }
 }
 int nsx_profile_reset(nsx_handle *h) {
-  if (!h) return NSX_ERR_ARG;
+  NSX_TRY(h)
   prof_collect(h);
   h->prof.clear();
-  return NSX_OK;
+  NSX_CATCH(h)
 }
 int nsx_profile_count(nsx_handle *h) {
-  if (!h) return NSX_ERR_ARG;
+  NSX_TRY(h)
   prof_collect(h);
   h->prof_names.clear();
   for (auto &kv : h->prof) h->prof_names.push_back(kv.first);
   return (int)h->prof_names.size();
+  NSX_CATCH(h)
 }
 int nsx_profile_get(nsx_handle *h, int i, const char **name, int64_t *launches, double *total_ms, double *bytes) {
   if (!h || i < 0 || i >= (int)h->prof_names.size()) return NSX_ERR_ARG;
+  NSX_TRY(h)
   const auto &e = h->prof[h->prof_names[i]];
   if (name) *name = h->prof_names[i].c_str();
   if (launches) *launches = e.launches;
   if (total_ms) *total_ms = e.ms;
   if (bytes) *bytes = e.launches ? e.bytes / (double)e.launches : 0.0;  // average algorithmic bytes per launch
-  return NSX_OK;
+  NSX_CATCH(h)
 }
 
 }  // extern "C"

@@ -671,165 +671,152 @@ void v_reciprocal(nsx_handle *h, int n, double *d, const double *s, double num) 
 
 }  // namespace nsx
 
-#define NSX_API_BODY(h_, ...)                  \
-  if (!(h_)) return NSX_ERR_ARG;               \
-  try {                                        \
-    __VA_ARGS__;                               \
-  } catch (const nsx::Error &e) {              \
-    (h_)->err = e.msg;                         \
-    return e.code;                             \
-  } catch (const std::exception &e) {          \
-    (h_)->err = e.what();                      \
-    return NSX_ERR_ARG;                        \
-  }                                            \
-  return NSX_OK;
-
 extern "C" {
 
 int nsx_solve_time_step(nsx_handle *h, int prec_type, double tol_abs, double inner_rtol, int maxiter, int inner_maxiter,
                         nsx_solve_stats *stats) {
-  NSX_API_BODY(h, {
-    if (!h->assembled) NSX_THROW(NSX_ERR_ARG, "assemble before solving");
-    nsx::solve_time_step(h, prec_type, tol_abs, inner_rtol, maxiter, inner_maxiter, stats);
-    if (stats && stats->status) {
-      h->err = stats->status == 1 ? "outer GMRES did not converge (SolverControl::NoConvergence)" : "an inner solve did not converge";
-      return NSX_ERR_NOCONV;
-    }
-  })
+  NSX_TRY(h)
+  if (!h->assembled) NSX_THROW(NSX_ERR_ARG, "assemble before solving");
+  nsx::solve_time_step(h, prec_type, tol_abs, inner_rtol, maxiter, inner_maxiter, stats);
+  if (stats && stats->status) {
+    h->err = stats->status == 1 ? "outer GMRES did not converge (SolverControl::NoConvergence)" : "an inner solve did not converge";
+    return NSX_ERR_NOCONV;
+  }
+  NSX_CATCH(h)
 }
 
 int nsx_prec_initialize(nsx_handle *h, int prec_type) {
-  NSX_API_BODY(h, {
-    nsx::prec_initialize(h, prec_type);
-    HIP_CHECK(hipStreamSynchronize(h->stream));
-    nsx::prec_confirm(h);
-  })
+  NSX_TRY(h)
+  nsx::prec_initialize(h, prec_type);
+  HIP_CHECK(hipStreamSynchronize(h->stream));
+  nsx::prec_confirm(h);
+  NSX_CATCH(h)
 }
 
 int nsx_prec_vmult(nsx_handle *h, int prec_type, double inner_rtol, int inner_maxiter, double *dst, const double *src, nsx_solve_stats *stats) {
-  NSX_API_BODY(h, {
-    if (!dst || !src) NSX_THROW(NSX_ERR_ARG, "null vector");
-    if (h->dist) NSX_THROW(NSX_ERR_UNSUPPORTED, "nsx_prec_vmult with host vectors works on a single-process handle only");
-    HIP_CHECK(hipSetDevice(h->prm.device));
-    const int n = h->n_u + h->n_p;
-    nsx::Tmp d(h, n), s(h, n);
-    nsx::vec_from_caller(h, s.p(), src, false);
-    nsx::vec_from_caller(h, d.p(), dst, false);  // aSIMPLE reads dst as initial guess
-    if (stats) memset(stats, 0, sizeof(*stats));
-    h->defer_red = false;
-    h->pending_red.clear();
-    h->inner_F_fp32_used = h->ilu_F_fp32_used = 0;
-    nsx::prec_vmult(h, prec_type, inner_rtol, inner_maxiter, d.p(), s.p(), stats, nsx::step_fused());
-    if (stats) stats->persistent_fallbacks = h->n_persistent_fallbacks;
-    nsx::vec_to_caller(h, d.p(), dst);
-    nsx::ilu_check(h);
-  })
+  NSX_TRY(h)
+  if (!dst || !src) NSX_THROW(NSX_ERR_ARG, "null vector");
+  if (h->dist) NSX_THROW(NSX_ERR_UNSUPPORTED, "nsx_prec_vmult with host vectors works on a single-process handle only");
+  HIP_CHECK(hipSetDevice(h->prm.device));
+  const int n = h->n_u + h->n_p;
+  nsx::Tmp d(h, n), s(h, n);
+  nsx::vec_from_caller(h, s.p(), src, false);
+  nsx::vec_from_caller(h, d.p(), dst, false);  // aSIMPLE reads dst as initial guess
+  if (stats) memset(stats, 0, sizeof(*stats));
+  h->defer_red = false;
+  h->pending_red.clear();
+  h->inner_F_fp32_used = h->ilu_F_fp32_used = 0;
+  nsx::prec_vmult(h, prec_type, inner_rtol, inner_maxiter, d.p(), s.p(), stats, nsx::step_fused());
+  if (stats) stats->persistent_fallbacks = h->n_persistent_fallbacks;
+  nsx::vec_to_caller(h, d.p(), dst);
+  nsx::ilu_check(h);
+  NSX_CATCH(h)
 }
 
 int nsx_system_vmult(nsx_handle *h, double *dst, const double *src) {
-  NSX_API_BODY(h, {
-    if (!dst || !src || !h->assembled) NSX_THROW(NSX_ERR_ARG, "null vector / nothing assembled");
-    HIP_CHECK(hipSetDevice(h->prm.device));
-    nsx::Tmp d(h, h->len_blk), s(h, h->len_blk);
-    // host vectors are globally indexed: pick the owned entries (ghosts come through the halo exchange of the product)
-    nsx::vec_from_caller(h, s.p(), src, false);
-    nsx::spmv_saddle(h, s.p(), d.p());
-    nsx::vec_to_caller(h, d.p(), dst);
-  })
+  NSX_TRY(h)
+  if (!dst || !src || !h->assembled) NSX_THROW(NSX_ERR_ARG, "null vector / nothing assembled");
+  HIP_CHECK(hipSetDevice(h->prm.device));
+  nsx::Tmp d(h, h->len_blk), s(h, h->len_blk);
+  // host vectors are globally indexed: pick the owned entries (ghosts come through the halo exchange of the product)
+  nsx::vec_from_caller(h, s.p(), src, false);
+  nsx::spmv_saddle(h, s.p(), d.p());
+  nsx::vec_to_caller(h, d.p(), dst);
+  NSX_CATCH(h)
 }
 
 int nsx_ilu_apply(nsx_handle *h, int which, double *dst, const double *src) {
-  NSX_API_BODY(h, {
-    if (!dst || !src || which < 0 || which > 1) NSX_THROW(NSX_ERR_ARG, "bad arguments");
-    if (!h->prec_ready) NSX_THROW(NSX_ERR_ARG, "no factors: call nsx_prec_initialize first");
-    if (h->dist) NSX_THROW(NSX_ERR_UNSUPPORTED, "nsx_ilu_apply with host vectors works on a single-process handle only");
-    HIP_CHECK(hipSetDevice(h->prm.device));
-    const int n = which == 0 ? h->n_u : h->n_p;
-    nsx::Tmp d(h, n), s(h, n);
-    nsx::part_from_caller(h, which, s.p(), src);
-    if (which == 0) nsx::ilu_solve(h, h->gA, h->schedF, h->luF.p, s.p(), d.p(), h->dim, "ilu_solve_F", -1, h->inner_precision == NSX_INNER_FP32, &h->ilu_F_fp32_used);
-    else nsx::ilu_solve(h, h->gS, h->schedS, h->luS.p, s.p(), d.p(), 1, "ilu_solve_S");
-    nsx::part_to_caller(h, which, d.p(), dst);
-    nsx::ilu_check(h);
-  })
+  NSX_TRY(h)
+  if (!dst || !src || which < 0 || which > 1) NSX_THROW(NSX_ERR_ARG, "bad arguments");
+  if (!h->prec_ready) NSX_THROW(NSX_ERR_ARG, "no factors: call nsx_prec_initialize first");
+  if (h->dist) NSX_THROW(NSX_ERR_UNSUPPORTED, "nsx_ilu_apply with host vectors works on a single-process handle only");
+  HIP_CHECK(hipSetDevice(h->prm.device));
+  const int n = which == 0 ? h->n_u : h->n_p;
+  nsx::Tmp d(h, n), s(h, n);
+  nsx::part_from_caller(h, which, s.p(), src);
+  if (which == 0) nsx::ilu_solve(h, h->gA, h->schedF, h->luF.p, s.p(), d.p(), h->dim, "ilu_solve_F", -1, h->inner_precision == NSX_INNER_FP32, &h->ilu_F_fp32_used);
+  else nsx::ilu_solve(h, h->gS, h->schedS, h->luS.p, s.p(), d.p(), 1, "ilu_solve_S");
+  nsx::part_to_caller(h, which, d.p(), dst);
+  nsx::ilu_check(h);
+  NSX_CATCH(h)
 }
 
 int nsx_set_inner_precision(nsx_handle *h, int precision) {
-  NSX_API_BODY(h, {
-    if (precision != NSX_INNER_FP64 && precision != NSX_INNER_FP32) NSX_THROW(NSX_ERR_ARG, "unknown inner precision %d (NSX_INNER_FP64 = 0, NSX_INNER_FP32 = 1)", precision);
-    h->inner_precision = precision;
-    h->prec_ready = false;  // the float copy of F and the solve stream of its factors are written by the next initialisation
-  })
+  NSX_TRY(h)
+  if (precision != NSX_INNER_FP64 && precision != NSX_INNER_FP32) NSX_THROW(NSX_ERR_ARG, "unknown inner precision %d (NSX_INNER_FP64 = 0, NSX_INNER_FP32 = 1)", precision);
+  h->inner_precision = precision;
+  h->prec_ready = false;  // the float copy of F and the solve stream of its factors are written by the next initialisation
+  NSX_CATCH(h)
 }
 
 int nsx_inner_F_vmult(nsx_handle *h, double *dst, const double *src) {
-  NSX_API_BODY(h, {
-    if (!dst || !src || !h->assembled) NSX_THROW(NSX_ERR_ARG, "null vector / nothing assembled");
-    if (!h->prec_ready) NSX_THROW(NSX_ERR_ARG, "call nsx_prec_initialize first (it brings F's copy in the inner precision up to date)");
-    if (h->dist) NSX_THROW(NSX_ERR_UNSUPPORTED, "nsx_inner_F_vmult with host vectors works on a single-process handle only");
-    HIP_CHECK(hipSetDevice(h->prm.device));
-    nsx::Tmp d(h, h->n_u), s(h, h->n_u);
-    nsx::part_from_caller(h, 0, s.p(), src);
-    h->inner_F_fp32_used = 0;
-    nsx::spmv_F_inner(h, s.p(), d.p());
-    nsx::part_to_caller(h, 0, d.p(), dst);
-  })
+  NSX_TRY(h)
+  if (!dst || !src || !h->assembled) NSX_THROW(NSX_ERR_ARG, "null vector / nothing assembled");
+  if (!h->prec_ready) NSX_THROW(NSX_ERR_ARG, "call nsx_prec_initialize first (it brings F's copy in the inner precision up to date)");
+  if (h->dist) NSX_THROW(NSX_ERR_UNSUPPORTED, "nsx_inner_F_vmult with host vectors works on a single-process handle only");
+  HIP_CHECK(hipSetDevice(h->prm.device));
+  nsx::Tmp d(h, h->n_u), s(h, h->n_u);
+  nsx::part_from_caller(h, 0, s.p(), src);
+  h->inner_F_fp32_used = 0;
+  nsx::spmv_F_inner(h, s.p(), d.p());
+  nsx::part_to_caller(h, 0, d.p(), dst);
+  NSX_CATCH(h)
 }
 
 int nsx_sparse_product(nsx_handle *h, int op, double *dst, const double *src, const double *aux) {
-  NSX_API_BODY(h, {
-    if (!dst || !src || !h->assembled) NSX_THROW(NSX_ERR_ARG, "null vector / nothing assembled");
-    if (op < 0 || op >= NSX_PROD_COUNT) NSX_THROW(NSX_ERR_ARG, "unknown sparse product %d", op);
-    const bool inner = op == NSX_PROD_F_INNER || op == NSX_PROD_F_RESID || op == NSX_PROD_S;
-    if (inner && !h->prec_ready) NSX_THROW(NSX_ERR_ARG, "call nsx_prec_initialize first (F's copy in the inner precision and the Schur complement are its work)");
-    const bool wants_aux = op == NSX_PROD_F_RESID || op == NSX_PROD_B_MINUS_R || op == NSX_PROD_R_MINUS_B || op == NSX_PROD_G_ACC;
-    if (wants_aux && !aux) NSX_THROW(NSX_ERR_ARG, "this product reads aux");
-    HIP_CHECK(hipSetDevice(h->prm.device));
-    nsx::ensure_schedules(h);
-    nsx::Tmp d(h, h->len_blk), s(h, h->len_blk), a(h, h->len_blk);
-    nsx::vec_from_caller(h, s.p(), src, false);
-    if (wants_aux) nsx::vec_from_caller(h, a.p(), aux, false);
-    // what the product does not write comes back as 0; NSX_PROD_G_ACC accumulates onto aux_u
-    if (op == NSX_PROD_G_ACC) nsx::vec_from_caller(h, d.p(), aux, false);
-    else HIP_CHECK(hipMemsetAsync(d.p(), 0, (size_t)h->len_blk * sizeof(double), h->stream));
-    h->inner_F_fp32_used = 0;
-    const double *xu = s.p(), *xp = s.p() + h->off_p, *au = a.p(), *ap = a.p() + h->off_p;
-    double *yu = d.p(), *yp = d.p() + h->off_p;
-    switch (op) {
-      case NSX_PROD_F: nsx::spmv_F(h, h->vF.p, xu, yu); break;
-      case NSX_PROD_F_INNER: nsx::spmv_F_inner(h, xu, yu); break;
-      case NSX_PROD_F_RESID: nsx::spmv_F_inner_resid(h, xu, au, yu); break;
-      case NSX_PROD_MASS: nsx::spmv_F(h, h->vMass.p, xu, yu); break;
-      case NSX_PROD_B: nsx::spmv_B(h, xu, yp, nullptr, 0); break;
-      case NSX_PROD_B_MINUS_R: nsx::spmv_B(h, xu, yp, ap, 1); break;
-      case NSX_PROD_R_MINUS_B: nsx::spmv_B(h, xu, yp, ap, -1); break;
-      case NSX_PROD_G: nsx::spmv_G(h, xp, yu, false); break;
-      case NSX_PROD_G_ACC: nsx::spmv_G(h, xp, yu, true); break;
-      case NSX_PROD_S: nsx::spmv_S(h, xp, yp); break;
-      default: nsx::spmv_saddle(h, s.p(), d.p()); break;
-    }
-    if (op == NSX_PROD_G_ACC) HIP_CHECK(hipMemsetAsync(yp, 0, (size_t)(h->len_blk - h->off_p) * sizeof(double), h->stream));  // aux_p is no result
-    nsx::vec_to_caller(h, d.p(), dst);
-  })
+  NSX_TRY(h)
+  if (!dst || !src || !h->assembled) NSX_THROW(NSX_ERR_ARG, "null vector / nothing assembled");
+  if (op < 0 || op >= NSX_PROD_COUNT) NSX_THROW(NSX_ERR_ARG, "unknown sparse product %d", op);
+  const bool inner = op == NSX_PROD_F_INNER || op == NSX_PROD_F_RESID || op == NSX_PROD_S;
+  if (inner && !h->prec_ready) NSX_THROW(NSX_ERR_ARG, "call nsx_prec_initialize first (F's copy in the inner precision and the Schur complement are its work)");
+  const bool wants_aux = op == NSX_PROD_F_RESID || op == NSX_PROD_B_MINUS_R || op == NSX_PROD_R_MINUS_B || op == NSX_PROD_G_ACC;
+  if (wants_aux && !aux) NSX_THROW(NSX_ERR_ARG, "this product reads aux");
+  HIP_CHECK(hipSetDevice(h->prm.device));
+  nsx::ensure_schedules(h);
+  nsx::Tmp d(h, h->len_blk), s(h, h->len_blk), a(h, h->len_blk);
+  nsx::vec_from_caller(h, s.p(), src, false);
+  if (wants_aux) nsx::vec_from_caller(h, a.p(), aux, false);
+  // what the product does not write comes back as 0; NSX_PROD_G_ACC accumulates onto aux_u
+  if (op == NSX_PROD_G_ACC) nsx::vec_from_caller(h, d.p(), aux, false);
+  else HIP_CHECK(hipMemsetAsync(d.p(), 0, (size_t)h->len_blk * sizeof(double), h->stream));
+  h->inner_F_fp32_used = 0;
+  const double *xu = s.p(), *xp = s.p() + h->off_p, *au = a.p(), *ap = a.p() + h->off_p;
+  double *yu = d.p(), *yp = d.p() + h->off_p;
+  switch (op) {
+    case NSX_PROD_F: nsx::spmv_F(h, h->vF.p, xu, yu); break;
+    case NSX_PROD_F_INNER: nsx::spmv_F_inner(h, xu, yu); break;
+    case NSX_PROD_F_RESID: nsx::spmv_F_inner_resid(h, xu, au, yu); break;
+    case NSX_PROD_MASS: nsx::spmv_F(h, h->vMass.p, xu, yu); break;
+    case NSX_PROD_B: nsx::spmv_B(h, xu, yp, nullptr, 0); break;
+    case NSX_PROD_B_MINUS_R: nsx::spmv_B(h, xu, yp, ap, 1); break;
+    case NSX_PROD_R_MINUS_B: nsx::spmv_B(h, xu, yp, ap, -1); break;
+    case NSX_PROD_G: nsx::spmv_G(h, xp, yu, false); break;
+    case NSX_PROD_G_ACC: nsx::spmv_G(h, xp, yu, true); break;
+    case NSX_PROD_S: nsx::spmv_S(h, xp, yp); break;
+    default: nsx::spmv_saddle(h, s.p(), d.p()); break;
+  }
+  if (op == NSX_PROD_G_ACC) HIP_CHECK(hipMemsetAsync(yp, 0, (size_t)(h->len_blk - h->off_p) * sizeof(double), h->stream));  // aux_p is no result
+  nsx::vec_to_caller(h, d.p(), dst);
+  NSX_CATCH(h)
 }
 
 int nsx_schur_cg(nsx_handle *h, double rtol, int maxiter, double *x, const double *b, int *steps, double *last_residual, int *status) {
-  NSX_API_BODY(h, {
-    if (!x || !b || !steps || !last_residual || !status) NSX_THROW(NSX_ERR_ARG, "null argument");
-    if (!h->prec_ready) NSX_THROW(NSX_ERR_ARG, "no Schur complement and no factors: call nsx_prec_initialize first");
-    HIP_CHECK(hipSetDevice(h->prm.device));
-    nsx::Tmp xd(h, h->len_p), bd(h, h->len_p);
-    nsx::pressure_from_caller(h, xd.p(), x);
-    nsx::pressure_from_caller(h, bd.p(), b);
-    h->defer_red = false;
-    h->pending_red.clear();
-    const nsx::SolveResult r = nsx::schur_cg(h, rtol, maxiter, xd.p(), bd.p());
-    *steps = r.steps;
-    *last_residual = r.last;
-    *status = r.status;
-    nsx::pressure_to_caller(h, xd.p(), x);
-    nsx::ilu_check(h);
-  })
+  NSX_TRY(h)
+  if (!x || !b || !steps || !last_residual || !status) NSX_THROW(NSX_ERR_ARG, "null argument");
+  if (!h->prec_ready) NSX_THROW(NSX_ERR_ARG, "no Schur complement and no factors: call nsx_prec_initialize first");
+  HIP_CHECK(hipSetDevice(h->prm.device));
+  nsx::Tmp xd(h, h->len_p), bd(h, h->len_p);
+  nsx::pressure_from_caller(h, xd.p(), x);
+  nsx::pressure_from_caller(h, bd.p(), b);
+  h->defer_red = false;
+  h->pending_red.clear();
+  const nsx::SolveResult r = nsx::schur_cg(h, rtol, maxiter, xd.p(), bd.p());
+  *steps = r.steps;
+  *last_residual = r.last;
+  *status = r.status;
+  nsx::pressure_to_caller(h, xd.p(), x);
+  nsx::ilu_check(h);
+  NSX_CATCH(h)
 }
 
 }  // extern "C"

@@ -1,8 +1,8 @@
 // nsx_tracer.hip — tracer particles: massless particles carried by u_h (include/nsx.h, section "tracer particles").  No counterpart in the
 // reference, whose output (one VTU every 20 steps, NavierStokes3D.cpp:643-683) cannot give pathlines.
 // A probe is located once and never moves; a tracer walks from cell to cell several times per step.  Everything it needs sits on the device:
-// the ghosted `solution` and `previous_solution`, cell_n2, geo (J^-1), cell_x0 and the probes' containment arithmetic (probe_lambda); the one
-// table that was missing, the face neighbours cell_nbr[k][cell], is built by the first nsx_set_tracers on a mesh (host/adjacency.hpp).
+// the ghosted `solution` and `previous_solution`, cell_n2, geo (J^-1), probe.cell_x0 and the probes' containment arithmetic (probe_lambda); the one
+// table that was missing, the face neighbours tracer.cell_nbr[k][cell], is built by the first nsx_set_tracers on a mesh (host/adjacency.hpp).
 //
 //   k_tracer_advect  one PARTICLE PER LANE, 64-lane workgroups, ALL n_substeps inside one launch.  Position, cell, stage velocities and the
 //                    cell map stay in registers; everything is unrolled with static indexing, as k_probe_eval.  Per stage point: the walk
@@ -17,7 +17,7 @@
 #include <cmath>
 
 #include "../host/adjacency.hpp"
-#include "nsx_internal.hpp"
+#include "nsx_post.hpp"
 
 namespace nsx {
 
@@ -55,20 +55,17 @@ __device__ __forceinline__ int tracer_walk(int n_cells, const int32_t *__restric
   return NSX_TRACER_LOST;
 }
 
-// u_h at lam in `cell`: the shape functions of k_probe_eval.  LINEAR: u_prev + theta (u - u_prev), both sums node by node.
+// u_h at lam in `cell` (p2_shape, nsx_post.hpp).  LINEAR: u_prev + theta (u - u_prev), both sums node by node.
 template <int DIM, int NP2, bool LINEAR>
 __device__ __forceinline__ void tracer_velocity(int n_cells, int cell, const int32_t *__restrict__ cell_n2, const double *__restrict__ sol,
                                                 const double *__restrict__ prev, const double (&lam)[DIM + 1], double theta, double (&u)[DIM]) {
-  constexpr int NV = DIM + 1;
-  constexpr int LI[6] = {0, 1, 2, 0, 1, 2}, LJ[6] = {1, 2, 0, 3, 3, 3};
   double up[DIM];
 #pragma unroll
   for (int i = 0; i < DIM; ++i) u[i] = up[i] = 0.0;
 #pragma unroll
   for (int a = 0; a < NP2; ++a) {
-    double n;
-    if (a < NV) n = lam[a] * (2.0 * lam[a] - 1.0);
-    else n = 4.0 * lam[LI[a - NV]] * lam[LJ[a - NV]];
+    double n, g[DIM + 1];  // g: not computed
+    p2_shape<DIM, true, false>(a, lam, n, g);
     const int node = cell_n2[(size_t)a * n_cells + cell];
 #pragma unroll
     for (int i = 0; i < DIM; ++i) {
@@ -159,20 +156,13 @@ __global__ __launch_bounds__(64) void k_tracer_advect(int n, double *__restrict_
 }
 
 // ------------------------------------------------------------------ host drivers
-static void tracer_check_space(nsx_handle *h) {
-  if (!h->have_mesh) NSX_THROW(NSX_ERR_ARG, "nsx_set_tables and nsx_set_mesh first");
-  if (!((h->dim == 2 && h->np2 == 6) || (h->dim == 3 && h->np2 == 10)))
-    NSX_THROW(NSX_ERR_UNSUPPORTED, "no tracer kernel instantiated for dim=%d n_p2=%d (P2/P1 on simplices only)", h->dim, h->np2);
+static void tracer_check_space(nsx_handle *h, const char *who) {
+  post_check_space(h, who);
   if (h->world > 1) NSX_THROW(NSX_ERR_UNSUPPORTED, "tracer particles on %d processes: particles that cross rank boundaries are not supported", h->world);
 }
 
-void tracer_clear(nsx_handle *h) {
-  h->tracer_n = 0;
-  h->have_nbr = false;
-}
-
 static void ensure_neighbours(nsx_handle *h) {
-  if (h->have_nbr) return;
+  if (h->tracer.have_nbr) return;
   const int nv = h->dim + 1;
   if (h->np1 != nv || h->cell_n1_in.size() != (size_t)h->n_cells * nv) NSX_THROW(NSX_ERR_ARG, "the connectivity does not name dim + 1 vertices per cell");
   std::vector<int32_t> nbr;
@@ -181,12 +171,12 @@ static void ensure_neighbours(nsx_handle *h) {
   if (rc < 0 || nbr.size() != (size_t)h->n_cells * nv) NSX_THROW(NSX_ERR_ARG, "the face-neighbour table could not be built");
   for (int32_t c : nbr)
     if (c < -1 || c >= h->n_cells) NSX_THROW(NSX_ERR_ARG, "the face-neighbour table names cell %d", c);
-  h->cell_nbr.upload(nbr, h->stream);
-  h->have_nbr = true;
+  h->tracer.cell_nbr.upload(nbr, h->stream);
+  h->tracer.have_nbr = true;
 }
 
 static void set_tracers(nsx_handle *h, int n, const double *points, double tol) {
-  tracer_check_space(h);
+  tracer_check_space(h, "nsx_set_tracers");
   if (n < 0) NSX_THROW(NSX_ERR_ARG, "n = %d", n);
   if (n > TRACER_MAX) NSX_THROW(NSX_ERR_UNSUPPORTED, "%d tracer particles: at most %d per handle", n, TRACER_MAX);
   if (n > 0 && !points) NSX_THROW(NSX_ERR_ARG, "null points");
@@ -195,45 +185,45 @@ static void set_tracers(nsx_handle *h, int n, const double *points, double tol) 
   for (size_t i = 0; i < (size_t)n * dim; ++i)
     if (!std::isfinite(points[i])) NSX_THROW(NSX_ERR_ARG, "tracer %zu: coordinate %zu is not finite", i / dim, i % dim);
   if (n == 0) {
-    h->tracer_n = 0;
+    h->tracer.n = 0;
     return;
   }
   if (tol < 0.0) tol = PROBE_TOL;
   HIP_CHECK(hipSetDevice(h->prm.device));
   ensure_neighbours(h);
-  h->tracer_n = 0;  // a failure below leaves no set
+  h->tracer.n = 0;  // a failure below leaves no set
   DevBuf<double> pts, lam;
   DevBuf<int32_t> best;
   pts.upload(points, (size_t)n * dim, h->stream);
   best.upload(std::vector<int32_t>((size_t)n, INT32_MAX), h->stream);
   lam.alloc((size_t)(dim + 1) * n);
-  h->tracer_cell.alloc(n);
-  probe_locate(h, n, pts.p, tol, best.p, h->tracer_cell.p, lam.p);
+  h->tracer.cell.alloc(n);
+  probe_locate(h, n, pts.p, tol, best.p, h->tracer.cell.p, lam.p);
   std::vector<int32_t> cells((size_t)n), status((size_t)n);
-  h->tracer_cell.download(cells.data(), cells.size(), h->stream);
+  h->tracer.cell.download(cells.data(), cells.size(), h->stream);
   for (int p = 0; p < n; ++p) status[p] = cells[p] >= 0 ? NSX_TRACER_ACTIVE : NSX_TRACER_NOT_FOUND;
   std::vector<double> x((size_t)dim * n);
   for (int p = 0; p < n; ++p)
     for (int d = 0; d < dim; ++d) x[(size_t)d * n + p] = points[(size_t)p * dim + d];
-  h->tracer_x.upload(x, h->stream);
-  h->tracer_status.upload(status, h->stream);
-  h->tracer_face.upload(std::vector<int32_t>((size_t)n, -1), h->stream);
-  h->tracer_age.upload(std::vector<double>((size_t)n, 0.0), h->stream);
-  h->tracer_tol = tol;
-  h->tracer_n = n;
+  h->tracer.x.upload(x, h->stream);
+  h->tracer.status.upload(status, h->stream);
+  h->tracer.face.upload(std::vector<int32_t>((size_t)n, -1), h->stream);
+  h->tracer.age.upload(std::vector<double>((size_t)n, 0.0), h->stream);
+  h->tracer.tol = tol;
+  h->tracer.n = n;
 }
 
 template <int DIM, int NP2, int SCHEME, bool LINEAR>
 static void launch_advect(nsx_handle *h, double dt, int n_substeps) {
   constexpr int NSTAGE = SCHEME == NSX_TRACER_RK4 ? 4 : SCHEME == NSX_TRACER_RK2 ? 2 : 1;
-  const int n = h->tracer_n;
+  const int n = h->tracer.n;
   // algorithmic bytes: the particle state in and out, and per substep NSTAGE + 1 cell maps and NSTAGE gathers (node ids + values) without a hop
   const double per_stage = 4.0 * NP2 + 8.0 * NP2 * DIM * (LINEAR ? 2 : 1), per_map = 8.0 * (DIM * DIM + DIM);
   const double bytes = (double)n * (2.0 * (8.0 * (DIM + 1) + 12.0) + (double)n_substeps * (NSTAGE * per_stage + (NSTAGE + 1) * per_map));
   LaunchScope ls(h, "tracer_advect", bytes);
-  hipLaunchKernelGGL((k_tracer_advect<DIM, NP2, SCHEME, LINEAR>), dim3(cdiv(n, 64)), dim3(64), 0, h->stream, n, h->tracer_x.p, h->tracer_cell.p,
-                     h->tracer_status.p, h->tracer_face.p, h->tracer_age.p, h->n_cells, h->cell_nbr.p, h->cell_n2.p, h->geo.p, h->cell_x0.p, h->sol.p,
-                     h->prev_sol.p, dt / n_substeps, n_substeps, dt > 0.0 ? 1 : 0, h->tracer_tol);
+  hipLaunchKernelGGL((k_tracer_advect<DIM, NP2, SCHEME, LINEAR>), dim3(cdiv(n, 64)), dim3(64), 0, h->stream, n, h->tracer.x.p, h->tracer.cell.p,
+                     h->tracer.status.p, h->tracer.face.p, h->tracer.age.p, h->n_cells, h->tracer.cell_nbr.p, h->cell_n2.p, h->geo.p, h->probe.cell_x0.p, h->sol.p,
+                     h->prev_sol.p, dt / n_substeps, n_substeps, dt > 0.0 ? 1 : 0, h->tracer.tol);
 }
 
 template <int DIM, int NP2>
@@ -245,8 +235,8 @@ static void dispatch_advect(nsx_handle *h, double dt, int n_substeps, int scheme
 }
 
 static void advect_tracers(nsx_handle *h, double dt, int n_substeps, int scheme, int field) {
-  tracer_check_space(h);
-  if (h->tracer_n == 0 || !h->have_nbr) NSX_THROW(NSX_ERR_ARG, "nsx_set_tracers first");
+  tracer_check_space(h, "nsx_advect_tracers");
+  if (h->tracer.n == 0 || !h->tracer.have_nbr) NSX_THROW(NSX_ERR_ARG, "nsx_set_tracers first");
   if (!std::isfinite(dt)) NSX_THROW(NSX_ERR_ARG, "dt is not finite");
   if (n_substeps < 1) NSX_THROW(NSX_ERR_ARG, "n_substeps = %d", n_substeps);
   if (scheme != NSX_TRACER_EULER && scheme != NSX_TRACER_RK2 && scheme != NSX_TRACER_RK4) NSX_THROW(NSX_ERR_ARG, "scheme = %d (NSX_TRACER_EULER / RK2 / RK4)", scheme);
@@ -260,20 +250,20 @@ static void advect_tracers(nsx_handle *h, double dt, int n_substeps, int scheme,
 }
 
 static void get_tracers(nsx_handle *h, double *positions, int32_t *cells, int32_t *status, int32_t *exit_faces, double *age) {
-  tracer_check_space(h);
-  if (h->tracer_n == 0) NSX_THROW(NSX_ERR_ARG, "nsx_set_tracers first");
+  tracer_check_space(h, "nsx_get_tracers");
+  if (h->tracer.n == 0) NSX_THROW(NSX_ERR_ARG, "nsx_set_tracers first");
   HIP_CHECK(hipSetDevice(h->prm.device));
-  const int dim = h->dim, n = h->tracer_n;
+  const int dim = h->dim, n = h->tracer.n;
   if (positions) {
     std::vector<double> x((size_t)dim * n);
-    h->tracer_x.download(x.data(), x.size(), h->stream);
+    h->tracer.x.download(x.data(), x.size(), h->stream);
     for (int p = 0; p < n; ++p)
       for (int d = 0; d < dim; ++d) positions[(size_t)p * dim + d] = x[(size_t)d * n + p];
   }
-  if (cells) h->tracer_cell.download(cells, n, h->stream);
-  if (status) h->tracer_status.download(status, n, h->stream);
-  if (exit_faces) h->tracer_face.download(exit_faces, n, h->stream);
-  if (age) h->tracer_age.download(age, n, h->stream);
+  if (cells) h->tracer.cell.download(cells, n, h->stream);
+  if (status) h->tracer.status.download(status, n, h->stream);
+  if (exit_faces) h->tracer.face.download(exit_faces, n, h->stream);
+  if (age) h->tracer.age.download(age, n, h->stream);
 }
 
 }  // namespace nsx
@@ -281,36 +271,21 @@ static void get_tracers(nsx_handle *h, double *positions, int32_t *cells, int32_
 extern "C" {
 
 int nsx_set_tracers(nsx_handle *h, int n, const double *points, double tol) {
-  if (!h) return NSX_ERR_ARG;
-  try {
-    nsx::set_tracers(h, n, points, tol);
-  } catch (const nsx::Error &e) {
-    h->err = e.msg;
-    return e.code;
-  }
-  return NSX_OK;
+  NSX_TRY(h)
+  nsx::set_tracers(h, n, points, tol);
+  NSX_CATCH(h)
 }
 
 int nsx_advect_tracers(nsx_handle *h, double dt, int n_substeps, int scheme, int field) {
-  if (!h) return NSX_ERR_ARG;
-  try {
-    nsx::advect_tracers(h, dt, n_substeps, scheme, field);
-  } catch (const nsx::Error &e) {
-    h->err = e.msg;
-    return e.code;
-  }
-  return NSX_OK;
+  NSX_TRY(h)
+  nsx::advect_tracers(h, dt, n_substeps, scheme, field);
+  NSX_CATCH(h)
 }
 
 int nsx_get_tracers(nsx_handle *h, double *positions, int32_t *cells, int32_t *status, int32_t *exit_faces, double *age) {
-  if (!h) return NSX_ERR_ARG;
-  try {
-    nsx::get_tracers(h, positions, cells, status, exit_faces, age);
-  } catch (const nsx::Error &e) {
-    h->err = e.msg;
-    return e.code;
-  }
-  return NSX_OK;
+  NSX_TRY(h)
+  nsx::get_tracers(h, positions, cells, status, exit_faces, age);
+  NSX_CATCH(h)
 }
 
 }  // extern "C"
