@@ -500,6 +500,51 @@ int nsx_extract_isosurface(nsx_handle *h, const nsx_iso_source *field, double is
 /* The primitives of the last nsx_extract_isosurface. */
 int nsx_get_isosurface(nsx_handle *h, double *points /*[n][dim][dim]*/, double *colour /*[n][dim]*/, int32_t *cells /*[n]*/);
 
+/* ---- lattice sampling ---- */
+/* u_h, p_h, grad u_h and the nodal fields on a regular axis-aligned lattice, sampled on the device: an image of a 2D flow, a volume for
+ * rendering, a plane image at constant z, uniform data for spectra.  No counterpart in the reference.  The point probes search every cell for
+ * every point and take at most 65536 points; here every cell visits the lattice points its bounding box can hold (a rasterisation,
+ * csrc/nsx_lattice.hip), and nothing is stored per point but the owning cell.
+ * Lattice: point (i_0, ..., i_{dim-1}) has the coordinates x_d = origin_d + (double)i_d * spacing_d, formed with one rounded multiply and one
+ * rounded add, never a fused multiply-add: origin + i * spacing in IEEE double arithmetic on the host gives the same bits.  Linear index
+ * i_0 + counts_0 (i_1 + counts_1 i_2), x fastest: a plane is an image as it stands.  n_total = prod counts_d; counts_d = 1 is allowed (a plane
+ * image of a 3D flow).  origin = spacing = counts = NULL clears the lattice.
+ * Ownership: containment, tolerance and ties are those of the point probes -- a point lies in a cell when all dim+1 barycentric coordinates
+ * are >= -tol (tol < 0: the library's 1e-12; 0 <= tol < 1 as given), and among several cells the one with the lowest position in the
+ * caller's cell list owns the point (an integer minimum: exact and order-free).  The owner table depends on the mesh and the lattice alone,
+ * not on the scheduling, nsx_set_ranks or nsx_set_internal_layout.  A point in no cell has cells = -1 and every sampled value exactly 0.0;
+ * *n_found is the number of owned points.
+ * Values: of the ghosted `solution` (current after nsx_set_solution and after nsx_solve_time_step), as nsx_eval_probes defines them --
+ * u_h = sum_a N_a(lambda) U_a, p_h = sum_v lambda_v P_v, gradient = (sum_a U_a (x) grad_lambda N_a) J^-1 taken in the owner cell (d_j u_i,
+ * discontinuous across faces as the probes').  NSX_LATTICE_NODAL samples the P2 interpolant sum_a N_a(lambda) V_a of every plane the last
+ * nsx_compute_nodal_fields left at the cell's nodes: continuous images of the recovered gradient, vorticity, Q, strain rate and divergence.
+ * A state value that is not finite propagates into the points whose cell holds it; the call still returns NSX_OK.
+ * `what` of nsx_eval_lattice is an OR of the NSX_LATTICE_* bits; only what is asked for is computed and stored (8 bytes per point and
+ * component).  nsx_get_lattice hands out one quantity (one of the bits; `which` an NSX_FIELD_* for NSX_LATTICE_NODAL, ignored otherwise) as
+ * planes values[n_components][n_total]: dim for the velocity, 1 for the pressure, dim^2 (row-major d_j u_i) for the gradient, the field's
+ * components for a nodal field.  It returns what the last nsx_eval_lattice computed and does not recompute after a later solve.
+ * The three calls read state only: no vector, matrix or solver state changes, a following solve computes bitwise what it would have computed
+ * without them, and two calls agree bitwise.  The lattice and its results survive nsx_set_ranks and nsx_set_internal_layout; a new
+ * nsx_set_mesh(_distributed) or a new nsx_set_lattice drops them.  A refused call leaves an earlier lattice and its results readable.  No call
+ * issues a collective or a ghost exchange (nsx_comm_counters does not move).
+ * Errors: NSX_ERR_ARG for a null handle or output pointer, a call before tables or mesh, an eval / get call without a lattice, some but not
+ * all of origin / spacing / counts null, a count < 1, a spacing that is not finite or not > 0, an origin that is not finite, tol >= 1 or not
+ * finite, a lattice whose neighbouring coordinates are not distinct finite doubles at either end of an axis, `what` = 0 or with unknown bits,
+ * an unknown `quantity` or `which`, a quantity the last nsx_eval_lattice did not compute, NSX_LATTICE_NODAL without valid nodal results on
+ * the current mesh and an eval before the handle holds a state.  NSX_ERR_UNSUPPORTED for a (dim, n_p2) other than (2, 6) / (3, 10), for
+ * n_total > 2^26 (checked before anything is allocated) and for a handle with more than one process (merging the ranks' lattices is out of
+ * scope; a 1-rank communicator works, as for the tracers). */
+enum { NSX_LATTICE_VELOCITY = 1, NSX_LATTICE_PRESSURE = 2, NSX_LATTICE_GRADIENT = 4, NSX_LATTICE_NODAL = 8 };
+/* Installs the lattice and finds the owner of every point; *n_found (may be NULL) = points that lie in a cell. */
+int nsx_set_lattice(nsx_handle *h, const double *origin /*[dim]*/, const double *spacing /*[dim]*/, const int32_t *counts /*[dim]*/, double tol,
+                    int64_t *n_found);
+/* cells[n_total]: position of the point's cell in the caller's cell list, -1: in no cell. */
+int nsx_get_lattice_cells(nsx_handle *h, int32_t *cells /*[n_total]*/);
+/* Samples what `what` names from the state the handle holds. */
+int nsx_eval_lattice(nsx_handle *h, int what);
+/* One quantity of the last nsx_eval_lattice. */
+int nsx_get_lattice(nsx_handle *h, int quantity, int which, double *values /*[n_components][n_total]*/);
+
 /* ---- measurement ---- */
 /* Per-kernel HIP-event timing of the hot path (bench.py roofline): enable, run, then read name/count/total-ms. */
 int nsx_profile_enable(nsx_handle *h, int on);

@@ -171,6 +171,14 @@ int nsxh_write_vtu(const nsxh_dofs *, const double *solution, const char *direct
 int nsxh_write_vtu_fields(const nsxh_dofs *, const double *solution, const double *vorticity, int n_vorticity, const double *q_criterion,
                           const char *directory, const char *basename, unsigned counter);
 
+/* A lattice of nsx_set_lattice as VTK ImageData, <directory>/<basename>_<counter>.vti (ASCII data arrays; the directory is created if
+ * missing): WholeExtent, Origin and Spacing from the lattice (a third axis of one point in 2D), and as PointData in the lattice's own order
+ * (x fastest) "velocity" (3 components, the third 0 in 2D; velocity[dim][n_total] as nsx_get_lattice hands it out), "pressure"
+ * (pressure[n_total]), the mask "cell_id" (cells[n_total] of nsx_get_lattice_cells: -1 outside the mesh) and, when vorticity is not NULL,
+ * "vorticity" (vorticity[n_vorticity][n_total], n_vorticity = 3 in 3D, 1 in 2D).  No counterpart in the reference.  0 on success. */
+int nsxh_write_vti(int dim, const double *origin, const double *spacing, const int32_t *counts, const double *velocity, const double *pressure,
+                   const int32_t *cells, const double *vorticity, int n_vorticity, const char *directory, const char *basename, unsigned counter);
+
 /* NavierStokes::compute_pressure_difference (reference NavierStokes3D.cpp:849-923): P1 pressure at two points
  * (VectorTools::point_value): p(a) - p(b).  A point outside the mesh contributes 0 like a rank that does not hold it.
  * Returns the number of points found (0..2). */

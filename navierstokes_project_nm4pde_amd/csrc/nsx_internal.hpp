@@ -386,6 +386,30 @@ struct IsoState {
   }
 };
 
+// Lattice sampling (nsx_lattice.hip).  The owner table is in the caller's cell order: lattice and results outlive a new layout / rank table,
+// not a new mesh.  Nothing is stored per point but the owning cell.
+struct LatticeState {
+  bool set = false;                 // a lattice is installed
+  double origin[3] = {0, 0, 0}, spacing[3] = {1, 1, 1}, tol = 0.0;  // tol: the containment tolerance the owners were found with
+  int32_t counts[3] = {1, 1, 1};
+  int64_t n_total = 0, n_found = 0; // points of the lattice, points that lie in a cell
+  DevBuf<int32_t> owner;            // [n_total] position of the owning cell in the caller's cell list, -1: in no cell
+  DevBuf<double> vel, pres, grad, nodal;  // SoA planes [dim | 1 | dim^2 | nodal_planes(dim)][n_total] of the last nsx_eval_lattice; allocated by the
+                                          // first one that asks for them and kept by a new lattice (what = 0) for the next evaluation to reuse
+  int what = 0;                     // the NSX_LATTICE_* bits the last nsx_eval_lattice computed (0: no results)
+  void clear() {                    // gives the lattice, its results and their memory up
+    set = false;
+    what = 0;
+    n_total = n_found = 0;
+    owner.release();
+    vel.release();
+    pres.release();
+    grad.release();
+    nodal.release();
+  }
+  void mesh_changed() { clear(); }  // a new mesh drops the lattice and its results
+};
+
 struct Comm;  // RCCL state (nsx_comm.hip)
 
 enum { N_SLOTS = 128 };  // device scalar slots (reduction results)
@@ -508,6 +532,7 @@ struct nsx_handle {
   nsx::TracerState tracer;  // nsx_tracer.hip
   nsx::NodalState nodal;    // nsx_nodal.hip
   nsx::IsoState iso;        // nsx_iso.hip
+  nsx::LatticeState lattice;  // nsx_lattice.hip
   // ---- profiling
   bool prof_on = false;
   std::map<std::string, nsx::ProfEntry> prof;
@@ -571,6 +596,7 @@ inline void post_mesh_changed(nsx_handle *h) {
   h->tracer.mesh_changed();
   h->nodal.mesh_changed();
   h->iso.mesh_changed();
+  h->lattice.mesh_changed();
 }
 
 // sparse (nsx_sparse.hip)

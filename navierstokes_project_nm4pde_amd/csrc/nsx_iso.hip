@@ -289,7 +289,7 @@ static double iso_source_bytes(const IsoSrc &q, int dim) {
 }
 
 // vertex coordinates of the cells, SoA, and the orientation of every cell: by the first extract on a mesh (cells are never renumbered)
-static void iso_ensure_coords(nsx_handle *h) {
+void iso_ensure_coords(nsx_handle *h) {
   if (h->iso.have_coords) return;
   const int dim = h->dim, nv = dim + 1, nc = h->n_cells;
   if (h->cell_coords_in.size() != (size_t)nc * nv * dim) NSX_THROW(NSX_ERR_ARG, "nsx_extract_isosurface: the handle holds no cell coordinates");
@@ -347,7 +347,7 @@ static void iso_ensure_maps(nsx_handle *h) {
 }
 
 // internal node -> slot of nodal.out, from the layout's node permutation and nodal.slot_of (caller-local owned node -> slot)
-static void iso_ensure_slots(nsx_handle *h) {
+void iso_ensure_slots(nsx_handle *h) {
   if (h->iso.slot_epoch == h->layout_epoch) return;
   const size_t n_slots = (size_t)h->nodal.tiles * NODAL_TILE;
   std::vector<int32_t> slot((size_t)h->N2_loc, -1);

@@ -1,6 +1,6 @@
-// nsx_post.hpp — what the post-processing files share (nsx_diag, nsx_probe, nsx_tracer, nsx_nodal, nsx_iso): the affine cell map, the P2
+// nsx_post.hpp — what the post-processing files share (nsx_diag, nsx_probe, nsx_tracer, nsx_nodal, nsx_iso, nsx_lattice): the affine cell map, the P2
 // shape functions in barycentric form, the push-forward of a reference gradient, the space check and the layout of the nodal results.
-// Their state lives in nsx_internal.hpp (DiagState ... IsoState), and so does the guard of their C entries (NSX_TRY / NSX_CATCH).
+// Their state lives in nsx_internal.hpp (DiagState ... LatticeState), and so does the guard of their C entries (NSX_TRY / NSX_CATCH).
 #pragma once
 #include "nsx_internal.hpp"
 
@@ -101,5 +101,10 @@ inline int nodal_first_plane(int dim, int which) {
   for (int f = 0; f < which; ++f) p += nodal_components(dim, f);
   return p;
 }
+
+// what nsx_iso.hip keeps on the device for itself and for nsx_lattice.hip: the vertex coordinates of every cell (iso.cellx, uploaded by the
+// first caller on a mesh) and the map internal P2 node -> slot of nodal.out (iso.slot, rebuilt when the layout has moved)
+void iso_ensure_coords(nsx_handle *h);
+void iso_ensure_slots(nsx_handle *h);
 
 }  // namespace nsx

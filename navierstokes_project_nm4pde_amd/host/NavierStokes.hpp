@@ -16,6 +16,7 @@
 #include <iomanip>
 #include <iostream>
 #include <map>
+#include <sstream>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -128,6 +129,7 @@ public:
       }
       ck(nsx_set_tracers(h, n_tracers, seeds.data(), -1.0));
     }
+    if (!lattice_counts.empty()) setup_lattice();
   }
 
   void solve() {  // NavierStokes3D.cpp:687-741
@@ -215,6 +217,7 @@ public:
           throw std::runtime_error("cannot write " + output_file_name);
       } else if (nsxh_write_vtu(dofs, x.data(), directory, output_file_name.c_str(), time_step))
         throw std::runtime_error("cannot write " + output_file_name);
+      if (!lattice_counts.empty()) write_lattice(time_step, directory);
       out() << "Output written to " << output_file_name << std::endl;
     }
     if (dim == 2 && write_csv) {
@@ -343,6 +346,57 @@ protected:
     }
   }
 
+  // opt-in image (NSX_LATTICE="nx,ny[,nz]"): a lattice of that many points spanning the bounding box of the mesh, located once
+  void setup_lattice() {
+    if ((int)lattice_counts.size() != dim) throw std::runtime_error("NSX_LATTICE: " + std::to_string(dim) + " counts of at least 1, separated by commas");
+    const double *X = nsxh_cell_coords(dofs);
+    const size_t n_vertices = (size_t)nsxh_mesh_n_cells(mesh) * (dim + 1);
+    for (int d = 0; d < dim; ++d) {
+      double lo = X[d], hi = X[d];
+      for (size_t v = 1; v < n_vertices; ++v) {
+        lo = std::min(lo, X[v * dim + d]);
+        hi = std::max(hi, X[v * dim + d]);
+      }
+      const int32_t n = lattice_counts[d];
+      lattice_origin[d] = n > 1 ? lo : (lo + hi) / 2;
+      lattice_spacing[d] = n > 1 ? (hi - lo) / (n - 1) : 1.0;
+    }
+    ck(nsx_set_lattice(h, lattice_origin, lattice_spacing, lattice_counts.data(), -1.0, nullptr));
+  }
+
+  // ... and at every output() velocity, pressure and, with NSX_FIELDS=1, the vorticity of the state are sampled on it on the device and
+  // written beside the VTU as lattice-navier-stokes-{2D,3D}_<step>.vti, with the owner cells as the mask "cell_id"
+  void write_lattice(const unsigned int time_step, const char *directory) const {
+    size_t n = 1;
+    for (const int32_t c : lattice_counts) n *= (size_t)c;
+    const int n_vorticity = dim == 3 ? 3 : 1;
+    std::vector<double> velocity(n * dim), pressure(n), vorticity(fields_vtu ? n * n_vorticity : 0);
+    std::vector<int32_t> cells(n);
+    ck(nsx_eval_lattice(h, NSX_LATTICE_VELOCITY | NSX_LATTICE_PRESSURE | (fields_vtu ? NSX_LATTICE_NODAL : 0)));  // output() has computed the nodal fields
+    ck(nsx_get_lattice(h, NSX_LATTICE_VELOCITY, 0, velocity.data()));
+    ck(nsx_get_lattice(h, NSX_LATTICE_PRESSURE, 0, pressure.data()));
+    if (fields_vtu) ck(nsx_get_lattice(h, NSX_LATTICE_NODAL, NSX_FIELD_VORTICITY, vorticity.data()));
+    ck(nsx_get_lattice_cells(h, cells.data()));
+    if (nsxh_write_vti(dim, lattice_origin, lattice_spacing, lattice_counts.data(), velocity.data(), pressure.data(), cells.data(),
+                       fields_vtu ? vorticity.data() : nullptr, n_vorticity, directory, dim == 3 ? "lattice-navier-stokes-3D" : "lattice-navier-stokes-2D", time_step))
+      throw std::runtime_error("cannot write the lattice file");
+  }
+
+  static std::vector<int32_t> parse_counts(const char *text) {  // "nx,ny[,nz]"; anything else: one entry 0, which setup_lattice refuses
+    std::vector<int32_t> counts;
+    if (!text || !*text) return counts;
+    std::stringstream in(text);
+    std::string item;
+    while (std::getline(in, item, ',')) {
+      char *end = nullptr;
+      const long v = std::strtol(item.c_str(), &end, 10);
+      counts.push_back(end != item.c_str() && *end == 0 && v >= 1 && v <= (1 << 26) ? (int32_t)v : 0);
+    }
+    for (const int32_t c : counts)
+      if (c == 0) return std::vector<int32_t>(4, 0);
+    return counts;
+  }
+
   void setup_force_faces() {  // faces with boundary id 3 and the face-quadrature tables (FEFaceValues of compute_forces)
     static const int TETF[4][3] = {{0, 1, 2}, {1, 0, 3}, {0, 2, 3}, {2, 1, 3}};
     static const int TRIF[3][2] = {{0, 1}, {1, 2}, {2, 0}};
@@ -395,6 +449,8 @@ protected:
   const bool diagnostics_csv = std::getenv("NSX_DIAGNOSTICS") && std::string(std::getenv("NSX_DIAGNOSTICS")) == "1";
   const bool probes_csv = std::getenv("NSX_PROBES") && std::string(std::getenv("NSX_PROBES")) == "1";
   const bool fields_vtu = std::getenv("NSX_FIELDS") && std::string(std::getenv("NSX_FIELDS")) == "1";
+  const std::vector<int32_t> lattice_counts = parse_counts(std::getenv("NSX_LATTICE"));
+  double lattice_origin[3] = {0.0, 0.0, 0.0}, lattice_spacing[3] = {1.0, 1.0, 1.0};
   const int n_tracers = std::getenv("NSX_TRACERS") ? std::max(0, std::min(1048576, std::atoi(std::getenv("NSX_TRACERS")))) : 0;
 };
 

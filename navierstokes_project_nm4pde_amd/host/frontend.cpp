@@ -1355,6 +1355,47 @@ int nsxh_write_vtu_fields(const nsxh_dofs *d, const double *solution, const doub
   return pv ? 0 : -1;
 }
 
+// A lattice of nsx_set_lattice as VTK ImageData, <directory>/<basename>_<counter>.vti: the planes of nsx_get_lattice as PointData -- "velocity"
+// (3 components, the third 0 in 2D), "pressure", the mask "cell_id" (nsx_get_lattice_cells: -1 outside the mesh) and, when given, "vorticity".
+int nsxh_write_vti(int dim, const double *origin, const double *spacing, const int32_t *counts, const double *velocity, const double *pressure,
+                   const int32_t *cells, const double *vorticity, int n_vorticity, const char *directory, const char *basename, unsigned counter) {
+  if ((dim != 2 && dim != 3) || !origin || !spacing || !counts || !velocity || !pressure || !cells || !directory || !basename) return -1;
+  if (vorticity && n_vorticity != 1 && n_vorticity != 3) return -1;
+  size_t n = 1;
+  for (int d = 0; d < dim; ++d) {
+    if (counts[d] < 1) return -1;
+    n *= (size_t)counts[d];
+  }
+  std::string dir(directory);
+  if (!dir.empty() && dir.back() != '/') dir += '/';
+  for (size_t pos = 1; pos < dir.size(); ++pos)  // mkdir -p
+    if (dir[pos] == '/') ::mkdir(dir.substr(0, pos).c_str(), 0777);
+  std::ofstream f(dir + std::string(basename) + "_" + std::to_string(counter) + ".vti");
+  if (!f) return -1;
+  f << std::setprecision(17);
+  f << "<?xml version=\"1.0\"?>\n<VTKFile type=\"ImageData\" version=\"0.1\" byte_order=\"LittleEndian\">\n<ImageData WholeExtent=\"";
+  for (int d = 0; d < 3; ++d) f << "0 " << (d < dim ? counts[d] - 1 : 0) << (d < 2 ? " " : "\" Origin=\"");
+  for (int d = 0; d < 3; ++d) f << (d < dim ? origin[d] : 0.0) << (d < 2 ? " " : "\" Spacing=\"");
+  for (int d = 0; d < 3; ++d) f << (d < dim ? spacing[d] : 1.0) << (d < 2 ? " " : "\">\n<Piece Extent=\"");
+  for (int d = 0; d < 3; ++d) f << "0 " << (d < dim ? counts[d] - 1 : 0) << (d < 2 ? " " : "\">\n");
+  f << "<PointData Scalars=\"pressure\" Vectors=\"velocity\">\n<DataArray type=\"Float64\" Name=\"velocity\" NumberOfComponents=\"3\" format=\"ascii\">\n";
+  for (size_t p = 0; p < n; ++p) f << velocity[p] << ' ' << velocity[n + p] << ' ' << (dim == 3 ? velocity[2 * n + p] : 0.0) << '\n';
+  f << "</DataArray>\n<DataArray type=\"Float64\" Name=\"pressure\" format=\"ascii\">\n";
+  for (size_t p = 0; p < n; ++p) f << pressure[p] << ((p + 1) % 8 ? ' ' : '\n');
+  f << "\n</DataArray>\n<DataArray type=\"Int32\" Name=\"cell_id\" format=\"ascii\">\n";
+  for (size_t p = 0; p < n; ++p) f << cells[p] << ((p + 1) % 16 ? ' ' : '\n');
+  f << "\n</DataArray>\n";
+  if (vorticity) {
+    f << "<DataArray type=\"Float64\" Name=\"vorticity\" NumberOfComponents=\"" << n_vorticity << "\" format=\"ascii\">\n";
+    for (size_t p = 0; p < n; ++p)
+      for (int k = 0; k < n_vorticity; ++k) f << vorticity[(size_t)k * n + p] << (k + 1 == n_vorticity ? '\n' : ' ');
+    f << "</DataArray>\n";
+  }
+  f << "</PointData>\n</Piece>\n</ImageData>\n</VTKFile>\n";
+  f.close();
+  return f ? 0 : -1;
+}
+
 int nsxh_pressure_difference(const nsxh_dofs *d, const double *solution, const double *pa, const double *pb, double *diff) {
   if (!d || !solution || !pa || !pb || !diff) return -1;
   const int dim = d->dim, nv = dim + 1;

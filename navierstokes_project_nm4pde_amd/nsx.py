@@ -29,6 +29,7 @@ API = [
     "nsx_set_probes", "nsx_get_probe_cells", "nsx_eval_probes", "nsx_set_tracers", "nsx_advect_tracers", "nsx_get_tracers",
     "nsx_sparse_product", "nsx_compute_nodal_fields", "nsx_nodal_field_components", "nsx_get_nodal_field",
     "nsx_extract_isosurface", "nsx_get_isosurface",
+    "nsx_set_lattice", "nsx_get_lattice_cells", "nsx_eval_lattice", "nsx_get_lattice",
 ]
 # declared in include/nsx.h as well, but with a capital letter in its name, which the header scan of tests/test_abi.py (lower case only)
 # does not see: kept beside the list that scan is compared with; build() checks both
@@ -46,6 +47,8 @@ TRACER_NOT_FOUND, TRACER_ACTIVE, TRACER_EXITED, TRACER_LOST = 0, 1, 2, 3        
 FIELD_GRADIENT, FIELD_VORTICITY, FIELD_Q, FIELD_STRAIN, FIELD_DIVERGENCE, FIELD_COUNT = range(6)
 # source kinds of nsx_extract_isosurface (NSX_ISO_*)
 ISO_VELOCITY, ISO_PRESSURE, ISO_NODAL, ISO_PLANE = range(4)
+# quantities of nsx_eval_lattice / nsx_get_lattice (NSX_LATTICE_*): bits
+LATTICE_VELOCITY, LATTICE_PRESSURE, LATTICE_GRADIENT, LATTICE_NODAL = 1, 2, 4, 8
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, _f64p, C.c_int)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(_f64p), C.POINTER(C.c_int),
@@ -157,6 +160,10 @@ def lib():
     L.nsx_get_nodal_field.argtypes = [vp, C.c_int, _f64p]
     L.nsx_extract_isosurface.argtypes = [vp, C.POINTER(IsoSource), C.c_double, C.POINTER(IsoSource), C.POINTER(C.c_int64)]
     L.nsx_get_isosurface.argtypes = [vp, _f64p, _f64p, _i32p]
+    L.nsx_set_lattice.argtypes = [vp, _f64p, _f64p, _i32p, C.c_double, C.POINTER(C.c_int64)]
+    L.nsx_get_lattice_cells.argtypes = [vp, _i32p]
+    L.nsx_eval_lattice.argtypes = [vp, C.c_int]
+    L.nsx_get_lattice.argtypes = [vp, C.c_int, C.c_int, _f64p]
     L.nsx_set_inner_precision.argtypes = [vp, C.c_int]
     L.nsx_inner_F_vmult.argtypes = [vp, _f64p, _f64p]
     L.nsx_schur_cg.argtypes = [vp, C.c_double, C.c_int, _f64p, _f64p, C.POINTER(C.c_int), _f64p, C.POINTER(C.c_int)]
@@ -627,6 +634,46 @@ class Nsx:
         col = np.empty((n.value, self.dim)) if colour is not None else None
         self._ck(self.L.nsx_get_isosurface(self._h, _d(pts), _d(col) if col is not None else None, _i(cells)))
         return pts, col, cells
+
+    # -- lattice sampling ----------------------------------------------------------------------
+    def set_lattice(self, origin, spacing, counts, tol=-1.0):
+        """nsx_set_lattice: the lattice x_d = origin_d + i_d * spacing_d, i_d < counts_d (x fastest), every point located once; returns
+        n_found, the points that lie in a cell.  origin = spacing = counts = None clears the lattice."""
+        n = C.c_int64(0)
+        if origin is None and spacing is None and counts is None:
+            self._ck(self.L.nsx_set_lattice(self._h, None, None, None, float(tol), C.byref(n)))
+            self._lattice_counts = None
+            return 0
+        o, s, c = _cd(origin), _cd(spacing), _ci(counts)
+        if not (o.shape == s.shape == c.shape == (self.dim,)):
+            raise ValueError("origin, spacing and counts have dim = %d entries each" % self.dim)
+        self._ck(self.L.nsx_set_lattice(self._h, _d(o), _d(s), _i(c), float(tol), C.byref(n)))
+        self._lattice_counts = tuple(int(k) for k in c)      # a refused call leaves the earlier lattice (and its shape) in place
+        return int(n.value)
+
+    def _lattice_shape(self):
+        counts = getattr(self, "_lattice_counts", None)
+        return counts[::-1] if counts else (0,)
+
+    def lattice_cells(self):
+        """owning cell of every lattice point, shaped counts[::-1] (x fastest), -1: in no cell (nsx_get_lattice_cells)"""
+        cells = np.empty(self._lattice_shape(), np.int32)
+        self._ck(self.L.nsx_get_lattice_cells(self._h, _i(cells)))
+        return cells
+
+    def eval_lattice(self, what):
+        """nsx_eval_lattice: sample `what` (an OR of LATTICE_*) from the state the handle holds; get_lattice() hands the planes out"""
+        self._ck(self.L.nsx_eval_lattice(self._h, int(what)))
+
+    def get_lattice(self, quantity, which=0):
+        """[n_components, *counts[::-1]] of one quantity (LATTICE_*; which = FIELD_* for LATTICE_NODAL) as the last eval_lattice() left it:
+        dim velocity components, 1 pressure, dim^2 gradient entries (row-major d_j u_i), the components of the nodal field"""
+        dim = self.dim
+        nc = {LATTICE_VELOCITY: dim, LATTICE_PRESSURE: 1, LATTICE_GRADIENT: dim * dim,
+              LATTICE_NODAL: {FIELD_GRADIENT: dim * dim, FIELD_VORTICITY: 3 if dim == 3 else 1}.get(which, 1)}.get(quantity, 1)
+        out = np.empty((nc,) + self._lattice_shape())
+        self._ck(self.L.nsx_get_lattice(self._h, int(quantity), int(which), _d(out)))
+        return out
 
     # -- export --------------------------------------------------------------------------------
     def export_block(self, which, block, graph=None):
