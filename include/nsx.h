@@ -545,6 +545,58 @@ int nsx_eval_lattice(nsx_handle *h, int what);
 /* One quantity of the last nsx_eval_lattice. */
 int nsx_get_lattice(nsx_handle *h, int quantity, int which, double *values /*[n_components][n_total]*/);
 
+/* ---- running statistics ---- */
+/* The time-averaged flow and its fluctuations, accumulated on the device one sample per call from the state the handle holds: weighted mean of
+ * velocity and pressure, the co-moments sum w u'_i u'_j (Reynolds stresses, rms, turbulent kinetic energy) and the pressure variance, in up to
+ * 64 phase bins (the caller decides which bin a time step belongs to: a phase-averaged flow of a periodic shedding), each bin on its own or all
+ * pooled.  No counterpart in the reference (its output() writes snapshots only).  csrc/nsx_stats.hip.
+ * Accumulators: per bin a weight sum W and a sample count on the host; on the device, per P2 node this handle owns, the mean m_c (dim planes)
+ * and the upper triangle of the co-moment C_ij (3 or 6 planes), and per owned P1 node m and C (2 planes).  Symmetric component order:
+ * xx, yy, [zz,] xy[, xz, yz].  The planes are kept in the CALLER's node numbering, so an accumulation survives nsx_set_ranks and
+ * nsx_set_internal_layout untouched (hand the state over again after a new layout, as always); a new nsx_set_mesh(_distributed) drops it.
+ * The recurrence (a contract: the results are reproducible to the bit from it).  For a sample x of weight w > 0 into a bin with weight W (0 when
+ * empty) the host forms three doubles, one rounded operation each,
+ *     W' = W + w,   r = w / W',   q = W * r,
+ * and the device does per DoF and per pair i <= j, every operation an IEEE double operation rounded on its own, never a fused multiply-add,
+ *     d_i  = x_i - m_i
+ *     m_i  = m_i + r * d_i                 (product, then sum)
+ *     C_ij = C_ij + (q * d_i) * d_j        (left to right; d from before the mean moved)
+ * With q >= 0 the diagonal increments are q times a square: C_ii never decreases and no variance is negative.  The first sample of a bin has
+ * r = 1, q = 0: m = x and C = 0 exactly.
+ * Quantities (nsx_stats_get; computed on the device from the raw planes, the host passes invW = 1 / W): NSX_STATS_MEAN_U [dim] and
+ * NSX_STATS_COMOMENT_U [3 | 6] are the raw planes; NSX_STATS_STRESS_U [3 | 6] = C_ij * invW; NSX_STATS_RMS_U [dim] = sqrt(C_ii * invW);
+ * NSX_STATS_TKE [1] = 0.5 * (R_00 + R_11 [+ R_22]) with R = the stresses, summed left to right, then halved; NSX_STATS_MEAN_P,
+ * NSX_STATS_COMOMENT_P, NSX_STATS_VAR_P = C * invW and NSX_STATS_RMS_P = sqrt(C * invW) [1 each].
+ * Pooled (bin = -1): the non-empty bins are folded in ascending order with the pairwise merge (a, b) -> a; the host forms W = W_a + W_b,
+ * s = W_b / W, t = W_a * s, the device per node, in registers, delta_i = m_b,i - m_a,i, C_ij = (C_a,ij + C_b,ij) + (t * delta_i) * delta_j,
+ * m_i = m_a,i + s * delta_i (C first: delta and m_a from before the mean moved), then the quantity with invW = 1 / W of the fold.  The
+ * accumulators themselves are not modified.
+ * nsx_stats_accumulate reads state only (the ghosted `solution`, current after nsx_set_solution and nsx_solve_time_step): no vector, matrix
+ * or solver state changes and a following solve computes bitwise what it would have computed without the call.  A state value that is not
+ * finite sticks in the accumulators of its own DoF only; the call returns NSX_OK.  The values do not depend on the scheduling, the rank
+ * tables or the internal layout.  Distributed handles accumulate the nodes they own and issue no collective and no ghost exchange
+ * (nsx_comm_counters does not move); the ranks need not call together.  nsx_stats_get is indexed globally and fills only the entries this
+ * rank owns, as nsx_get_nodal_field does; they are bitwise those of a single-process handle.
+ * Errors: NSX_ERR_ARG for a null handle or output pointer (nsx_stats_info: any pointer may be NULL), a call before tables, mesh or (accumulate)
+ * a state, accumulate / info / get without an open accumulation, `what` with unknown bits, exactly one of what / n_bins zero, n_bins outside
+ * 1..64, a bin out of range, a weight that is not finite or <= 0, an unknown quantity, a get of a quantity whose part (`what`) is not
+ * accumulated, a get from an empty bin or pooled with all bins empty; NSX_ERR_UNSUPPORTED for a (dim, n_p2) other than (2, 6) / (3, 10).  A
+ * refused call leaves the accumulation as it was. */
+enum { NSX_STATS_VELOCITY = 1, NSX_STATS_PRESSURE = 2 };
+/* Opens (or, with what = 0 and n_bins = 0, closes and frees) an accumulation: zeroed accumulators for n_bins phase bins, 1 <= n_bins <= 64. */
+int nsx_stats_begin(nsx_handle *h, int what, int n_bins);
+/* Adds the state the handle holds as one sample of weight `weight` to bin `bin`.  One kernel launch. */
+int nsx_stats_accumulate(nsx_handle *h, int bin, double weight);
+/* what, n_bins, samples[n_bins], weights[n_bins] (the running W of each bin); any pointer may be NULL. */
+int nsx_stats_info(nsx_handle *h, int *what, int *n_bins, int64_t *samples, double *weights);
+enum { NSX_STATS_MEAN_U = 0, NSX_STATS_COMOMENT_U, NSX_STATS_STRESS_U, NSX_STATS_RMS_U, NSX_STATS_TKE,
+       NSX_STATS_MEAN_P, NSX_STATS_COMOMENT_P, NSX_STATS_VAR_P, NSX_STATS_RMS_P, NSX_STATS_QUANTITY_COUNT };
+/* Components per node of a quantity (needs a mesh, not an open accumulation). */
+int nsx_stats_components(nsx_handle *h, int quantity, int *n_components);
+/* values[n_nodes][n_components] (P2 nodes for the velocity quantities, P1 nodes for the pressure's); bin >= 0: that bin; bin = -1: all
+ * non-empty bins pooled. */
+int nsx_stats_get(nsx_handle *h, int quantity, int bin, double *values);
+
 /* ---- measurement ---- */
 /* Per-kernel HIP-event timing of the hot path (bench.py roofline): enable, run, then read name/count/total-ms. */
 int nsx_profile_enable(nsx_handle *h, int on);

@@ -171,6 +171,15 @@ int nsxh_write_vtu(const nsxh_dofs *, const double *solution, const char *direct
 int nsxh_write_vtu_fields(const nsxh_dofs *, const double *solution, const double *vorticity, int n_vorticity, const double *q_criterion,
                           const char *directory, const char *basename, unsigned counter);
 
+/* The running statistics of nsx_stats_get on the mesh of nsxh_write_vtu, one file <directory>/<basename>.vtu (ASCII data arrays; the directory
+ * is created if missing): points, cells and "partitioning" as nsxh_write_vtu writes them, and as PointData at the cell vertices
+ * "mean_velocity" and "rms_velocity" (3 components, the third 0 in 2D), "mean_pressure", "reynolds_stress" (6 components in VTK's symmetric
+ * tensor order XX YY ZZ XY YZ XZ; in 2D ZZ, YZ and XZ are 0) and "tke".  mean_u[n_nodes][dim], rms_u[n_nodes][dim],
+ * stress[n_nodes][dim (dim + 1) / 2] (the library's order xx, yy, [zz,] xy[, xz, yz]) and tke[n_nodes] are indexed by P2 node, mean_p[n_p] by
+ * P1 node, in the global numbering (NSX_STATS_MEAN_U, _RMS_U, _STRESS_U, _TKE, _MEAN_P).  No counterpart in the reference.  0 on success. */
+int nsxh_write_vtu_stats(const nsxh_dofs *, const double *mean_u, const double *mean_p, const double *rms_u, const double *stress, const double *tke,
+                         const char *directory, const char *basename);
+
 /* A lattice of nsx_set_lattice as VTK ImageData, <directory>/<basename>_<counter>.vti (ASCII data arrays; the directory is created if
  * missing): WholeExtent, Origin and Spacing from the lattice (a third axis of one point in 2D), and as PointData in the lattice's own order
  * (x fastest) "velocity" (3 components, the third 0 in 2D; velocity[dim][n_total] as nsx_get_lattice hands it out), "pressure"

@@ -16,6 +16,8 @@
 //                  patch size (the nodal fields' gather, built on demand: host/nodal_patch.hpp; NodalState)
 //   iso tables     iso.cellx[(v dim + d)][cell] vertex coordinates, node maps in the internal numbering (P2 node -> P1 nodes, position, slot of
 //                  the nodal results), built on demand (the isosurface extraction: nsx_iso.hip; IsoState)
+//   stats planes   per phase bin and owned node, in the caller's numbering: mean and co-moment of velocity and pressure (the running statistics:
+//                  nsx_stats.hip; StatsState)
 //   gather maps    per CSR entry the list of (local entry, cell) contributions -> deterministic assembly, no atomics
 #pragma once
 #include <hip/hip_runtime.h>
@@ -410,6 +412,28 @@ struct LatticeState {
   void mesh_changed() { clear(); }  // a new mesh drops the lattice and its results
 };
 
+// Running statistics (nsx_stats.hip).  The accumulator planes are in the CALLER's node numbering: an accumulation outlives a new layout / rank
+// table, not a new mesh.
+struct StatsState {
+  int what = 0, n_bins = 0;         // NSX_STATS_* bits and phase bins of the open accumulation (0, 0: none)
+  size_t stride2 = 0, stride1 = 0;  // entries per plane: the owned P2 / P1 nodes rounded up to a multiple of 64 (the kernels take two nodes per lane)
+  DevBuf<double> vel;               // SoA [n_bins][dim + dim (dim + 1) / 2][stride2]: mean, then co-moment xx, yy, [zz,] xy[, xz, yz]
+  DevBuf<double> pres;              // SoA [n_bins][2][stride1]: mean, co-moment
+  DevBuf<double> out;               // [n_nodes][n_components] of the last nsx_stats_get on its way to the host
+  std::vector<double> W;            // [n_bins] weight sums
+  std::vector<int64_t> samples;     // [n_bins]
+  void clear() {                    // gives the accumulation and its memory up
+    what = n_bins = 0;
+    stride2 = stride1 = 0;
+    vel.release();
+    pres.release();
+    out.release();
+    W.clear();
+    samples.clear();
+  }
+  void mesh_changed() { clear(); }  // a new mesh drops the accumulation
+};
+
 struct Comm;  // RCCL state (nsx_comm.hip)
 
 enum { N_SLOTS = 128 };  // device scalar slots (reduction results)
@@ -533,6 +557,7 @@ struct nsx_handle {
   nsx::NodalState nodal;    // nsx_nodal.hip
   nsx::IsoState iso;        // nsx_iso.hip
   nsx::LatticeState lattice;  // nsx_lattice.hip
+  nsx::StatsState stats;    // nsx_stats.hip
   // ---- profiling
   bool prof_on = false;
   std::map<std::string, nsx::ProfEntry> prof;
@@ -597,6 +622,7 @@ inline void post_mesh_changed(nsx_handle *h) {
   h->nodal.mesh_changed();
   h->iso.mesh_changed();
   h->lattice.mesh_changed();
+  h->stats.mesh_changed();
 }
 
 // sparse (nsx_sparse.hip)

@@ -151,6 +151,7 @@ public:
       if (diagnostics_csv) write_diagnostics(time_step, time);
       if (probes_csv) write_pressure_difference(time_step, time);
       if (n_tracers > 0) write_tracers(time_step, time);
+      if (stats_first > 0 && time_step >= (unsigned int)stats_first) accumulate_statistics();
       // NavierStokes3D.cpp:725-726, as written: an EXACT floating-point comparison of the accumulated time with T - deltat (true or false
       // by the rounding of the additions; the reference's own run decides it the same way, so the mirror does not "repair" it)
       if (dim == 3 && time == T - deltat) compute_pressure_difference();
@@ -163,6 +164,7 @@ public:
       }
       if (time_step % (dim == 3 ? 20 : 1) == 0) output(time_step, coefficients);  // NavierStokes3D.cpp:734, NavierStokes2D.cpp:743
     }
+    if (stats_open) write_statistics();
     out() << "===============================================" << std::endl
           << "Drag Coefficient Max ----->   " << c_D_max << std::endl
           << std::endl
@@ -346,6 +348,31 @@ protected:
     }
   }
 
+  // opt-in statistics (NSX_STATS=<first step>): from that time step on velocity and pressure of every step go into one running mean and
+  // co-moment on the device with weight deltat (nsx_stats_accumulate, one launch per step, nothing is downloaded) ...
+  void accumulate_statistics() {
+    if (!stats_open) ck(nsx_stats_begin(h, NSX_STATS_VELOCITY | NSX_STATS_PRESSURE, 1));
+    stats_open = true;
+    ck(nsx_stats_accumulate(h, 0, deltat));
+  }
+
+  // ... and after the last step the time-averaged flow is written to stats_{2D,3D}.vtu: mean velocity, mean pressure, rms velocity, the
+  // Reynolds stresses and the turbulent kinetic energy
+  void write_statistics() const {
+    const size_t n_nodes = (size_t)(n_u / dim), nsym = (size_t)dim * (dim + 1) / 2;
+    std::vector<double> mean_u(n_nodes * dim), mean_p((size_t)n_p), rms_u(n_nodes * dim), stress(n_nodes * nsym), tke(n_nodes);
+    ck(nsx_stats_get(h, NSX_STATS_MEAN_U, 0, mean_u.data()));
+    ck(nsx_stats_get(h, NSX_STATS_MEAN_P, 0, mean_p.data()));
+    ck(nsx_stats_get(h, NSX_STATS_RMS_U, 0, rms_u.data()));
+    ck(nsx_stats_get(h, NSX_STATS_STRESS_U, 0, stress.data()));
+    ck(nsx_stats_get(h, NSX_STATS_TKE, 0, tke.data()));
+    if (nsxh_write_vtu_stats(dofs, mean_u.data(), mean_p.data(), rms_u.data(), stress.data(), tke.data(), "./", dim == 3 ? "stats_3D" : "stats_2D"))
+      throw std::runtime_error("cannot write the statistics file");
+    int64_t samples = 0;
+    ck(nsx_stats_info(h, nullptr, nullptr, &samples, nullptr));
+    out() << "Statistics of " << samples << " time steps written to " << (dim == 3 ? "stats_3D.vtu" : "stats_2D.vtu") << std::endl;
+  }
+
   // opt-in image (NSX_LATTICE="nx,ny[,nz]"): a lattice of that many points spanning the bounding box of the mesh, located once
   void setup_lattice() {
     if ((int)lattice_counts.size() != dim) throw std::runtime_error("NSX_LATTICE: " + std::to_string(dim) + " counts of at least 1, separated by commas");
@@ -451,6 +478,8 @@ protected:
   const bool fields_vtu = std::getenv("NSX_FIELDS") && std::string(std::getenv("NSX_FIELDS")) == "1";
   const std::vector<int32_t> lattice_counts = parse_counts(std::getenv("NSX_LATTICE"));
   double lattice_origin[3] = {0.0, 0.0, 0.0}, lattice_spacing[3] = {1.0, 1.0, 1.0};
+  const int stats_first = std::getenv("NSX_STATS") ? std::max(0, std::atoi(std::getenv("NSX_STATS"))) : 0;  // first time step of the statistics (0: none)
+  bool stats_open = false;
   const int n_tracers = std::getenv("NSX_TRACERS") ? std::max(0, std::min(1048576, std::atoi(std::getenv("NSX_TRACERS")))) : 0;
 };
 

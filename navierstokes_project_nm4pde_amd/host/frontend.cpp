@@ -1355,6 +1355,69 @@ int nsxh_write_vtu_fields(const nsxh_dofs *d, const double *solution, const doub
   return pv ? 0 : -1;
 }
 
+// The running statistics on the mesh of nsxh_write_vtu, <directory>/<basename>.vtu: the arrays of nsx_stats_get (indexed by P2 node; the mean
+// pressure by P1 node) at the cell vertices.  The node of a vertex is its first velocity dof / dim, its P1 node its pressure dof - n_u.
+int nsxh_write_vtu_stats(const nsxh_dofs *d, const double *mean_u, const double *mean_p, const double *rms_u, const double *stress, const double *tke,
+                         const char *directory, const char *basename) {
+  if (!d || !mean_u || !mean_p || !rms_u || !stress || !tke || !directory || !basename) return -1;
+  const int dim = d->dim, nv = dim + 1, nc = d->n_cells, nsym = dim * (dim + 1) / 2;
+  std::string dir(directory);
+  if (!dir.empty() && dir.back() != '/') dir += '/';
+  for (size_t pos = 1; pos < dir.size(); ++pos)  // mkdir -p
+    if (dir[pos] == '/') ::mkdir(dir.substr(0, pos).c_str(), 0777);
+  std::ofstream f(dir + basename + ".vtu");
+  if (!f) return -1;
+  f << std::setprecision(17);
+  const int32_t *sub = d->mesh->subdomain.empty() ? nullptr : d->mesh->subdomain.data();
+  auto node = [&](int c, int v) { return (size_t)(d->cell_dofs[(size_t)c * d->dpc + (size_t)(dim + 1) * v] / dim); };
+  auto vector3 = [&](const char *name, const double *a) {
+    f << "<DataArray type=\"Float64\" Name=\"" << name << "\" NumberOfComponents=\"3\" format=\"ascii\">\n";
+    for (int c = 0; c < nc; ++c)
+      for (int v = 0; v < nv; ++v) {
+        const double *x = a + node(c, v) * dim;
+        f << x[0] << ' ' << x[1] << ' ' << (dim == 3 ? x[2] : 0.0) << '\n';
+      }
+    f << "</DataArray>\n";
+  };
+  f << "<?xml version=\"1.0\"?>\n<VTKFile type=\"UnstructuredGrid\" version=\"0.1\" byte_order=\"LittleEndian\">\n<UnstructuredGrid>\n"
+    << "<Piece NumberOfPoints=\"" << (int64_t)nc * nv << "\" NumberOfCells=\"" << nc << "\">\n";
+  f << "<Points>\n<DataArray type=\"Float64\" NumberOfComponents=\"3\" format=\"ascii\">\n";
+  for (int c = 0; c < nc; ++c)
+    for (int v = 0; v < nv; ++v) {
+      const double *x = d->cell_coords.data() + ((size_t)c * nv + v) * dim;
+      f << x[0] << ' ' << x[1] << ' ' << (dim == 3 ? x[2] : 0.0) << '\n';
+    }
+  f << "</DataArray>\n</Points>\n<Cells>\n<DataArray type=\"Int32\" Name=\"connectivity\" format=\"ascii\">\n";
+  for (int64_t k = 0; k < (int64_t)nc * nv; ++k) f << k << ((k + 1) % nv ? ' ' : '\n');
+  f << "</DataArray>\n<DataArray type=\"Int32\" Name=\"offsets\" format=\"ascii\">\n";
+  for (int c = 1; c <= nc; ++c) f << (int64_t)c * nv << (c % 16 ? ' ' : '\n');
+  f << "\n</DataArray>\n<DataArray type=\"UInt8\" Name=\"types\" format=\"ascii\">\n";
+  for (int c = 1; c <= nc; ++c) f << (dim == 3 ? 10 : 5) << (c % 32 ? ' ' : '\n');  // VTK_TETRA / VTK_TRIANGLE
+  f << "\n</DataArray>\n</Cells>\n<PointData Scalars=\"scalars\">\n";
+  vector3("mean_velocity", mean_u);
+  f << "<DataArray type=\"Float64\" Name=\"mean_pressure\" format=\"ascii\">\n";
+  for (int c = 0; c < nc; ++c)
+    for (int v = 0; v < nv; ++v) f << mean_p[d->cell_dofs[(size_t)c * d->dpc + (size_t)(dim + 1) * v + dim] - d->n2 * dim] << (v + 1 == nv ? '\n' : ' ');
+  f << "</DataArray>\n";
+  vector3("rms_velocity", rms_u);
+  f << "<DataArray type=\"Float64\" Name=\"reynolds_stress\" NumberOfComponents=\"6\" format=\"ascii\">\n";
+  for (int c = 0; c < nc; ++c)
+    for (int v = 0; v < nv; ++v) {
+      const double *s = stress + node(c, v) * nsym;  // xx, yy, [zz,] xy[, xz, yz] -> XX YY ZZ XY YZ XZ
+      if (dim == 3) f << s[0] << ' ' << s[1] << ' ' << s[2] << ' ' << s[3] << ' ' << s[5] << ' ' << s[4] << '\n';
+      else f << s[0] << ' ' << s[1] << " 0 " << s[2] << " 0 0\n";
+    }
+  f << "</DataArray>\n<DataArray type=\"Float64\" Name=\"tke\" format=\"ascii\">\n";
+  for (int c = 0; c < nc; ++c)
+    for (int v = 0; v < nv; ++v) f << tke[node(c, v)] << (v + 1 == nv ? '\n' : ' ');
+  f << "</DataArray>\n<DataArray type=\"Float64\" Name=\"partitioning\" format=\"ascii\">\n";
+  for (int c = 0; c < nc; ++c)
+    for (int v = 0; v < nv; ++v) f << (sub ? sub[c] : 0) << (v + 1 == nv ? '\n' : ' ');
+  f << "</DataArray>\n</PointData>\n</Piece>\n</UnstructuredGrid>\n</VTKFile>\n";
+  f.close();
+  return f ? 0 : -1;
+}
+
 // A lattice of nsx_set_lattice as VTK ImageData, <directory>/<basename>_<counter>.vti: the planes of nsx_get_lattice as PointData -- "velocity"
 // (3 components, the third 0 in 2D), "pressure", the mask "cell_id" (nsx_get_lattice_cells: -1 outside the mesh) and, when given, "vorticity".
 int nsxh_write_vti(int dim, const double *origin, const double *spacing, const int32_t *counts, const double *velocity, const double *pressure,

@@ -30,6 +30,7 @@ API = [
     "nsx_sparse_product", "nsx_compute_nodal_fields", "nsx_nodal_field_components", "nsx_get_nodal_field",
     "nsx_extract_isosurface", "nsx_get_isosurface",
     "nsx_set_lattice", "nsx_get_lattice_cells", "nsx_eval_lattice", "nsx_get_lattice",
+    "nsx_stats_begin", "nsx_stats_accumulate", "nsx_stats_info", "nsx_stats_components", "nsx_stats_get",
 ]
 # declared in include/nsx.h as well, but with a capital letter in its name, which the header scan of tests/test_abi.py (lower case only)
 # does not see: kept beside the list that scan is compared with; build() checks both
@@ -49,6 +50,10 @@ FIELD_GRADIENT, FIELD_VORTICITY, FIELD_Q, FIELD_STRAIN, FIELD_DIVERGENCE, FIELD_
 ISO_VELOCITY, ISO_PRESSURE, ISO_NODAL, ISO_PLANE = range(4)
 # quantities of nsx_eval_lattice / nsx_get_lattice (NSX_LATTICE_*): bits
 LATTICE_VELOCITY, LATTICE_PRESSURE, LATTICE_GRADIENT, LATTICE_NODAL = 1, 2, 4, 8
+# parts of nsx_stats_begin (NSX_STATS_*: bits) and quantities of nsx_stats_get
+STATS_VELOCITY, STATS_PRESSURE = 1, 2
+(STATS_MEAN_U, STATS_COMOMENT_U, STATS_STRESS_U, STATS_RMS_U, STATS_TKE, STATS_MEAN_P, STATS_COMOMENT_P, STATS_VAR_P, STATS_RMS_P,
+ STATS_QUANTITY_COUNT) = range(10)
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, _f64p, C.c_int)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(_f64p), C.POINTER(C.c_int),
@@ -164,6 +169,11 @@ def lib():
     L.nsx_get_lattice_cells.argtypes = [vp, _i32p]
     L.nsx_eval_lattice.argtypes = [vp, C.c_int]
     L.nsx_get_lattice.argtypes = [vp, C.c_int, C.c_int, _f64p]
+    L.nsx_stats_begin.argtypes = [vp, C.c_int, C.c_int]
+    L.nsx_stats_accumulate.argtypes = [vp, C.c_int, C.c_double]
+    L.nsx_stats_info.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int64), _f64p]
+    L.nsx_stats_components.argtypes = [vp, C.c_int, C.POINTER(C.c_int)]
+    L.nsx_stats_get.argtypes = [vp, C.c_int, C.c_int, _f64p]
     L.nsx_set_inner_precision.argtypes = [vp, C.c_int]
     L.nsx_inner_F_vmult.argtypes = [vp, _f64p, _f64p]
     L.nsx_schur_cg.argtypes = [vp, C.c_double, C.c_int, _f64p, _f64p, C.POINTER(C.c_int), _f64p, C.POINTER(C.c_int)]
@@ -673,6 +683,34 @@ class Nsx:
               LATTICE_NODAL: {FIELD_GRADIENT: dim * dim, FIELD_VORTICITY: 3 if dim == 3 else 1}.get(which, 1)}.get(quantity, 1)
         out = np.empty((nc,) + self._lattice_shape())
         self._ck(self.L.nsx_get_lattice(self._h, int(quantity), int(which), _d(out)))
+        return out
+
+    # -- running statistics --------------------------------------------------------------------
+    def stats_begin(self, what=STATS_VELOCITY | STATS_PRESSURE, n_bins=1):
+        """nsx_stats_begin: open an accumulation of `what` (an OR of STATS_VELOCITY, STATS_PRESSURE) with n_bins zeroed phase bins;
+        what = n_bins = 0 closes it and frees its memory"""
+        self._ck(self.L.nsx_stats_begin(self._h, int(what), int(n_bins)))
+
+    def stats_accumulate(self, bin=0, weight=1.0):
+        """nsx_stats_accumulate: the state the handle holds as one sample of weight `weight` into bin `bin`"""
+        self._ck(self.L.nsx_stats_accumulate(self._h, int(bin), float(weight)))
+
+    def stats_info(self):
+        """{"what", "n_bins", "samples" [n_bins], "weights" [n_bins]} of the open accumulation (nsx_stats_info)"""
+        what, n_bins = C.c_int(0), C.c_int(0)
+        self._ck(self.L.nsx_stats_info(self._h, C.byref(what), C.byref(n_bins), None, None))
+        samples, weights = np.zeros(n_bins.value, np.int64), np.zeros(n_bins.value)
+        self._ck(self.L.nsx_stats_info(self._h, None, None, samples.ctypes.data_as(C.POINTER(C.c_int64)), _d(weights)))
+        return {"what": what.value, "n_bins": n_bins.value, "samples": samples, "weights": weights}
+
+    def stats_get(self, quantity, bin=-1):
+        """[n_nodes][n_components] of one quantity (STATS_*) of bin `bin`, or of all non-empty bins pooled (bin = -1), nodes in the
+        caller's numbering: P2 nodes for the velocity quantities, P1 nodes for the pressure's (nsx_stats_get).  Distributed handles:
+        global-sized, the entries this rank owns filled, the rest 0."""
+        nc = C.c_int(0)
+        self._ck(self.L.nsx_stats_components(self._h, int(quantity), C.byref(nc)))
+        out = np.zeros((self.n_u // self.dim if quantity < STATS_MEAN_P else self.n_p, nc.value))
+        self._ck(self.L.nsx_stats_get(self._h, int(quantity), int(bin), _d(out)))
         return out
 
     # -- export --------------------------------------------------------------------------------
