@@ -32,15 +32,6 @@ enum { S_CGP = 100 };           // scalar slots of the publication: steps, last 
 __device__ __forceinline__ double ld_agent(const double *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void st_agent(double *p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-template <int W>
-__device__ __forceinline__ double cg_group_sum(double v) {
-  v += dpp_f64<0xB1>(v);
-  v += dpp_f64<0x4E>(v);
-  if (W >= 8) v += dpp_f64<0x141>(v);
-  if (W >= 16) v += dpp_f64<0x140>(v);
-  return v;
-}
-
 // Grid-wide fixed-order sums of NV values in two halves, so that the caller can issue loads between them:
 //   cg_post:     the workgroup's partial sums go out (one barrier for all NV values); workgroup 0 also waits for every
 //                mailbox and publishes the totals
@@ -167,7 +158,7 @@ __device__ __forceinline__ void cg_block_spmv(int s0, int s1, const double *__re
       acc += V[k] * xst[L[k]];                                  \
       const int inf = sinfo[s_];                                \
       if (inf & 0x8000) {                                       \
-        const double r_ = cg_group_sum<16>(acc);                \
+        const double r_ = lane_group_sum<16>(acc);              \
         if (lane == 0) hvs[(inf & 0x7fff) * 16 + grp] = r_;     \
         acc = 0.0;                                              \
       }                                                         \
@@ -274,7 +265,7 @@ __global__ __launch_bounds__(CG_THREADS) void k_cg_schur(const int32_t *__restri
           double acc = 0.0;
 #pragma unroll
           for (int c = 0; c < RPG; ++c) acc += pr[r][c] * gs[lane + 16 * c];
-          acc = cg_group_sum<16>(acc);
+          acc = lane_group_sum<16>(acc);
           if (lane == 0) hs[q] = acc;
         }
       }
@@ -284,7 +275,7 @@ __global__ __launch_bounds__(CG_THREADS) void k_cg_schur(const int32_t *__restri
         double acc = 0.0;
 #pragma unroll
         for (int c = 0; c < 8; ++c) acc += pv[c] * gs[lane + 16 * c];
-        acc = cg_group_sum<16>(acc);
+        acc = lane_group_sum<16>(acc);
         if (lane == 0) hs[q] = acc;
       };
       for (int q = grp; q < nb; q += 2 * CG_NG) {
@@ -305,7 +296,7 @@ __global__ __launch_bounds__(CG_THREADS) void k_cg_schur(const int32_t *__restri
         double acc = 0.0;
 #pragma unroll
         for (int c = 0; c < 16; ++c) acc += pv[c] * gs[lane + 16 * c];
-        acc = cg_group_sum<16>(acc);
+        acc = lane_group_sum<16>(acc);
         if (lane == 0) hs[q] = acc;
       }
     }
@@ -337,7 +328,7 @@ __global__ __launch_bounds__(CG_THREADS) void k_cg_schur(const int32_t *__restri
           const int e1 = lrow[q + 1];
           double acc = 0.0;
           for (int e = lrow[q] + lane; e < e1; e += 16) acc += lval[e] * xst[lidx[e]];
-          acc = cg_group_sum<16>(acc);
+          acc = lane_group_sum<16>(acc);
           if (lane == 0) hvs[q] = acc;
         }
       }
@@ -506,7 +497,7 @@ void build_cg_plan(nsx_handle *h) {
   pl.s_val.alloc((size_t)pl.n_slots);
   pl.ok = true;
   pl.values_current = false;
-  if (getenv("NSX_DEBUG"))
+  if (nsx_debug())
     fprintf(stderr, "[nsx] persistent Schur CG plan: %d blocks, %lld slabs (fill %.2f), unique columns per block avg %.0f\n", nb,
             (long long)s_info.size(), (double)g.nnz() / (double)std::max<int64_t>(1, pl.n_slots), (double)u_cols.size() / std::max(1, nb));
 }
@@ -523,7 +514,7 @@ void cg_pack_values(nsx_handle *h) {
 static void cg_setup(nsx_handle *h) {
   if (h->cg_box.p || h->cg_disabled) return;
   h->cg_max_wg = 0;
-  if (getenv("NSX_CG_PERSISTENT") && atoi(getenv("NSX_CG_PERSISTENT")) == 0) {
+  if (!env_on("NSX_CG_PERSISTENT")) {
     h->cg_disabled = true;
     return;
   }
@@ -544,7 +535,7 @@ static void cg_setup(nsx_handle *h) {
   HIP_CHECK(hipMemsetAsync(h->cg_box.p, 0xff, 2 * CG_REGION * sizeof(unsigned long long), h->stream));
   HIP_CHECK(hipMemsetAsync(h->cg_box.p + 2 * CG_REGION, 0, 2 * sizeof(unsigned long long), h->stream));
   h->cg_max_wg = std::min(CG_MAX_WG, per_cu * cus);
-  if (getenv("NSX_DEBUG"))
+  if (nsx_debug())
     fprintf(stderr, "[nsx] persistent Schur CG: %d CUs x %d resident workgroups, grid <= %d (block inverses in registers: <= 96 rows x %d, <= 128 rows x %d; operator in LDS as well: x %d, x %d)\n", cus, per_cu,
             h->cg_max_wg, per_cu_res[0], per_cu_res[1], per_cu_lres[0], per_cu_lres[1]);
 }
@@ -557,11 +548,11 @@ bool cg_schur_persistent(nsx_handle *h, double *x, const double *b, double rtol,
   if (h->comm || !s.dense || s.max_rows > CG_MAXB || !pl.ok || !pl.values_current) return false;
   cg_setup(h);
   if (h->cg_max_wg == 0 || s.n_blocks > h->cg_max_wg) return false;
-  const bool pres_ok = !(getenv("NSX_CG_PRES") && atoi(getenv("NSX_CG_PRES")) == 0);  // read per solve: the tests switch it
+  const bool pres_ok = env_on("NSX_CG_PRES");  // read per solve: the tests switch it
   // rows per group of the register-resident variant: the smallest that holds the largest block, if its grid is resident
   const int rpg = !pres_ok ? 0 : (s.max_rows <= 96 && s.n_blocks <= h->cg_max_wg_res[0]) ? 6 : (s.max_rows <= 128 && s.n_blocks <= h->cg_max_wg_res[1]) ? 8 : 0;
   const bool pres = rpg > 0;
-  const bool lres_ok = !(getenv("NSX_CG_LRES") && atoi(getenv("NSX_CG_LRES")) == 0);
+  const bool lres_ok = env_on("NSX_CG_LRES");
   // ... and the block's rows of the operator in LDS, if every block fits the pool and that grid is resident too
   const bool lres = lres_ok && pres && pl.max_block_nnz <= CG_LPOOL && s.n_blocks <= h->cg_max_wg_lres[rpg == 6 ? 0 : 1];
   const int n = h->n_p;
@@ -583,7 +574,7 @@ bool cg_schur_persistent(nsx_handle *h, double *x, const double *b, double rtol,
     if (rpg == 6 && lres) NSX_CG_GO(6, true); else if (rpg == 8 && lres) NSX_CG_GO(8, true);
     else if (rpg == 6) NSX_CG_GO(6, false); else if (rpg == 8) NSX_CG_GO(8, false); else NSX_CG_GO(0, false);
 #undef NSX_CG_GO
-    if (getenv("NSX_DEBUG") && (h->cg_resident != pres || h->cg_lds_resident != lres || !h->cg_variant_said)) {
+    if (nsx_debug() && (h->cg_resident != pres || h->cg_lds_resident != lres || !h->cg_variant_said)) {
       fprintf(stderr, "[nsx] Schur CG variant: block inverses in registers %d (rows per lane group %d), operator in LDS %d (largest block: %d entries)\n", (int)pres, rpg,
               (int)lres, (int)pl.max_block_nnz);
       h->cg_variant_said = true;
@@ -682,7 +673,7 @@ __device__ __forceinline__ void cgd_dense_apply(const double *__restrict__ Pb, i
     double acc = 0.0;
 #pragma unroll
     for (int c = 0; c < 16; ++c) acc += pv[c] * gs[lane + 16 * c];
-    acc = cg_group_sum<16>(acc);
+    acc = lane_group_sum<16>(acc);
     if (lane == 0) hs[q] = acc;
   }
 }
@@ -822,7 +813,7 @@ __global__ __launch_bounds__(CG_THREADS) void k_cgd_B(const int32_t *__restrict_
 bool cg_schur_fused(nsx_handle *h, double *x, const double *b, double rtol, int maxiter, int *steps, double *last, int *status) {
   const IluSchedule &s = h->schedS;
   const CgPlan &pl = h->cgplan;
-  const bool wanted = !(getenv("NSX_CG_FUSED") && atoi(getenv("NSX_CG_FUSED")) == 0);  // read per solve: the tests switch it inside one process
+  const bool wanted = env_on("NSX_CG_FUSED");  // read per solve: the tests switch it inside one process
   if (!wanted) return false;  // (one GPU: reached when the persistent kernel cannot run -- more Schur blocks than resident workgroups, i.e. beyond ~1.16 M DoF)
   // whether THIS rank's Schur blocks fit the kernels (dense inverses, <= 256 rows, <= 1024 unique columns per block) depends on its
   // own part of the mesh: the ranks agree once per set of schedules, or one of them would run the launch-per-operation solver's
@@ -861,7 +852,7 @@ bool cg_schur_fused(nsx_handle *h, double *x, const double *b, double rtol, int 
   comm_allreduce_partials(h, parts + CGD_P0, 3 * CGD_PARTS);
   int it = 0, conv = 0;
   double tol = 0.0, res = 0.0;
-  static const bool trace = getenv("NSX_TRACE") != nullptr;
+  static const bool trace = env_set("NSX_TRACE");
   for (;;) {
     const int nx = it + 1;
     if (trace && (it < 3 || it % 200 == 0)) fprintf(stderr, "[nsx trace] rank %d: Schur CG iteration %d, residual %.3e, tolerance %.3e\n", h->rank, it, res, tol);

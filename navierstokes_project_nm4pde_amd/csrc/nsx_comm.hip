@@ -138,7 +138,7 @@ static void ensure_comm_stream(nsx_handle *h) {
   // every kernel of the compute stream runs three times slower (spmv_F 31 -> 92 us, with the highest and with the lowest priority
   // alike), so the default priority it is; whether the two streams really run side by side is PROBED (comm_streams_concurrent)
   // before the sweep relies on it.
-  const int prio = getenv("NSX_COMM_PRIO") ? atoi(getenv("NSX_COMM_PRIO")) : 0;  // 1 highest, 0 default, -1 lowest
+  const int prio = env_int("NSX_COMM_PRIO", 0);  // 1 highest, 0 default, -1 lowest
   HIP_CHECK(hipStreamCreateWithPriority(&h->comm_stream, hipStreamNonBlocking, prio > 0 ? hi : prio < 0 ? lo : (lo + hi) / 2));
   HIP_CHECK(hipEventCreateWithFlags(&h->ev_ready, hipEventDisableTiming));
 }
@@ -196,7 +196,7 @@ void comm_prepare_streams(nsx_handle *h) {
     }
   }
   ensure_comm_stream(h);
-  if (getenv("NSX_DEBUG")) fprintf(stderr, "[nsx] communication stream runs beside a waiting compute kernel: %d\n", h->comm_probe_local);
+  if (nsx_debug()) fprintf(stderr, "[nsx] communication stream runs beside a waiting compute kernel: %d\n", h->comm_probe_local);
 }
 // A persistent grid whose waves allocate 256 VGPRs leaves RCCL's generic kernel (264 per lane) no place on any CU it touches, and the
 // dispatcher touches them all.  A compute stream with a CU mask does: bit i of the mask is CU i / 8 of XCD i % 8
@@ -253,7 +253,7 @@ bool comm_reserve_cus(nsx_handle *h) {
   }
   h->stream_plain = plain;
   h->cu_reserved = 8;
-  if (getenv("NSX_DEBUG")) fprintf(stderr, "[nsx] compute stream replaced by one that leaves one CU per XCD to the communication stream\n");
+  if (nsx_debug()) fprintf(stderr, "[nsx] compute stream replaced by one that leaves one CU per XCD to the communication stream\n");
   return true;
 }
 // The way back: the plain compute stream and an unmasked communication stream, as the handle had them before comm_reserve_cus
@@ -271,7 +271,7 @@ void comm_release_cus(nsx_handle *h) {
   h->comm_stream = nullptr;
   h->cu_reserved = 0;
   if (h->comm) comm_prepare_streams(h);
-  if (getenv("NSX_DEBUG")) fprintf(stderr, "[nsx] compute stream back on all CUs\n");
+  if (nsx_debug()) fprintf(stderr, "[nsx] compute stream back on all CUs\n");
 }
 // ... on every rank?  The ranks take the minimum of their answers (one collective in the lifetime of a handle), so that all of them
 // use the collective-inside-the-grid sweep or none does.
@@ -287,7 +287,7 @@ bool comm_streams_concurrent(nsx_handle *h) {
   NCCL_CHECK(ncclAllReduce(ans.p, ans.p, 1, ncclDouble, ncclMin, c->comm, h->stream));
   HIP_CHECK(hipStreamSynchronize(h->stream));
   HIP_CHECK(hipMemcpy(&v, ans.p, sizeof(double), hipMemcpyDeviceToHost));
-  if (getenv("NSX_DEBUG")) fprintf(stderr, "[nsx] communication stream beside the compute stream: here %d, on all ranks %d\n", h->comm_probe_local, (int)(v > 0.5));
+  if (nsx_debug()) fprintf(stderr, "[nsx] communication stream beside the compute stream: here %d, on all ranks %d\n", h->comm_probe_local, (int)(v > 0.5));
   return v > 0.5;
 }
 
@@ -302,8 +302,7 @@ void comm_ext_allreduce(nsx_handle *h, double *vals, int count, int fail_word, u
   NCCL_CHECK(ncclAllReduce(vals, vals, count, ncclDouble, ncclSum, c->comm, h->comm_stream));
   // fault injection (tests, NSX_EXT_LATE_RELEASE=k): the k-th collective of this kind never tells its grid that it is complete -- what a
   // collective that arrives after the grid's bounded wait looks like to ONE rank
-  const char *late_env = getenv("NSX_EXT_LATE_RELEASE");  // (read per call: the tests switch it inside one process)
-  const int late = late_env ? atoi(late_env) : 0;
+  const int late = env_int("NSX_EXT_LATE_RELEASE", 0);  // (read per call: the tests switch it inside one process)
   if (late > 0 && ++h->n_ext_collectives == late) return;
   hipLaunchKernelGGL(k_ext_release, dim3(1), dim3(1), 0, h->comm_stream, flag, seq);
 }
@@ -452,7 +451,7 @@ int nsx_comm_init(nsx_handle *h, int rank, int world, const uint8_t id[128]) {
   ncclUniqueId u;
   memcpy(&u, id, 128);
   NCCL_CHECK(ncclCommInitRank(&h->comm->comm, world, u, rank));
-  h->self_p2p = getenv("NSX_EXT_SELF_P2P") ? atoi(getenv("NSX_EXT_SELF_P2P")) : 0;
+  h->self_p2p = nsx::env_int("NSX_EXT_SELF_P2P", 0);
   nsx::comm_prepare_streams(h);
   h->mgs.dist_state = -1;  // a new communicator: the paths the ranks choose together are chosen again
   h->mgs.dist_fit.clear();

@@ -1,4 +1,4 @@
-// nsx_ilu_lanes.hpp — device side of the lane-owner triangular solve (kernel k_ilu_solve_lanes in nsx_sparse.hip; the stream
+// nsx_ilu_lanes.hpp — device side of the lane-owner triangular solve (kernel k_ilu_solve_lanes in nsx_ilu.hip; the stream
 // is laid out by host/ilu_stream.hpp).  Kept in a header so that tools/ilu_lanes_bench.hip times exactly this code.
 #pragma once
 #include <hip/hip_runtime.h>

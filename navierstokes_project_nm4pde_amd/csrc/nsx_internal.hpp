@@ -22,13 +22,16 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <exception>
 #include <map>
 #include <string>
 #include <functional>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/nsx.h"
@@ -593,6 +596,37 @@ struct LaunchScope {
 
 inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
+// ---- environment knobs (NSX_*): THE readers.  A reader reads when it is called, so the call site decides how long a value holds: per
+//      call (what the tests switch inside one process: the ILU, Schur CG and step variants, NSX_PF, NSX_SCHUR_CACHE), once per process (the
+//      initialiser of a function's `static`) or once per handle (nsx_create, mgs_setup, the schedule builders).  DESIGN.md section 4 has the list.
+inline int env_int(const char *name, int dflt) {
+  const char *e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
+inline int64_t env_i64(const char *name, int64_t dflt) {
+  const char *e = getenv(name);
+  return e ? atoll(e) : dflt;
+}
+inline double env_double(const char *name, double dflt) {
+  const char *e = getenv(name);
+  return e ? atof(e) : dflt;
+}
+inline bool env_set(const char *name) { return getenv(name) != nullptr; }
+inline bool env_on(const char *name) { return env_int(name, 1) != 0; }      // on unless set to 0
+inline bool env_opt_in(const char *name) { return env_int(name, 0) == 1; }  // off unless set to 1
+inline bool nsx_debug() { return env_set("NSX_DEBUG"); }
+// knobs more than one file reads
+inline bool ilu_mgs_wanted() { return env_opt_in("NSX_ILU_MGS"); }          // the velocity triangular solves inside the sweep's launch (k_ilu_mgs)
+inline int ilu_lanes_pf() { return env_int("NSX_PF", 8) == 4 ? 4 : 8; }     // slabs a lane-owner solve keeps in flight: 4, anything else 8
+inline int mgs_maxwg_cap(int limit) { return env_set("NSX_MGS_MAXWG") ? std::min(limit, env_int("NSX_MGS_MAXWG", 0)) : limit; }  // tests: small grids
+
+// A run-time integer as a compile-time constant: f(std::integral_constant<int, V>) for the V among Vs... that equals v; false if none does.
+//   with_int<2, 3>(h->dim, [&](auto D) { launch<decltype(D)::value>(...); });
+template <int... Vs, class F>
+inline bool with_int(int v, F &&f) {
+  return ((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+}
+
 // ---- kernels / steps implemented across the .hip files
 void setup_ilu_schedule(nsx_handle *h, const Csr &g, const std::vector<int32_t> &block_ptr, IluSchedule &s, int blocks_per_wave, bool allow_dense = false,
                         int ncomp = 1);
@@ -636,13 +670,15 @@ void spmv_G(nsx_handle *h, const double *xp, double *yu, bool accumulate);      
 void spmv_B(nsx_handle *h, const double *xu, double *yp, const double *r = nullptr, int sub = 0);  // y_p = block(1,0) x_u; r: y_p = (block(1,0) x_u) - r (sub = 1) or r - (block(1,0) x_u) (sub = -1)
 void spmv_S(nsx_handle *h, const double *x, double *y);                                     // y = negative_S x
 void schur_numeric(nsx_handle *h, const double *w);                                         // S = B diag(w) G
+void extract_diag(nsx_handle *h, const DevCsr &g, const double *vals, double *d);           // scalar diag
+void abs_rowsum(nsx_handle *h, const DevCsr &g, const double *vals, double *d);
+
+// block-Jacobi ILU(0) (nsx_ilu.hip)
 void ilu_factor(nsx_handle *h, const DevCsr &g, IluSchedule &s, const double *vals, double *lu, const char *name, bool f32 = false);
 void ilu_check(nsx_handle *h);  // after a synchronisation: throws if a factorisation kernel reported a failure
 // dot_slot >= 0: also leave b.x in that scalar slot when the packed kernel can do it; returns whether it did
 bool ilu_solve(nsx_handle *h, const DevCsr &g, const IluSchedule &s, const double *lu, const double *b, double *x, int ncomp,
                const char *name, int dot_slot = -1, bool f32 = false, int *used_f32 = nullptr);
-void extract_diag(nsx_handle *h, const DevCsr &g, const double *vals, double *d);           // scalar diag
-void abs_rowsum(nsx_handle *h, const DevCsr &g, const double *vals, double *d);
 
 // Index span of a BLAS-1 operation: n owned entries; entries at i >= split sit `gap` further (the ghost velocity block
 // between the owned velocity and the owned pressure part of a distributed block vector).  Plain vectors: Span(n).
@@ -661,6 +697,17 @@ __device__ __forceinline__ double dpp_f64(double v) {
   lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xf, 0xf, true);
   hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xf, 0xf, true);
   return __hiloint2double(hi, lo);
+}
+// sum over the LW lanes of a row group, result in every lane: DPP (pure VALU) up to 16 lanes, then cross-row shuffles
+template <int LW>
+__device__ __forceinline__ double lane_group_sum(double v) {
+  if (LW >= 2) v += dpp_f64<0xB1>(v);    // quad_perm [1,0,3,2]
+  if (LW >= 4) v += dpp_f64<0x4E>(v);    // quad_perm [2,3,0,1]
+  if (LW >= 8) v += dpp_f64<0x141>(v);   // row_half_mirror
+  if (LW >= 16) v += dpp_f64<0x140>(v);  // row_mirror
+  if (LW >= 32) v += __shfl_xor(v, 16, 64);
+  if (LW >= 64) v += __shfl_xor(v, 32, 64);
+  return v;
 }
 // same, but only the rows of 16 lanes selected by ROW_MASK receive a value; the other rows get 0 (used with the row
 // broadcasts 0x142 row_bcast:15 and 0x143 row_bcast:31, which hand the last lane of a row / of the lower half to the rows above)

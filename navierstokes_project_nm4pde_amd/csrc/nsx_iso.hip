@@ -362,8 +362,7 @@ void iso_ensure_slots(nsx_handle *h) {
 }
 
 static int iso_wg_width() {
-  const char *e = getenv("NSX_ISO_WG");
-  const int w = e ? atoi(e) : 256;
+  const int w = env_int("NSX_ISO_WG", 256);
   return (w == 64 || w == 128) ? w : 256;
 }
 

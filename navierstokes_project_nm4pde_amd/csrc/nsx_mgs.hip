@@ -1185,25 +1185,24 @@ static unsigned int mgs_committed(nsx_handle *h, unsigned long long seq) {
 void mgs_setup(nsx_handle *h) {
   if (h->mgs.box.p || h->mgs.disabled) return;
   h->mgs.max_wg = 0;
-  if (getenv("NSX_MGS") && atoi(getenv("NSX_MGS")) == 0) {
+  if (!env_on("NSX_MGS")) {
     h->mgs.disabled = true;
     return;
   }
   // links per exchange: 0 = all of them (k_mgs_one, the default), 1 = deal.II's chain link by link (k_mgs), 2..5 = k_mgs_blk
-  h->mgs.links = getenv("NSX_MGS_LINKS") ? std::max(0, std::min(5, atoi(getenv("NSX_MGS_LINKS")))) : 0;
+  h->mgs.links = std::max(0, std::min(5, env_int("NSX_MGS_LINKS", 0)));
   int cus = 0;
   HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->prm.device));
   h->mgs.box.alloc(2 * MGS_BOX_REGION + MGS_TAIL);
   mgs_clear_boxes(h);
   const int es[3] = {8, 10, h->mgs.links == 0 ? 12 : 20};
   // NSX_MGS_MAXWG caps every grid limit (tests: a small mesh then needs the instantiations a large one does)
-  const char *maxwg = getenv("NSX_MGS_MAXWG");
-  auto capped = [maxwg](int limit) { return maxwg ? std::max(1, std::min(limit, atoi(maxwg))) : limit; };
+  auto capped = [](int limit) { return env_set("NSX_MGS_MAXWG") ? std::max(1, mgs_maxwg_cap(limit)) : limit; };
   for (int k = 0; k < 3; ++k) {
     int per_cu = 0;
     HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, mgs_fn(h->mgs.links, es[k]), 256, 0));
     h->mgs.max_wg_e[k] = capped(std::min(MGS_MAX_WG, per_cu * cus));
-    if (getenv("NSX_DEBUG")) fprintf(stderr, "[nsx] mgs sweep (%d links per exchange, %d entries per thread): %d CUs x %d resident workgroups\n", h->mgs.links, es[k], cus, per_cu);
+    if (nsx_debug()) fprintf(stderr, "[nsx] mgs sweep (%d links per exchange, %d entries per thread): %d CUs x %d resident workgroups\n", h->mgs.links, es[k], cus, per_cu);
   }
   h->mgs.max_wg = h->mgs.max_wg_e[1];
   // distributed instantiations: the collective's own kernels (RCCL's all-reduce, the two one-thread kernels around it) must find a
@@ -1409,7 +1408,7 @@ __global__ __launch_bounds__(256) void k_ls_update(int n, int split, int gap, do
 // It is accepted when |w'|^2 > guard * |w|^2 (default 1e-2: the norm of the new basis vector is then good to ~1e-13, two orders
 // below the tightest tolerance the parity tests solve to); otherwise |w'|^2 is summed over the vector (one more exchange / collective).
 static double mgs_norm_guard(const nsx_handle *h) {
-  static const double g = getenv("NSX_MGS_NORM_GUARD") ? atof(getenv("NSX_MGS_NORM_GUARD")) : 1e-2;
+  static const double g = env_double("NSX_MGS_NORM_GUARD", 1e-2);
   return h->mgs.guard_override >= 0.0 ? h->mgs.guard_override : g;  // the override: nsx_gram_schmidt_cycle / nsx_gram_schmidt_sweeps (tests)
 }
 
@@ -1479,12 +1478,12 @@ static int ilu_mgs_entries(nsx_handle *h, Span sp, int dim, const double *gram) 
   // history (the sweep's sums are grouped by rank block): both sampled windows of the chaotic GMRES(28) sequence came out with MORE
   // restart steps (driver window 25.4 against 21.9 outer iterations per step, 325 steps 30.4 against 28.0), i.e. slower per time step.
   // The default therefore stays with the separate kernels and rounds 3-4's history.
-  const bool wanted = getenv("NSX_ILU_MGS") && atoi(getenv("NSX_ILU_MGS")) == 1;
+  const bool wanted = ilu_mgs_wanted();
   const IluSchedule &s = h->schedF;
   if (!wanted || h->comm || h->mgs.disabled || !h->mgs.box.p || h->mgs.links != 0 || !gram || dim + 2 > MGS_STEPS) return 0;
   if (sp.n != h->n_u || sp.split != sp.n || sp.gap != 0 || (h->dim != 2 && h->dim != 3)) return 0;
   if (!s.packed_ok || s.levelled || s.stream_ncomp != h->dim || s.stream_epl != 2 || s.n_waves < 1 || s.n_waves > MGS_MAX_WG) return 0;
-  if (getenv("NSX_PF") && atoi(getenv("NSX_PF")) != 8) return 0;
+  if (ilu_lanes_pf() != 8) return 0;  // (the fused kernel keeps 8 slabs in flight)
   // entries per thread x basis vectors kept in registers: 8 x 10, 9 x 9 (the bench layout: 747 rows in its largest wave), 10 x 8
   const int entries = s.max_wave_rows * h->dim, e = entries <= 256 * 8 ? 8 : entries <= 256 * 9 ? 9 : entries <= 256 * 10 ? 10 : 0;
   if (!e) return 0;
@@ -1499,10 +1498,9 @@ static int ilu_mgs_entries(nsx_handle *h, Span sp, int dim, const double *gram) 
     else {
       if (shm > 64 * 1024) HIP_CHECK(hipFuncSetAttribute(ilu_mgs_fn(h->dim, e), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));  // (160 KB per CU on gfx950; the runtime's default limit per workgroup is 64 KB)
       HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, ilu_mgs_fn(h->dim, e), 256, shm));
-      h->mgs.ilu_cap[k] = std::min(MGS_MAX_WG, per_cu * cus);
-      if (getenv("NSX_MGS_MAXWG")) h->mgs.ilu_cap[k] = std::min(h->mgs.ilu_cap[k], atoi(getenv("NSX_MGS_MAXWG")));
+      h->mgs.ilu_cap[k] = mgs_maxwg_cap(std::min(MGS_MAX_WG, per_cu * cus));
     }
-    if (getenv("NSX_DEBUG"))
+    if (nsx_debug())
       fprintf(stderr, "[nsx] triangular solves + sweep in one launch (%d entries per thread, %zu B of LDS): %d resident workgroups for %d waves of the solve\n", e, shm,
               h->mgs.ilu_cap[k], s.n_waves);
   }
@@ -1540,7 +1538,7 @@ static MgsPlan mgs_plan(nsx_handle *h, Span sp, int dim, const double *gram, int
   // distributed run: the persistent sweep with the collective inside its exchange (k_mgs_one<.., true>) needs stream collectives
   // (RCCL), the Gram cache and room on the device; NSX_MGS_DIST=0 keeps the two-pass sweep (mgs_lowsync)
   if (h->comm && m.dist_state < 0) {  // decided once per handle, by all ranks together (comm_streams_concurrent)
-    const bool wanted = !(getenv("NSX_MGS_DIST") && atoi(getenv("NSX_MGS_DIST")) == 0);
+    const bool wanted = env_on("NSX_MGS_DIST");
     m.dist_state = (wanted && comm_on_stream(h) && comm_streams_concurrent(h)) ? 1 : 0;
   }
   bool dist = h->comm && m.dist_state == 1 && !m.disabled && gram;
@@ -1564,7 +1562,7 @@ static MgsPlan mgs_plan(nsx_handle *h, Span sp, int dim, const double *gram, int
     // 0 never, 1 (default) when that is what keeps the collective inside the grid, 2 always.  Every condition below is an answer all
     // ranks gave together, so every rank takes the same steps -- including the outcome of the reservation itself: if it fails anywhere
     // (no masked stream, the probe) every rank goes back to its plain streams and nobody asks again on this communicator.
-    static const int reserve = getenv("NSX_COMM_CU_RESERVE") ? atoi(getenv("NSX_COMM_CU_RESERVE")) : 1;
+    static const int reserve = env_int("NSX_COMM_CU_RESERVE", 1);
     const bool fits8 = p.pick.e != 0 && p.pick.per_thread <= 8;
     const bool fits_reserved = mgs_pick(n, m.dist_cap_reserved, 3, es_one).fits();
     const bool all8 = reserve > 0 ? comm_agree_all(h, fits8) : true;
@@ -1600,7 +1598,7 @@ static MgsPlan mgs_plan(nsx_handle *h, Span sp, int dim, const double *gram, int
 // The sweep without a persistent grid.  two_pass: two collectives per sweep (mgs_lowsync) instead of one per link; NSX_MGS_LOWSYNC=0:
 // one launch + all-reduce per link, as the reference's MPI run does.  Without a Gram cache (or too many vectors for it) the chain as well.
 static void mgs_fallback(nsx_handle *h, Span sp, double *w, int dim, double *const *vs, int slot0, double *out, bool consider, double *gram, bool two_pass) {
-  if (h->mgs.ls_mode < 0) h->mgs.ls_mode = getenv("NSX_MGS_LOWSYNC") ? atoi(getenv("NSX_MGS_LOWSYNC")) : 2;  // read once per handle: 0 chain, 1 two collectives, 2 one
+  if (h->mgs.ls_mode < 0) h->mgs.ls_mode = env_int("NSX_MGS_LOWSYNC", 2);  // read once per handle: 0 chain, 1 two collectives, 2 one
   if (two_pass && h->mgs.ls_mode && gram && dim <= 31) mgs_lowsync(h, sp, w, dim, vs, slot0, out, consider, gram);
   else mgs_chain(h, sp, w, dim, vs, slot0, out, consider);
 }
@@ -1671,7 +1669,7 @@ static double *mgs_launch(nsx_handle *h, const MgsPlan &p, Span sp, double *w, i
     // development: wall-clock stamps of every wave of ONE launch (the NSX_ILU_MGS_TRACE_CALL-th, default 3000)
     DevBuf<unsigned long long> trace_buf;
     const char *trace_path = getenv("NSX_ILU_MGS_TRACE");
-    const bool traced = trace_path && m.fused_launches == (getenv("NSX_ILU_MGS_TRACE_CALL") ? atoi(getenv("NSX_ILU_MGS_TRACE_CALL")) : 3000);
+    const bool traced = trace_path && m.fused_launches == env_int("NSX_ILU_MGS_TRACE_CALL", 3000);
     if (traced) {
       trace_buf.alloc((size_t)nwg * 4 * 16);
       trace_buf.zero(h->stream);

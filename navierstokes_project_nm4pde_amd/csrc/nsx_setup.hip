@@ -153,7 +153,7 @@ void setup_ilu_schedule(nsx_handle *h, const Csr &g, const std::vector<int32_t> 
     s.fac_order.upload(order, h->stream);
   }
   // ---- blocks beyond what one wave (packed stream) or one workgroup can hold: merged level lists, one launch per level
-  const int levelled_min = getenv("NSX_LEVELLED_MIN") ? atoi(getenv("NSX_LEVELLED_MIN")) : 4096;
+  const int levelled_min = env_int("NSX_LEVELLED_MIN", 4096);
   s.levelled = s.max_rows > levelled_min;
   s.packed_ok = false;
   s.dense = false;
@@ -185,7 +185,7 @@ void setup_ilu_schedule(nsx_handle *h, const Csr &g, const std::vector<int32_t> 
       (pass == 0 ? s.gl_f_rec : s.gl_b_rec).upload(rec, h->stream);
     }
     s.block_ptr.upload(bptr, h->stream);
-    if (getenv("NSX_DEBUG"))
+    if (nsx_debug())
       fprintf(stderr, "[nsx] ilu schedule: rows %d blocks %d max_rows %d -> levelled, %d levels\n", g.n_rows, nb, s.max_rows, s.max_levels);
     return;
   }
@@ -209,13 +209,13 @@ void setup_ilu_schedule(nsx_handle *h, const Csr &g, const std::vector<int32_t> 
     }
     // (blocks of at most 256 rows -- what the Schur CG kernels take -- cost at most 256 entries per row whatever the mesh size: no limit on their total;
     // the 10.6 M-DoF mesh on one GPU has 4 833 blocks of <= 96 rows, 42 M entries = 335 MB)
-    const int64_t limit = getenv("NSX_DENSE_MAX") ? atoll(getenv("NSX_DENSE_MAX")) : ((int64_t)32 << 20);  // entries (256 MB)
-    if (off[nb] > 0 && (off[nb] <= limit || (s.max_rows <= 256 && !getenv("NSX_DENSE_MAX"))) && s.max_rows <= 4096) {
+    const int64_t limit = env_i64("NSX_DENSE_MAX", (int64_t)32 << 20);  // entries (256 MB)
+    if (off[nb] > 0 && (off[nb] <= limit || (s.max_rows <= 256 && !env_set("NSX_DENSE_MAX"))) && s.max_rows <= 4096) {
       s.dense = true;
       s.dn_entries = off[nb];
       s.dn_off.upload(off, h->stream);
       s.dn_P.alloc((size_t)off[nb]);
-      if (getenv("NSX_DEBUG")) fprintf(stderr, "[nsx] ilu schedule: explicit block inverses, %lld entries (%.1f MB)\n", (long long)off[nb], 8e-6 * off[nb]);
+      if (nsx_debug()) fprintf(stderr, "[nsx] ilu schedule: explicit block inverses, %lld entries (%.1f MB)\n", (long long)off[nb], 8e-6 * off[nb]);
     }
   }
   // ---- the packed stream of the solve kernel (host/ilu_stream.hpp, k_ilu_solve_lanes) -- unless it would never be used: the
@@ -229,7 +229,7 @@ void setup_ilu_schedule(nsx_handle *h, const Csr &g, const std::vector<int32_t> 
   s.stream_ncomp = 0;
   if (!s.dense && stream_fits) {
     IluStream st;
-    const int ept = getenv("NSX_ILU_EPT") ? std::max(1, std::min(4, atoi(getenv("NSX_ILU_EPT")))) : 2;
+    const int ept = std::max(1, std::min(4, env_int("NSX_ILU_EPT", 2)));
     build_ilu_stream(g, bptr, std::max(1, blocks_per_wave), ncomp, 2, st, ept);
     s.stream_ncomp = ncomp;
     s.stream_epl = st.epl;
@@ -238,7 +238,7 @@ void setup_ilu_schedule(nsx_handle *h, const Csr &g, const std::vector<int32_t> 
     s.max_wave_rows = st.max_wave_rows;
     s.n_slabs = st.n_slabs;
     s.packed_ok = st.ok;
-    if (getenv("NSX_DEBUG"))
+    if (nsx_debug())
       fprintf(stderr, "[nsx] ilu schedule: rows %d blocks %d max_rows %d levels(max) %d lane-owner stream: %d waves (%d blocks each), %d entries per tick, slabs %lld (max/wave %lld) fill %.2f, "
                       "%.1f MB, in-block entries %lld, LDS rows/wave <= %d%s\n",
               g.n_rows, nb, s.max_rows, s.max_levels, st.n_waves, blocks_per_wave, st.epl, (long long)st.n_slabs, (long long)st.max_wave_slabs,
@@ -339,7 +339,7 @@ void build_blocked(nsx_handle *h, const Csr &g, const std::vector<int32_t> &boun
   b.cptr.upload(cptr, h->stream);
   b.ucols.upload(ucols, h->stream);
   b.lidx.upload(lidx, h->stream);
-  if (getenv("NSX_DEBUG"))
+  if (nsx_debug())
     fprintf(stderr, "[nsx] blocked spmv: rows %d chunks %d (max %d rows; %d of them stage a ghost column: %.1f %% of the non-zeros) unique cols/chunk avg %.0f max %d (nnz/unique %.1f)\n",
             g.n_rows, b.n_chunks, b.max_rows, b.n_chunks_if, 100.0 * b.frac_if, b.ucols_total / std::max(1, b.n_chunks), b.max_ucols, (double)g.nnz() / b.ucols_total);
 }
@@ -351,14 +351,14 @@ void build_blocked(nsx_handle *h, const Csr &g, const std::vector<int32_t> &boun
 // Without a rank table, or with ranks too large for a chunk: a fixed row count.
 static std::vector<int32_t> spmv_chunks(nsx_handle *h) {
   const int n = h->gA.host.n_rows;
-  const int target = getenv("NSX_SPMV_R") ? std::max(16, std::min(448, atoi(getenv("NSX_SPMV_R")))) : 130;
+  const int target = std::max(16, std::min(448, env_int("NSX_SPMV_R", 130)));
   std::vector<int32_t> bounds{0};
   const std::vector<int32_t> &rk = h->rank_u_h;
-  const bool by_rank = !(getenv("NSX_SPMV_BY_RANK") && atoi(getenv("NSX_SPMV_BY_RANK")) == 0) && rk.size() > 2 &&
+  const bool by_rank = env_on("NSX_SPMV_BY_RANK") && rk.size() > 2 &&
                        (double)n / (double)(rk.size() - 1) <= target;
   // ranks larger than a chunk (fewer, larger virtual ranks: --ranks 2048 has ~170 rows per block) are cut into equal parts of at most
   // `target` rows: a chunk still ends where a subdomain ends
-  const bool split_ranks = !by_rank && !(getenv("NSX_SPMV_BY_RANK") && atoi(getenv("NSX_SPMV_BY_RANK")) == 0) && rk.size() > 2 &&
+  const bool split_ranks = !by_rank && env_on("NSX_SPMV_BY_RANK") && rk.size() > 2 &&
                            (double)n / (double)(rk.size() - 1) <= 4.0 * target;
   if (by_rank) {
     int start = 0;
@@ -454,10 +454,10 @@ void ensure_schedules(nsx_handle *h) {
   // best at 1 M DoF / 4096 ranks: fewer blocks per wave leave idle slots in the stream, more leave too few waves)
   auto blocks_per_wave = [](int n_rows, size_t n_blocks) { return std::max(1, std::min(64, (int)(680.0 * (double)n_blocks / std::max(1, n_rows) + 0.5))); };
   const std::vector<int32_t> &sb = h->sblk_h.empty() ? h->rank_p_h : h->sblk_h;
-  const int bpwF = getenv("NSX_BPW_F") ? atoi(getenv("NSX_BPW_F")) : blocks_per_wave(h->N2, h->rank_u_h.size() - 1);
-  const int bpwS = getenv("NSX_BPW_S") ? atoi(getenv("NSX_BPW_S")) : blocks_per_wave(h->NP, sb.size() - 1);
+  const int bpwF = env_int("NSX_BPW_F", blocks_per_wave(h->N2, h->rank_u_h.size() - 1));
+  const int bpwS = env_int("NSX_BPW_S", blocks_per_wave(h->NP, sb.size() - 1));
   setup_ilu_schedule(h, h->gA.host, h->rank_u_h, h->schedF, bpwF, false, h->dim);
-  const bool denseS = !(getenv("NSX_DENSE_S") && atoi(getenv("NSX_DENSE_S")) == 0);
+  const bool denseS = env_on("NSX_DENSE_S");
   setup_ilu_schedule(h, h->gS.host, sb, h->schedS, bpwS, denseS, 1);
   build_cg_plan(h);
   h->cgd_agreed = -1;  // path choices that the ranks make together are made again for the new schedules
@@ -593,11 +593,11 @@ int nsx_create(const nsx_params *p, nsx_handle **out) {
   auto *h = new nsx_handle;
   h->prm = *p;
   h->dim = p->dim;
-  if (getenv("NSX_GX_DROP_WG")) h->gx_drop_wg = atoi(getenv("NSX_GX_DROP_WG"));  // fault injection for the tests of the time-out fallbacks
+  h->gx_drop_wg = env_int("NSX_GX_DROP_WG", h->gx_drop_wg);  // fault injection for the tests of the time-out fallbacks
   // the switches of the velocity product, per handle like the inner precision (defaults 16 / 1 / 1)
-  if (getenv("NSX_SPMV_W")) h->spmv_w = atoi(getenv("NSX_SPMV_W"));
-  h->spmv_blocked = !(getenv("NSX_SPMV_BLOCKED") && atoi(getenv("NSX_SPMV_BLOCKED")) == 0);
-  h->spmv_largest_first = !(getenv("NSX_SPMV_ORDER") && atoi(getenv("NSX_SPMV_ORDER")) == 0);
+  h->spmv_w = env_int("NSX_SPMV_W", h->spmv_w);
+  h->spmv_blocked = env_on("NSX_SPMV_BLOCKED");
+  h->spmv_largest_first = env_on("NSX_SPMV_ORDER");
   if (const char *ip = getenv("NSX_INNER_PRECISION")) {  // the handle's initial inner precision (nsx_set_inner_precision)
     if (!strcmp(ip, "fp32")) h->inner_precision = NSX_INNER_FP32;
     else if (!strcmp(ip, "fp64")) h->inner_precision = NSX_INNER_FP64;
@@ -897,7 +897,7 @@ void install_mesh(nsx_handle *h) {
       for (auto &v : idx) v = (p == &h->haloU ? h->perm2_h : h->perm1_h)[v];
     p->send_idx.upload(idx, h->stream);
   }
-  if (getenv("NSX_DEBUG") && h->layout_on)
+  if (nsx_debug() && h->layout_on)
     fprintf(stderr, "[nsx] internal layout: %d virtual ranks inside %d rank(s) of the caller, %d Schur blocks, %d / %d colours\n", (int)h->rank_u_h.size() - 1,
             (int)h->in_rank_u_h.size() - 1, (int)(h->sblk_h.empty() ? h->rank_p_h.size() : h->sblk_h.size()) - 1, h->layout_colours, h->layout_colours_p);
 }

@@ -146,7 +146,7 @@ static SolveResult gmres(nsx_handle *h, const Op &A, double *x, const double *b,
   }
   // (in place needs the lane-owner stream: its kernel loads the right-hand side rows into LDS before it writes anything)
   const bool ilu_conv = P_is_ilu_F && h->inner_precision == NSX_INNER_FP64 /* the fused kernel reads the double stream only */ && !h->comm && h->schedF.packed_ok && !h->schedF.levelled && h->schedF.stream_ncomp == h->dim &&
-                        (getenv("NSX_ILU_MGS") && atoi(getenv("NSX_ILU_MGS")) == 1);  // opt-in: see ilu_mgs_entries (nsx_mgs.hip)
+                        ilu_mgs_wanted();  // opt-in: see ilu_mgs_entries (nsx_mgs.hip)
   double H[N_TMP][N_TMP - 1];
   double gamma[N_TMP], ci[N_TMP - 1], si[N_TMP - 1], hh[N_TMP + 2], h2[N_TMP + 2];
   int accumulated = 0, state = 0, dim = 0;
@@ -185,7 +185,7 @@ static SolveResult gmres(nsx_handle *h, const Op &A, double *x, const double *b,
     double rho_before = 0.0;  // residual estimate one iteration earlier (0: none yet in this cycle)
     for (int inner = 0; inner < N_TMP - 2 && state == 0; ++inner) {
       ++accumulated;
-      static const bool trace = getenv("NSX_TRACE") != nullptr;
+      static const bool trace = env_set("NSX_TRACE");
       if (trace && h->gmres_depth == 1) fprintf(stderr, "[nsx trace] rank %d: outer iteration %d, residual %.3e\n", h->rank, accumulated, rho);
       double *vv = vec(inner + 1);
       // (already enqueued behind the previous iteration's Gram-Schmidt sweep when `ahead`)
@@ -217,11 +217,11 @@ static SolveResult gmres(nsx_handle *h, const Op &A, double *x, const double *b,
       // ... unless this iteration will probably be the last one: the residual after it is estimated from the last reduction factor
       // (rho * rho / rho_before); a wrong "continues" costs one wasted operator + preconditioner application, a wrong
       // "converges" one exposed host round trip, so the test leans towards not running ahead (NSX_AHEAD_MARGIN, default 2 x tol).
-      static const double ahead_margin = getenv("NSX_AHEAD_MARGIN") ? atof(getenv("NSX_AHEAD_MARGIN")) : 2.0;
+      static const double ahead_margin = env_double("NSX_AHEAD_MARGIN", 2.0);
       const bool likely_last = rho_before > 0.0 && rho * std::min(1.0, rho / rho_before) <= ahead_margin * tol;
       const std::function<void()> next_A = [&]() {
         if (inner + 1 < N_TMP - 2 && !likely_last) {
-          static const int ahead_mode = getenv("NSX_AHEAD_MODE") ? atoi(getenv("NSX_AHEAD_MODE")) : 2;
+          static const int ahead_mode = env_int("NSX_AHEAD_MODE", 2);
           if (ilu_conv) {  // the next iteration's product goes straight into its own vector; its preconditioner runs inside the next sweep's launch
             A(vec(inner + 2), vv);
             ahead = 1;
@@ -396,7 +396,7 @@ __global__ void k_same_and_keep(int n, const double *__restrict__ w, double *__r
 // Are the inputs of the Schur product the ones its current values were computed from?  (Bitwise comparison of the weight vector
 // on the device; the answer comes back through a mapped word behind one stream synchronisation.)
 static bool schur_inputs_unchanged(nsx_handle *h, int type) {
-  const bool cache = !(getenv("NSX_SCHUR_CACHE") && atoi(getenv("NSX_SCHUR_CACHE")) == 0);  // read per call: bench.py times both schedules on one handle
+  const bool cache = env_on("NSX_SCHUR_CACHE");  // read per call: bench.py times both schedules on one handle
   const int n = h->len_u;  // owned + ghost weights
   volatile int *flag = (volatile int *)(h->pub_host + N_SLOTS + 4);
   const bool had = h->schur_valid && h->schur_type == type && (int)h->schur_w_prev.n == n;
@@ -493,7 +493,7 @@ static void count(nsx_solve_stats *st, bool F, const SolveResult &r) {
 
 // NSX_STEP_FUSED=0: the launch sequence that follows the reference statement by statement.  Read once per call of the API
 // (solve_time_step, nsx_prec_vmult) and handed down: whether new basis vectors are zeroed and what prec_vmult overwrites must agree.
-static bool step_fused() { return !(getenv("NSX_STEP_FUSED") && atoi(getenv("NSX_STEP_FUSED")) == 0); }
+static bool step_fused() { return env_on("NSX_STEP_FUSED"); }
 
 void prec_vmult(nsx_handle *h, int type, double tol, int maxit, double *dst, const double *src, nsx_solve_stats *st, bool fused) {
   if (!h->prec_ready) NSX_THROW(NSX_ERR_ARG, "preconditioner not initialised");
@@ -629,7 +629,7 @@ void solve_time_step(nsx_handle *h, int type, double tol, double inner_rtol, int
   double t0 = now_s();
   h->defer_red = false;  // a solve that unwound in the middle of a batched reduction must not leave the handle deferring
   h->pending_red.clear();
-  static const bool trace = getenv("NSX_TRACE") != nullptr;
+  static const bool trace = env_set("NSX_TRACE");
   if (trace) fprintf(stderr, "[nsx trace] rank %d: solve_time_step: preconditioner set-up\n", h->rank);
   prec_initialize(h, type);  // NS3D.cpp:568-569
   HIP_CHECK(hipStreamSynchronize(h->stream));
@@ -652,7 +652,7 @@ void solve_time_step(nsx_handle *h, int type, double tol, double inner_rtol, int
   comm_halo_u(h, h->sol.p);
   comm_halo_p(h, h->sol.p + h->off_p);
   HIP_CHECK(hipStreamSynchronize(h->stream));
-  ilu_check(h);  // a triangular-solve kernel that refused to run (nsx_sparse.hip: k_ilu_solve_lanes) fails the call
+  ilu_check(h);  // a triangular-solve kernel that refused to run (nsx_ilu.hip: k_ilu_solve_lanes) fails the call
   st->t_solve = now_s() - t0;
   st->outer_iterations = r.steps;
   st->final_residual = r.last;

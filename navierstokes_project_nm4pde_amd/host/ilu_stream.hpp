@@ -1,4 +1,4 @@
-// ilu_stream.hpp — host-side schedule of the packed block-ILU(0) triangular solve (device kernel: csrc/nsx_sparse.hip,
+// ilu_stream.hpp — host-side schedule of the packed block-ILU(0) triangular solve (device kernel: csrc/nsx_ilu.hip,
 // k_ilu_solve_lanes), i.e. of TrilinosWrappers::PreconditionILU::vmult inside every inner Krylov iteration
 // (reference Navier-Stokes/include/Preconditioners.hpp:215-216,382,405; Ifpack_ILU::ApplyInverse, overlap 0 = one
 // independent factor per MPI rank).

@@ -1,4 +1,4 @@
-"""Extended-precision reference of the block-Jacobi ILU(0) (the factorisation, inversion and solve kernels of csrc/nsx_sparse.hip and
+"""Extended-precision reference of the block-Jacobi ILU(0) (the factorisation, inversion and solve kernels of csrc/nsx_ilu.hip and
 csrc/nsx_ilu_lanes.hpp), the yardstick they are measured with, and the comparisons the GPU tests call (tests/test_gpu_ilu.py; checked on
 the CPU by tests/test_ilu_reference.py).  A plain helper module, no fixtures, NumPy only.
 

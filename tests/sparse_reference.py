@@ -175,7 +175,7 @@ def column(o, op, j):
 # ------------------------------------------------------------------------------------------------ float64 restatements (CPU suite)
 def _sum64(t, order):
     """float64 sum of the terms t of one row in one of three orders: "forward", "reversed", or "lanes16" -- lane l of 16 adds the
-    terms l, l + 16, ... in turn, then the butterfly of group_sum<16> (csrc/nsx_sparse.hip): xor 1, xor 2, mirror in 8, mirror in 16"""
+    terms l, l + 16, ... in turn, then the butterfly of lane_group_sum<16> (csrc/nsx_internal.hpp): xor 1, xor 2, mirror in 8, mirror in 16"""
     if order == "lanes16":
         v = np.zeros(16)
         for k, tk in enumerate(t):

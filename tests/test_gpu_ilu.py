@@ -1,4 +1,4 @@
-"""GPU suite: every factorisation, inversion and solve kernel of the block-Jacobi ILU(0) (csrc/nsx_sparse.hip, csrc/nsx_ilu_lanes.hpp)
+"""GPU suite: every factorisation, inversion and solve kernel of the block-Jacobi ILU(0) (csrc/nsx_ilu.hip, csrc/nsx_ilu_lanes.hpp)
 DIRECTLY against an extended-precision restatement (tests/ilu_reference.py), entry by entry.
 
 A case = set the environment, nsx_set_ranks / nsx_set_schur_blocks, nsx_prec_initialize, then
@@ -30,7 +30,7 @@ pytestmark = pytest.mark.gpu
 MESHES = {"A": ("cylinder", 3, 1), "B": ("cylinder", 2, 2)}
 ENV_KEYS = ("NSX_ILU_EPT", "NSX_PF", "NSX_BPW_F", "NSX_BPW_S", "NSX_DENSE_S", "NSX_ILU_SMALL", "NSX_ILU_FACTOR_LDS", "NSX_ILU_INVERT_LDS",
             "NSX_LEVELLED_MIN", "NSX_DENSE_MAX", "NSX_ILU_MGS")
-# limits of csrc/nsx_sparse.hip / csrc/nsx_setup.hip the expected kernels follow from
+# limits of csrc/nsx_ilu.hip / csrc/nsx_setup.hip the expected kernels follow from
 ILU_WAVES, ILU_DENSE_ROWS, FACTOR_LDS_MAX, INVERT_LDS_ROWS, LEVELLED_MIN, LANES_K = 4, 512, 80 * 1024, 112, 4096, 12
 
 _state = {"handles": {}, "refs": {}, "factors": {}, "solves": {}}
