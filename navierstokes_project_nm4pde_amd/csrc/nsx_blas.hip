@@ -217,7 +217,7 @@ void v_add_and_dot(nsx_handle *h, Span sp, double *d, double a, int aslot, const
 }
 
 void wait_published(nsx_handle *h, unsigned long long seq) {
-  volatile unsigned long long *flag_host = (volatile unsigned long long *)(h->pub_host + N_SLOTS);
+  volatile unsigned long long *flag_host = pub_word_host<unsigned long long>(h, PUB_FLAG);
   unsigned long long spins = 0;
   // sequence numbers only grow: a later publication that has already landed also proves this one did
   while (__atomic_load_n(flag_host, __ATOMIC_ACQUIRE) < seq) {
@@ -246,9 +246,11 @@ __global__ __launch_bounds__(256) void k_axpby(int n, int split, int gap, double
 __global__ void k_scale_vec(int n, double *__restrict__ d, const double *__restrict__ f) {
   for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) d[i] *= f[i];
 }
+constexpr int MULTI_MAX = 32;  // vectors of one launch
+static_assert(MULTI_MAX >= KRYLOV_N_TMP + 2, "a GMRES cycle's update is one launch");
 struct MultiArgs {
-  const double *v[32];
-  double c[32];
+  const double *v[MULTI_MAX];
+  double c[MULTI_MAX];
   int k;
 };
 // START: where the sum starts from.  AX_SELF: x itself.  AX_FROM: x0 (x is only written).  AX_ZERO: 0.0 -- what reading a zeroed x gives,
@@ -320,9 +322,9 @@ void v_scale_vec(nsx_handle *h, int n, double *d, const double *f) {
 }
 void v_axpy_multi(nsx_handle *h, Span sp, double *x, int k, double *const *vs, const double *coef) {
   const int n = sp.n;
-  for (int j0 = 0; j0 < k; j0 += 32) {
+  for (int j0 = 0; j0 < k; j0 += MULTI_MAX) {
     MultiArgs m;
-    m.k = std::min(32, k - j0);
+    m.k = std::min(MULTI_MAX, k - j0);
     for (int j = 0; j < m.k; ++j) {
       m.v[j] = vs[j0 + j];
       m.c[j] = coef[j0 + j];
@@ -332,10 +334,10 @@ void v_axpy_multi(nsx_handle *h, Span sp, double *x, int k, double *const *vs, c
   }
 }
 
-// The same update when x does not hold its starting value yet (k <= 32): x = x0 + sum (x0 != nullptr), or x = sum (x0 == nullptr: the
+// The same update when x does not hold its starting value yet (k <= MULTI_MAX): x = x0 + sum (x0 != nullptr), or x = sum (x0 == nullptr: the
 // starting value is zero), the latter optionally followed by x = -y + x (y may be x itself).  One launch; x is only written.
 void v_axpy_multi_into(nsx_handle *h, Span sp, double *x, const double *x0, const double *y, int k, double *const *vs, const double *coef) {
-  if (k > 32 || (x0 && y)) NSX_THROW(NSX_ERR_ARG, "internal: v_axpy_multi_into takes one launch's worth of vectors, and y only with a zero start");
+  if (k > MULTI_MAX || (x0 && y)) NSX_THROW(NSX_ERR_ARG, "internal: v_axpy_multi_into takes one launch's worth of vectors, and y only with a zero start");
   const int n = sp.n;
   MultiArgs m;
   m.k = k;
@@ -376,7 +378,7 @@ unsigned long long publish_scalars(nsx_handle *h, int slot0, int count) {
     h->slot_nb[slot0 + i] = 0;
   }
   const unsigned long long seq = ++h->pub_seq;
-  unsigned long long *flag_dev = (unsigned long long *)(h->pub_dev + N_SLOTS);
+  unsigned long long *flag_dev = pub_word_dev<unsigned long long>(h, PUB_FLAG);
   hipLaunchKernelGGL(k_publish, dim3(count), dim3(256), 0, h->stream, slot0, count, args, h->red_partial.p, h->scal.p, h->pub_dev, flag_dev, seq,
                      h->pub_counter.p);
   return seq;
@@ -394,16 +396,14 @@ void write_scalar(nsx_handle *h, int slot, double v) {
   HIP_CHECK(hipStreamSynchronize(h->stream));
 }
 
-int cg_dirty_words(nsx_handle *h);
-
 }  // namespace nsx
 
 extern "C" int nsx_persistent_state(nsx_handle *h, int state[4]) {
   if (!h || !state) return NSX_ERR_ARG;
   NSX_TRY(h)
   HIP_CHECK(hipSetDevice(h->prm.device));
-  state[0] = h->mgs.box.p != nullptr && !h->mgs.disabled && h->mgs.max_wg > 0;
-  state[1] = h->cg_box.p != nullptr && !h->cg_disabled && h->cg_max_wg > 0;
+  state[0] = h->mgs.box.allocated() && !h->mgs.disabled && h->mgs.max_wg > 0;
+  state[1] = h->cg.box.allocated() && !h->cg.disabled && h->cg.max_wg > 0;
   state[2] = h->n_persistent_fallbacks;
   state[3] = nsx::mgs_dirty_words(h) + nsx::cg_dirty_words(h);
   NSX_CATCH(h)
@@ -425,7 +425,7 @@ extern "C" int nsx_path_info(nsx_handle *h, int info[32]) {
   info[5] = h->mgs.last_dist;
   info[6] = h->mgs.max_e_seen;
   info[7] = h->cu_reserved;
-  info[8] = h->cg_last_path;
+  info[8] = h->cg.last_path;
   info[9] = h->schedS.n_blocks;
   info[10] = (int)h->haloU.nbr.size();
   info[11] = h->haloU.nbr.empty() ? 0 : h->haloU.send_ptr[h->haloU.nbr.size()];
@@ -456,8 +456,8 @@ extern "C" int nsx_path_info(nsx_handle *h, int info[32]) {
   info[25] = h->mgs.fused_launches;
   info[26] = h->inner_F_fp32_used;
   info[27] = h->ilu_F_fp32_used;
-  info[28] = h->cg_last_rpg;
-  info[29] = h->cg_last_lres;
+  info[28] = h->cg.last_rpg;
+  info[29] = h->cg.last_lres;
   info[30] = b.max_rows;
   info[31] = b.max_ucols;
   NSX_CATCH(h)

@@ -27,7 +27,6 @@ constexpr int CG_MAX_WG = 1024;
 constexpr int CG_NV = 3;        // values per exchange
 constexpr int CG_RING = 4;      // mailbox rows in flight; row (e + 2) % 4 is emptied at exchange e
 constexpr size_t CG_REGION = (size_t)CG_RING * CG_NV * CG_MAX_WG + (size_t)CG_RING * CG_NV;
-enum { S_CGP = 100 };           // scalar slots of the publication: steps, last residual, status, tolerance
 
 __device__ __forceinline__ double ld_agent(const double *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void st_agent(double *p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -442,7 +441,7 @@ __global__ __launch_bounds__(CG_THREADS) void k_cg_schur(const int32_t *__restri
 // host: slab layout of negative_S_tilde per Schur ILU block (see above).  Built with the ILU schedules; values are
 // refreshed by cg_pack_values after every numeric Schur product.
 void build_cg_plan(nsx_handle *h) {
-  CgPlan &pl = h->cgplan;
+  CgPlan &pl = h->cg.plan;
   pl.ok = false;
   const IluSchedule &s = h->schedS;
   if (!s.dense || s.max_rows > CG_MAXB) return;  // (distributed handles use the plan through cg_schur_fused: columns may be ghosts)
@@ -504,7 +503,7 @@ void build_cg_plan(nsx_handle *h) {
 
 // after schur_numeric: the packed copy of the values
 void cg_pack_values(nsx_handle *h) {
-  CgPlan &pl = h->cgplan;
+  CgPlan &pl = h->cg.plan;
   if (!pl.ok) return;
   LaunchScope ls(h, "cg_pack", 20.0 * (double)pl.n_slots);
   hipLaunchKernelGGL(k_cg_pack, dim3(cdiv(pl.n_slots, 256)), dim3(256), 0, h->stream, pl.n_slots, pl.s_src.p, h->vSchur.p, pl.s_val.p);
@@ -512,102 +511,91 @@ void cg_pack_values(nsx_handle *h) {
 }
 
 static void cg_setup(nsx_handle *h) {
-  if (h->cg_box.p || h->cg_disabled) return;
-  h->cg_max_wg = 0;
+  CgState &c = h->cg;
+  if (c.box.allocated() || c.disabled) return;
+  c.max_wg = 0;
   if (!env_on("NSX_CG_PERSISTENT")) {
-    h->cg_disabled = true;
+    c.disabled = true;
     return;
   }
-  int cus = 0, per_cu = 0;
-  HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->prm.device));
-  int per_cu_res[2] = {0, 0};
-  HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_cg_schur<0, false>, CG_THREADS, 0));
-  HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_res[0], k_cg_schur<6, false>, CG_THREADS, 0));
-  HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_res[1], k_cg_schur<8, false>, CG_THREADS, 0));
-  h->cg_max_wg_res[0] = std::min(CG_MAX_WG, per_cu_res[0] * cus);
-  h->cg_max_wg_res[1] = std::min(CG_MAX_WG, per_cu_res[1] * cus);
-  int per_cu_lres[2] = {0, 0};
-  HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_lres[0], k_cg_schur<6, true>, CG_THREADS, 0));
-  HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_lres[1], k_cg_schur<8, true>, CG_THREADS, 0));
-  h->cg_max_wg_lres[0] = std::min(CG_MAX_WG, per_cu_lres[0] * cus);
-  h->cg_max_wg_lres[1] = std::min(CG_MAX_WG, per_cu_lres[1] * cus);
-  h->cg_box.alloc(2 * CG_REGION + 2);
-  HIP_CHECK(hipMemsetAsync(h->cg_box.p, 0xff, 2 * CG_REGION * sizeof(unsigned long long), h->stream));
-  HIP_CHECK(hipMemsetAsync(h->cg_box.p + 2 * CG_REGION, 0, 2 * sizeof(unsigned long long), h->stream));
-  h->cg_max_wg = std::min(CG_MAX_WG, per_cu * cus);
+  auto grid = [&](auto fn) { return resident_grid(h, (const void *)fn, CG_THREADS); };
+  const ResidentGrid g0 = grid(k_cg_schur<0, false>), res[2] = {grid(k_cg_schur<6, false>), grid(k_cg_schur<8, false>)},
+                     lres[2] = {grid(k_cg_schur<6, true>), grid(k_cg_schur<8, true>)};
+  for (int k = 0; k < 2; ++k) {
+    c.max_wg_res[k] = std::min(CG_MAX_WG, res[k].slots());
+    c.max_wg_lres[k] = std::min(CG_MAX_WG, lres[k].slots());
+  }
+  c.box.alloc(CG_REGION, 2);
+  c.box.clear(h->stream);
+  c.max_wg = std::min(CG_MAX_WG, g0.slots());
   if (nsx_debug())
-    fprintf(stderr, "[nsx] persistent Schur CG: %d CUs x %d resident workgroups, grid <= %d (block inverses in registers: <= 96 rows x %d, <= 128 rows x %d; operator in LDS as well: x %d, x %d)\n", cus, per_cu,
-            h->cg_max_wg, per_cu_res[0], per_cu_res[1], per_cu_lres[0], per_cu_lres[1]);
+    fprintf(stderr, "[nsx] persistent Schur CG: %d CUs x %d resident workgroups, grid <= %d (block inverses in registers: <= 96 rows x %d, <= 128 rows x %d; operator in LDS as well: x %d, x %d)\n", g0.cus, g0.per_cu,
+            c.max_wg, res[0].per_cu, res[1].per_cu, lres[0].per_cu, lres[1].per_cu);
 }
 
 // CG on negative_S_tilde with the explicit block inverses as preconditioner, one launch.  Returns false when the launch-per-
 // operation path has to be used instead (distributed run, blocks too large or too many, persistent kernels disabled).
-bool cg_schur_persistent(nsx_handle *h, double *x, const double *b, double rtol, int maxiter, int *steps, double *last, int *status) {
+bool cg_schur_persistent(nsx_handle *h, double *x, const double *b, double rtol, int maxiter, SolveResult &res) {
   const IluSchedule &s = h->schedS;
-  const CgPlan &pl = h->cgplan;
+  CgState &c = h->cg;
+  const CgPlan &pl = c.plan;
   if (h->comm || !s.dense || s.max_rows > CG_MAXB || !pl.ok || !pl.values_current) return false;
   cg_setup(h);
-  if (h->cg_max_wg == 0 || s.n_blocks > h->cg_max_wg) return false;
+  if (c.max_wg == 0 || s.n_blocks > c.max_wg) return false;
   const bool pres_ok = env_on("NSX_CG_PRES");  // read per solve: the tests switch it
   // rows per group of the register-resident variant: the smallest that holds the largest block, if its grid is resident
-  const int rpg = !pres_ok ? 0 : (s.max_rows <= 96 && s.n_blocks <= h->cg_max_wg_res[0]) ? 6 : (s.max_rows <= 128 && s.n_blocks <= h->cg_max_wg_res[1]) ? 8 : 0;
+  const int rpg = !pres_ok ? 0 : (s.max_rows <= 96 && s.n_blocks <= c.max_wg_res[0]) ? 6 : (s.max_rows <= 128 && s.n_blocks <= c.max_wg_res[1]) ? 8 : 0;
   const bool pres = rpg > 0;
   const bool lres_ok = env_on("NSX_CG_LRES");
   // ... and the block's rows of the operator in LDS, if every block fits the pool and that grid is resident too
-  const bool lres = lres_ok && pres && pl.max_block_nnz <= CG_LPOOL && s.n_blocks <= h->cg_max_wg_lres[rpg == 6 ? 0 : 1];
+  const bool lres = lres_ok && pres && pl.max_block_nnz <= CG_LPOOL && s.n_blocks <= c.max_wg_lres[rpg == 6 ? 0 : 1];
   const int n = h->n_p;
-  if ((int)h->cg_vec.n < 3 * n) h->cg_vec.alloc((size_t)3 * n);
-  double *D0 = h->cg_vec.p, *D1 = D0 + n, *H = D1 + n;
+  if ((int)c.vec.n < 3 * n) c.vec.alloc((size_t)3 * n);
+  double *D0 = c.vec.p, *D1 = D0 + n, *H = D1 + n;
   const unsigned long long seq = ++h->pub_seq;
-  unsigned long long *box = h->cg_box.p + (size_t)h->cg_parity * CG_REGION, *box_other = h->cg_box.p + (size_t)(1 - h->cg_parity) * CG_REGION;
-  int *err_dev = (int *)(h->cg_box.p + 2 * CG_REGION);
-  double *pub_vals = h->pub_dev + S_CGP;
-  unsigned long long *pub_flag = (unsigned long long *)(h->pub_dev + N_SLOTS);
   ProfEntry *pe = nullptr;
   {
     LaunchScope ls(h, "cg_S", 0.0);
     pe = ls.e;
-#define NSX_CG_GO(PRES_, LRES_)                                                                                                                       \
-  hipLaunchKernelGGL((k_cg_schur<PRES_, LRES_>), dim3(s.n_blocks), dim3(CG_THREADS), 0, h->stream, s.block_ptr.p, pl.u_ptr.p, pl.u_cols.p, pl.s_ptr.p,  \
-                     pl.s_val.p, pl.s_lidx.p, pl.s_info.p, s.dn_off.p, s.dn_P.p, b, x, D0, D1, H, rtol, maxiter, box, box_other, pub_vals, pub_flag, seq, \
-                     err_dev, h->gx_drop_wg, h->gS.rowptr.p, h->vSchur.p, pl.a_lidx.p)
-    if (rpg == 6 && lres) NSX_CG_GO(6, true); else if (rpg == 8 && lres) NSX_CG_GO(8, true);
-    else if (rpg == 6) NSX_CG_GO(6, false); else if (rpg == 8) NSX_CG_GO(8, false); else NSX_CG_GO(0, false);
-#undef NSX_CG_GO
-    if (nsx_debug() && (h->cg_resident != pres || h->cg_lds_resident != lres || !h->cg_variant_said)) {
+    auto go = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, dim3(s.n_blocks), dim3(CG_THREADS), 0, h->stream, s.block_ptr.p, pl.u_ptr.p, pl.u_cols.p, pl.s_ptr.p, pl.s_val.p, pl.s_lidx.p,
+                         pl.s_info.p, s.dn_off.p, s.dn_P.p, b, x, D0, D1, H, rtol, maxiter, c.box.cur(), c.box.other(), h->pub_dev + S_CGP,
+                         pub_word_dev<unsigned long long>(h, PUB_FLAG), seq, (int *)c.box.tail(), h->gx_drop_wg, h->gS.rowptr.p, h->vSchur.p, pl.a_lidx.p);
+    };
+    with_int<0, 6, 8>(rpg, [&](auto R) {
+      if constexpr (decltype(R)::value != 0) {  // (<0, true> does not exist: the operator sits in LDS only beside the block inverses in registers)
+        if (lres) return go(k_cg_schur<decltype(R)::value, true>);
+      }
+      go(k_cg_schur<decltype(R)::value, false>);
+    });
+    if (nsx_debug() && (c.resident != pres || c.lds_resident != lres || !c.variant_said)) {
       fprintf(stderr, "[nsx] Schur CG variant: block inverses in registers %d (rows per lane group %d), operator in LDS %d (largest block: %d entries)\n", (int)pres, rpg,
               (int)lres, (int)pl.max_block_nnz);
-      h->cg_variant_said = true;
+      c.variant_said = true;
     }
-    h->cg_resident = pres;
-    h->cg_lds_resident = lres;
-    h->cg_last_rpg = rpg;
-    h->cg_last_lres = lres ? 1 : 0;
+    c.resident = pres;
+    c.lds_resident = lres;
+    c.last_rpg = rpg;
+    c.last_lres = lres ? 1 : 0;
   }
-  h->cg_parity ^= 1;
-  h->cg_last_path = 2;
+  c.box.flip();
+  c.last_path = 2;
   wait_published(h, seq);
-  const int st = (int)h->pub_host[S_CGP + 2];
-  if (st == 3) {
-    // a workgroup never arrived (the grid was not co-resident: something else holds compute units).  x is untouched; clean
-    // up and leave the persistent path for good on this handle
-    HIP_CHECK(hipStreamSynchronize(h->stream));
-    HIP_CHECK(hipMemsetAsync(h->cg_box.p, 0xff, 2 * CG_REGION * sizeof(unsigned long long), h->stream));
-    HIP_CHECK(hipMemsetAsync(h->cg_box.p + 2 * CG_REGION, 0, 2 * sizeof(unsigned long long), h->stream));
-    h->cg_max_wg = 0;
-    h->cg_disabled = true;
-    h->n_persistent_fallbacks++;
-    h->cg_last_rpg = h->cg_last_lres = 0;  // the solve that is reported is the one the caller runs next
-    fprintf(stderr, "[nsx] warning: the persistent Schur CG timed out (grid not co-resident): this handle uses one launch per operation from now on\n");
+  const double *pub = h->pub_host + S_CGP;  // steps, last residual, status (3: a workgroup never arrived), tolerance
+  if ((int)pub[2] == 3) {
+    // x is untouched; clean up and leave the persistent path for good on this handle
+    grid_gave_up(h, c.box, false, "Schur CG", "operation", [&] {
+      c.max_wg = 0;
+      c.disabled = true;
+      c.last_rpg = c.last_lres = 0;  // the solve that is reported is the one the caller runs next
+    });
     return false;
   }
-  *steps = (int)h->pub_host[S_CGP];
-  *last = h->pub_host[S_CGP + 1];
-  *status = st;
+  res = SolveResult{(int)pub[2], (int)pub[0], pub[1]};
   // algorithmic bytes: per iteration the matrix (12 B / entry) and the block inverses once, plus the vectors
   // (block inverses resident in registers: read once per solve)
   // (operator resident in LDS: read once per solve, too)
-  if (pe) pe->bytes += (lres ? 1.0 : (double)(*steps + 1)) * 10.0 * h->gS.nnz() + (double)(*steps + 1) * 48.0 * n + (pres ? 1.0 : (double)(*steps + 1)) * 8.0 * (double)s.dn_entries;
+  if (pe) pe->bytes += (lres ? 1.0 : (double)(res.steps + 1)) * 10.0 * h->gS.nnz() + (double)(res.steps + 1) * 48.0 * n + (pres ? 1.0 : (double)(res.steps + 1)) * 8.0 * (double)s.dn_entries;
   return true;
 }
 
@@ -810,43 +798,43 @@ __global__ __launch_bounds__(CG_THREADS) void k_cgd_B(const int32_t *__restrict_
   cgd_clear_tail(mine, 2);
 }
 
-bool cg_schur_fused(nsx_handle *h, double *x, const double *b, double rtol, int maxiter, int *steps, double *last, int *status) {
+bool cg_schur_fused(nsx_handle *h, double *x, const double *b, double rtol, int maxiter, SolveResult &out) {
   const IluSchedule &s = h->schedS;
-  const CgPlan &pl = h->cgplan;
+  const CgPlan &pl = h->cg.plan;
   const bool wanted = env_on("NSX_CG_FUSED");  // read per solve: the tests switch it inside one process
   if (!wanted) return false;  // (one GPU: reached when the persistent kernel cannot run -- more Schur blocks than resident workgroups, i.e. beyond ~1.16 M DoF)
   // whether THIS rank's Schur blocks fit the kernels (dense inverses, <= 256 rows, <= 1024 unique columns per block) depends on its
   // own part of the mesh: the ranks agree once per set of schedules, or one of them would run the launch-per-operation solver's
   // collectives against the others' (found by the 2-process test with 6 virtual ranks per GPU: one rank had a 260-row block)
-  if (h->cgd_agreed < 0)
-    h->cgd_agreed = comm_agree_all(h, s.dense && s.max_rows <= CG_MAXB && pl.ok && s.n_blocks <= CGD_PARTS * CGD_FOLD_MAX && CG_THREADS == 256) ? 1 : 0;
-  if (!h->cgd_agreed) return false;
+  if (h->cg.d_agreed < 0)
+    h->cg.d_agreed = comm_agree_all(h, s.dense && s.max_rows <= CG_MAXB && pl.ok && s.n_blocks <= CGD_PARTS * CGD_FOLD_MAX && CG_THREADS == 256) ? 1 : 0;
+  if (!h->cg.d_agreed) return false;
   if (!pl.values_current) cg_pack_values(h);  // (as the persistent variant's fall-back to the launch-per-operation solver used to allow: a stale packed copy is refreshed, not an error)
   const int n = h->n_p, len = h->len_p, nblk = s.n_blocks;
   // more blocks than entries of a partial-sum array: raw sums + fold (see CGD_PARTS)
   const bool fold = nblk > CGD_PARTS;
   const int fold_grp = cdiv(nblk, CGD_PARTS);
-  if (fold && (int)h->cgd_raw.n < 3 * nblk) h->cgd_raw.alloc((size_t)3 * nblk);
+  if (fold && (int)h->cg.d_raw.n < 3 * nblk) h->cg.d_raw.alloc((size_t)3 * nblk);
   auto fold_into = [&](double *dst, int n_arrays) {
-    if (fold) hipLaunchKernelGGL(k_cgd_fold, dim3(4 * n_arrays), dim3(256), 0, h->stream, nblk, fold_grp, h->cgd_raw.p, dst);
+    if (fold) hipLaunchKernelGGL(k_cgd_fold, dim3(4 * n_arrays), dim3(256), 0, h->stream, nblk, fold_grp, h->cg.d_raw.p, dst);
   };
-  h->cg_last_path = 3;
-  if ((int)h->cgd_vec.n < 3 * n + 2 * len) {
-    h->cgd_vec.alloc((size_t)3 * n + 2 * len);
-    h->cgd_vec.zero(h->stream);
+  h->cg.last_path = 3;
+  if ((int)h->cg.d_vec.n < 3 * n + 2 * len) {
+    h->cg.d_vec.alloc((size_t)3 * n + 2 * len);
+    h->cg.d_vec.zero(h->stream);
   }
-  if (!h->cgd_parts.p) {
-    h->cgd_parts.alloc(CGD_TOTAL);
-    h->cgd_parts.zero(h->stream);  // entries beyond a rank's blocks stay 0 for good: the collectives add them element-wise
+  if (!h->cg.d_parts.p) {
+    h->cg.d_parts.alloc(CGD_TOTAL);
+    h->cg.d_parts.zero(h->stream);  // entries beyond a rank's blocks stay 0 for good: the collectives add them element-wise
   }
-  double *G = h->cgd_vec.p, *H = G + n, *Hv = H + n, *D[2] = {Hv + n, Hv + n + len}, *parts = h->cgd_parts.p;
+  double *G = h->cg.d_vec.p, *H = G + n, *Hv = H + n, *D[2] = {Hv + n, Hv + n + len}, *parts = h->cg.d_parts.p;
   double *pub_vals = h->pub_dev + S_CGP;
-  unsigned long long *pub_flag = (unsigned long long *)(h->pub_dev + N_SLOTS);
+  unsigned long long *pub_flag = pub_word_dev<unsigned long long>(h, PUB_FLAG);
   comm_halo_p(h, x);  // the ghost entries of the initial guess
   {
     LaunchScope ls(h, "cgd_init", 12.0 * h->gS.nnz() + 8.0 * (double)s.dn_entries + 40.0 * n);
     hipLaunchKernelGGL(k_cgd_init, dim3(nblk), dim3(CG_THREADS), 0, h->stream, s.block_ptr.p, pl.u_ptr.p, pl.u_cols.p, pl.s_ptr.p, pl.s_val.p, pl.s_lidx.p,
-                       pl.s_info.p, s.dn_off.p, s.dn_P.p, b, x, G, H, fold ? h->cgd_raw.p : parts + CGD_P0, fold ? nblk : CGD_PARTS);
+                       pl.s_info.p, s.dn_off.p, s.dn_P.p, b, x, G, H, fold ? h->cg.d_raw.p : parts + CGD_P0, fold ? nblk : CGD_PARTS);
     fold_into(parts + CGD_P0, 3);
   }
   comm_allreduce_partials(h, parts + CGD_P0, 3 * CGD_PARTS);
@@ -869,42 +857,29 @@ bool cg_schur_fused(nsx_handle *h, double *x, const double *b, double rtol, int 
     {
       LaunchScope ls(h, "cgd_A", 10.0 * h->gS.nnz() + 40.0 * n);
       hipLaunchKernelGGL(k_cgd_A, dim3(nblk), dim3(CG_THREADS), 0, h->stream, s.block_ptr.p, pl.u_ptr.p, pl.u_cols.p, pl.s_ptr.p, pl.s_val.p, pl.s_lidx.p, pl.s_info.p,
-                         n, nx, parts, H, Dp, Dc, Hv, fold ? h->cgd_raw.p : parts + CGD_DH, pub_vals, pub_flag, seq);
+                         n, nx, parts, H, Dp, Dc, Hv, fold ? h->cg.d_raw.p : parts + CGD_DH, pub_vals, pub_flag, seq);
       fold_into(parts + CGD_DH, 1);
     }
     comm_allreduce_partials(h, parts + CGD_DH, CGD_PARTS);
     wait_published(h, seq);
     if (it == 0) tol = rtol * std::sqrt(h->pub_host[S_CGP + 1]);  // solver_control_S(maxiter, 1e-2 * tmp.l2_norm())
     res = std::sqrt(std::fabs(h->pub_host[S_CGP]));
-    conv = res <= tol ? 1 : ((it >= maxiter || res != res) ? 2 : 0);  // SolverControl::check
+    conv = sc_check(it, res, tol, maxiter);
     if (conv != 0) break;
     it = nx;
     {
       LaunchScope ls(h, "cgd_B", 8.0 * (double)s.dn_entries + 56.0 * n);
       double *mine = parts + ((it & 1) ? CGD_P1 : CGD_P0);
-      hipLaunchKernelGGL(k_cgd_B, dim3(nblk), dim3(CG_THREADS), 0, h->stream, s.block_ptr.p, s.dn_off.p, s.dn_P.p, it, parts, x, G, H, Dc, Hv, fold ? h->cgd_raw.p : mine,
+      hipLaunchKernelGGL(k_cgd_B, dim3(nblk), dim3(CG_THREADS), 0, h->stream, s.block_ptr.p, s.dn_off.p, s.dn_P.p, it, parts, x, G, H, Dc, Hv, fold ? h->cg.d_raw.p : mine,
                          fold ? nblk : CGD_PARTS);
       fold_into(mine, 2);
     }
     comm_allreduce_partials(h, parts + ((it & 1) ? CGD_P1 : CGD_P0), 2 * CGD_PARTS);
   }
-  *steps = it;
-  *last = res;
-  *status = conv == 1 ? 0 : 1;
+  out = SolveResult{conv == 1 ? 0 : 1, it, res};
   return true;
 }
 
-// diagnostics (nsx_persistent_state): mailbox words of both regions that are not empty while nothing is in flight
-int cg_dirty_words(nsx_handle *h) {
-  if (!h->cg_box.p) return 0;
-  std::vector<unsigned long long> w(2 * CG_REGION);
-  HIP_CHECK(hipStreamSynchronize(h->stream));
-  HIP_CHECK(hipMemcpy(w.data(), h->cg_box.p, w.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-  // the region the next launch will use must be all empty; the other one holds the last solve's sums (its successor clears it)
-  const size_t base = (size_t)h->cg_parity * CG_REGION;
-  int dirty = 0;
-  for (size_t q = 0; q < CG_REGION; ++q) dirty += w[base + q] != GX_EMPTY;
-  return dirty;
-}
+int cg_dirty_words(nsx_handle *h) { return h->cg.box.dirty_words(h); }  // diagnostics (nsx_persistent_state)
 
 }  // namespace nsx

@@ -118,13 +118,13 @@ bool comm_on_stream(const nsx_handle *h) { return h->comm && h->comm->comm; }
 bool comm_agree_all(nsx_handle *h, bool mine) {
   Comm *c = h->comm;
   if (!c || (c->world == 1 && !c->comm)) return mine;
-  h->scal_host[N_SLOTS - 1] = mine ? 0.0 : 1.0;  // the sum of the objections
-  HIP_CHECK(hipMemcpyAsync(h->scal.p + N_SLOTS - 1, h->scal_host + N_SLOTS - 1, sizeof(double), hipMemcpyHostToDevice, h->stream));
-  h->slot_nb[N_SLOTS - 1] = 0;
-  comm_allreduce_scalars(h, N_SLOTS - 1, 1);
-  HIP_CHECK(hipMemcpyAsync(h->scal_host + N_SLOTS - 1, h->scal.p + N_SLOTS - 1, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  h->scal_host[S_AGREE] = mine ? 0.0 : 1.0;  // the sum of the objections
+  HIP_CHECK(hipMemcpyAsync(h->scal.p + S_AGREE, h->scal_host + S_AGREE, sizeof(double), hipMemcpyHostToDevice, h->stream));
+  h->slot_nb[S_AGREE] = 0;
+  comm_allreduce_scalars(h, S_AGREE, 1);
+  HIP_CHECK(hipMemcpyAsync(h->scal_host + S_AGREE, h->scal.p + S_AGREE, sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIP_CHECK(hipStreamSynchronize(h->stream));
-  return h->scal_host[N_SLOTS - 1] == 0.0;
+  return h->scal_host[S_AGREE] == 0.0;
 }
 
 // A communication stream of the device's highest priority would take its hardware queue from another pool than the compute
@@ -411,9 +411,7 @@ void comm_destroy(nsx_handle *h) {
     } catch (const Error &) {
     }
   }
-  h->cu_reserve_failed = false;
-  h->mgs.leave_req = false;
-  h->mgs.local_timeouts = 0;
+  krylov_communicator_gone(h);
   for (HaloPlan *p : {&h->haloU, &h->haloP})
     if (p->ev_done) {
       (void)hipEventDestroy(p->ev_done);
@@ -453,9 +451,7 @@ int nsx_comm_init(nsx_handle *h, int rank, int world, const uint8_t id[128]) {
   NCCL_CHECK(ncclCommInitRank(&h->comm->comm, world, u, rank));
   h->self_p2p = nsx::env_int("NSX_EXT_SELF_P2P", 0);
   nsx::comm_prepare_streams(h);
-  h->mgs.dist_state = -1;  // a new communicator: the paths the ranks choose together are chosen again
-  h->mgs.dist_fit.clear();
-  h->cgd_agreed = -1;
+  nsx::krylov_new_communicator(h);
   NSX_CATCH(h)
 }
 
@@ -512,9 +508,7 @@ int nsx_comm_init_callbacks(nsx_handle *h, int rank, int world, nsx_allreduce_fn
   h->comm->allreduce = allreduce;
   h->comm->exchange = exchange;
   h->comm->ctx = ctx;
-  h->mgs.dist_state = -1;
-  h->mgs.dist_fit.clear();
-  h->cgd_agreed = -1;
+  nsx::krylov_new_communicator(h);
   NSX_CATCH(h)
 }
 

@@ -293,15 +293,16 @@ static double run_diagnostics(nsx_handle *h, nsx_flow_diag *out) {
   double cfl = t[NSX_DIAG_CFL], speed = t[NSX_DIAG_SPEED];
   if (h->comm) {
     // every rank issues the same two collectives, whatever it found: an error is reported behind them, never instead of them
-    // scalar slots 0..7 are per-solve scratch of the Krylov drivers (written before they are read in every solve, nothing is carried
-    // from one call to the next), as nsx_compute_forces uses slots 0 and 1
-    for (int i = 0; i < 8; ++i) {
-      h->scal_host[i] = s[i];
-      h->slot_nb[i] = 0;
+    // the slots of S_POST are per-solve scratch of the Krylov drivers (written before they are read in every solve, nothing is carried
+    // from one call to the next), as nsx_compute_forces uses the first two
+    static_assert(sizeof(s) / sizeof(s[0]) == S_POST_LEN, "the slot table has the length");
+    for (int i = 0; i < S_POST_LEN; ++i) {
+      h->scal_host[S_POST + i] = s[i];
+      h->slot_nb[S_POST + i] = 0;
     }
-    HIP_CHECK(hipMemcpyAsync(h->scal.p, h->scal_host, 8 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    comm_allreduce_scalars(h, 0, 8);
-    read_scalars(h, 0, 8, s);
+    HIP_CHECK(hipMemcpyAsync(h->scal.p + S_POST, h->scal_host + S_POST, S_POST_LEN * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    comm_allreduce_scalars(h, S_POST, S_POST_LEN);
+    read_scalars(h, S_POST, S_POST_LEN, s);
     // the maxima through the same SUM collective: every rank fills its own slot of a zeroed vector (x + 0 is exact, NaN and inf survive)
     const int w = h->world;
     std::vector<double> m((size_t)2 * w, 0.0);

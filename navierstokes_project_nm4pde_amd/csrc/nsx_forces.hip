@@ -134,12 +134,13 @@ int nsx_compute_forces(nsx_handle *h, double *drag, double *lift) {
     }
   }
   if (h->comm) {  // Utilities::MPI::sum (NS3D.cpp:830-831)
-    h->scal_host[0] = sums[0];
-    h->scal_host[1] = sums[1];
-    HIP_CHECK(hipMemcpyAsync(h->scal.p, h->scal_host, 2 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    h->slot_nb[0] = h->slot_nb[1] = 0;
-    nsx::comm_allreduce_scalars(h, 0, 2);
-    nsx::read_scalars(h, 0, 2, sums);
+    const int s0 = nsx::S_POST;  // per-solve scratch of the Krylov drivers between solves (the slot table: nsx_internal.hpp)
+    h->scal_host[s0] = sums[0];
+    h->scal_host[s0 + 1] = sums[1];
+    HIP_CHECK(hipMemcpyAsync(h->scal.p + s0, h->scal_host + s0, 2 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    h->slot_nb[s0] = h->slot_nb[s0 + 1] = 0;
+    nsx::comm_allreduce_scalars(h, s0, 2);
+    nsx::read_scalars(h, s0, 2, sums);
   }
   *drag = sums[0];
   *lift = sums[1];

@@ -98,4 +98,42 @@ __device__ __forceinline__ double gx_block_sum(double v, double *sh) {
   return (sh[0] + sh[1]) + (sh[2] + sh[3]);
 }
 
+// ---- host half: what every persistent grid needs around its launches (the mailboxes themselves: GridBox, nsx_internal.hpp)
+
+// The region the next launch will use must be all empty; the other one holds the last launch's sums (its successor clears it)
+inline int GridBox::dirty_words(nsx_handle *h) const {
+  if (!allocated()) return 0;
+  std::vector<unsigned long long> w(region);
+  HIP_CHECK(hipStreamSynchronize(h->stream));
+  HIP_CHECK(hipMemcpy(w.data(), cur(), region * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  int dirty = 0;
+  for (unsigned long long v : w) dirty += v != GX_EMPTY;
+  return dirty;
+}
+
+// How many workgroups of `fn` (threads per workgroup, shm bytes of dynamic LDS) the device holds at once: cus * per_cu.  The callers
+// apply their own caps.
+struct ResidentGrid {
+  int cus = 0, per_cu = 0;
+  int slots() const { return cus * per_cu; }
+};
+inline ResidentGrid resident_grid(nsx_handle *h, const void *fn, int threads, size_t shm = 0) {
+  ResidentGrid g;
+  HIP_CHECK(hipDeviceGetAttribute(&g.cus, hipDeviceAttributeMultiprocessorCount, h->prm.device));
+  HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&g.per_cu, fn, threads, shm));
+  return g;
+}
+
+// A persistent grid ended on a time-out (it was not co-resident: something else holds compute units).  Wait for the stragglers, let the
+// caller look at what the grid left (own: its commit words, its own limits and flags), empty the mailboxes, count the fallback and say so.
+template <class Own>
+inline void grid_gave_up(nsx_handle *h, GridBox &box, bool comm_stream_too, const char *what, const char *unit, Own &&own) {
+  HIP_CHECK(hipStreamSynchronize(h->stream));
+  if (comm_stream_too && h->comm_stream) HIP_CHECK(hipStreamSynchronize(h->comm_stream));
+  own();
+  box.clear(h->stream);
+  h->n_persistent_fallbacks++;
+  fprintf(stderr, "[nsx] warning: the persistent %s timed out (grid not co-resident): this handle uses one launch per %s from now on\n", what, unit);
+}
+
 }  // namespace nsx

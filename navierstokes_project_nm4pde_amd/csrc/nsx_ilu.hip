@@ -514,7 +514,7 @@ static void ilu_solve_levelled(nsx_handle *h, const DevCsr &g, const IluSchedule
 // The factorisation kernels report a failure (row too long, zero pivot) through a word in mapped host memory, written only
 // when something is wrong; ilu_check() looks at it after the caller's next synchronisation (no stream sync, no copy here).
 void ilu_check(nsx_handle *h) {
-  volatile int *err = (volatile int *)(h->pub_host + N_SLOTS + 3);
+  volatile int *err = pub_word_host(h, PUB_ILU_ERR);
   const int herr = *err;
   if (!herr) return;
   *err = 0;
@@ -528,7 +528,7 @@ void ilu_check(nsx_handle *h) {
 // f32: write the off-diagonal entries into the FLOAT solve stream (pk_val32) instead of the double one -- only where the solve will
 // read the lane-owner stream (ilu_lanes_stream, the predicate ilu_solve uses); lu itself always holds the double factors
 void ilu_factor(nsx_handle *h, const DevCsr &g, IluSchedule &s, const double *vals, double *lu, const char *name, bool f32) {
-  int *err = (int *)(h->pub_dev + N_SLOTS + 3);
+  int *err = pub_word_dev(h, PUB_ILU_ERR);
   float *pk32 = nullptr;
   if (f32 && ilu_lanes_stream(s, s.stream_ncomp)) {
     if (s.pk_val32.n != s.pk_val.n || !s.pk_val32.p) {  // (released whenever the schedule is rebuilt: unused slots must read 0)
@@ -835,7 +835,7 @@ static void launch_lanes(nsx_handle *h, const IluSchedule &s, const double *b, d
   const size_t shm = (size_t)(s.max_wave_rows + 64) * NCOMP * sizeof(double);
   const int pf = ilu_lanes_pf();  // read per launch, like NSX_ILU_LDS_GUARD_TEST below (the fused launch of nsx_mgs.hip asks the same function)
   s.path.solve_pf = pf;
-  int *err = (int *)(h->pub_dev + N_SLOTS + 3);  // the mapped word ilu_check() reads
+  int *err = pub_word_dev(h, PUB_ILU_ERR);  // the mapped word ilu_check() reads
   const int force_guard = env_int("NSX_ILU_LDS_GUARD_TEST", 0);  // fault injection (tests), read per launch
   const bool known = with_int<1, 2, 3, 4>(s.stream_epl, [&](auto E_) {
     with_int<4, 8>(pf, [&](auto PF_) {

@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -243,6 +244,25 @@ struct SpmvBlocked {
   double frac_if = 0;
 };
 
+// Mailboxes of a persistent grid: two regions used alternately by successive launches (a launch empties the other region for its
+// successor), then tail words that start as 0 (commit / error words).  The host half of nsx_grid.hpp works on it.
+struct GridBox {
+  DevBuf<unsigned long long> buf;
+  size_t region = 0, n_tail = 0;
+  int parity = 0;  // region of the next launch
+  bool allocated() const { return buf.p != nullptr; }
+  void alloc(size_t region_words, size_t tail_words) { buf.alloc(2 * (region = region_words) + (n_tail = tail_words)); }
+  void clear(hipStream_t s) {  // both regions empty (GX_EMPTY is all ones), the tail zero: a new handle's state
+    HIP_CHECK(hipMemsetAsync(buf.p, 0xff, 2 * region * sizeof(unsigned long long), s));
+    HIP_CHECK(hipMemsetAsync(tail(), 0, n_tail * sizeof(unsigned long long), s));
+  }
+  unsigned long long *cur() const { return buf.p + (size_t)parity * region; }
+  unsigned long long *other() const { return buf.p + (size_t)(1 - parity) * region; }
+  unsigned long long *tail() const { return buf.p + 2 * region; }
+  void flip() { parity ^= 1; }
+  int dirty_words(nsx_handle *h) const;  // diagnostics (nsx_grid.hpp): the stream synchronised, words of cur() that are not empty
+};
+
 // Persistent Schur-complement CG (nsx_cg.hip): negative_S_tilde as slabs of 256 slots per Schur ILU block, 16-bit columns
 // into the block's unique-column list.
 struct CgPlan {
@@ -255,6 +275,26 @@ struct CgPlan {
   int32_t max_block_nnz = 0;
 };
 
+// State of the Schur-complement CG (nsx_cg.hip: k_cg_schur in one persistent launch, k_cgd_* in two launches per iteration), grouped by lifetime.
+struct CgState {
+  // ---- per handle: allocated / read from the environment once (cg_setup), given up after a time-out (cg_schur_persistent)
+  GridBox box;                         // mailbox regions, then the error word
+  int max_wg = 0;                      // resident-grid limit of k_cg_schur<0, false>; 0: the persistent launch is not used
+  int max_wg_res[2] = {0, 0};          // ... of the variants that keep the block inverses in registers (96 / 128 rows)
+  int max_wg_lres[2] = {0, 0};         // ... and of the variants that keep the operator's rows in LDS as well
+  bool disabled = false;
+  DevBuf<double> vec;                  // work vectors of the persistent launch: d (double-buffered), h
+  DevBuf<double> d_vec, d_parts;       // two launches per iteration (cg_schur_fused): g, h, S d, d (double-buffered, with ghosts); partial sums
+  DevBuf<double> d_raw;                // ... per-block partial sums of a rank with more Schur blocks than entries of a partial-sum array (k_cgd_fold)
+  // ---- per schedule set: rebuilt with the ILU schedules (ensure_schedules), and what the ranks agreed for them
+  CgPlan plan;
+  int d_agreed = -1;                   // two-launch Schur CG: -1 not decided for the current schedules and communicator, 0 / 1 the ranks' common answer
+  // ---- last solve: diagnostics for nsx_path_info
+  int last_path = 0;                   // 0 none yet, 1 one launch per operation, 2 one persistent launch, 3 two launches per iteration
+  int last_rpg = 0, last_lres = 0;     // its persistent kernel's rows per lane group (0, 6, 8) and whether the operator sat in LDS ([28], [29]); 0 when it did not run
+  bool resident = false, lds_resident = false, variant_said = false;  // the variant NSX_DEBUG reported last (block inverses in registers, operator in LDS), and whether it has
+};
+
 struct ProfEntry {
   int64_t launches = 0;
   double bytes = 0;  // algorithmic bytes summed over the launches (a scope's size may vary: Gram-Schmidt sweeps)
@@ -265,9 +305,9 @@ struct ProfEntry {
 // State of the modified Gram-Schmidt sweep (nsx_mgs.hip), grouped by lifetime.
 struct MgsState {
   // ---- per handle: allocated / read from the environment once (mgs_setup, mgs_lowsync), given up by mgs_recover after a time-out
-  DevBuf<unsigned long long> box;      // persistent sweep: two mailbox regions used alternately by successive launches, then one commit word per workgroup
-  int parity = 0, max_wg = 0;          // region of the next launch; max_wg = 0: the launch-per-link chain is used
-  int used_wg[2] = {0, 0}, used_steps[2] = {0, 0};  // what the last launch on each region filled
+  GridBox box;                         // persistent sweep: mailbox regions, then one commit word per workgroup
+  int max_wg = 0;                      // 0: the launch-per-link chain is used
+  int used_wg[2] = {0, 0}, used_steps[2] = {0, 0};  // what the last launch on each region filled (the sweep's own clearing protocol)
   int max_wg_e[3] = {0, 0, 0};         // resident-grid limit of the 8 / 10 / 12 (link-by-link variants: 20) entries-per-thread instantiations
   int max_wg_dist[3] = {0, 0, 0};      // resident-grid limits of the distributed instantiations (8 / 10 / 12 entries per thread), room left for the collective
   int dist_cap_reserved[3] = {0, 0, 0};  // grid limits of the distributed sweep's instantiations on the masked compute stream
@@ -283,7 +323,7 @@ struct MgsState {
   unsigned int ext_expected = 0;
   int ext_parity = 0;
   bool redo_ahead = false;             // a sweep fell back to the chain after work depending on its w had been enqueued (read and cleared by the GMRES driver)
-  // ---- per communicator: what the ranks chose together (reset by nsx_comm_init and comm_destroy)
+  // ---- per communicator: what the ranks chose together (krylov_new_communicator / krylov_communicator_gone; dist_fit also krylov_new_schedules)
   int dist_state = -1;                 // -1 not decided yet, 0 two-pass sweep (mgs_lowsync), 1 the collective inside the persistent grid
   std::map<int, int> dist_fit;         // role of the vector in the solve (mgs_role) -> do ALL ranks' resident grids hold their vector of that role (agreed once per role; asked again when the sizes change)
   bool leave_req = false;              // a flag wait of this rank's grid timed out on its own: the next sweep asks all ranks to leave the persistent path
@@ -439,7 +479,50 @@ struct StatsState {
 
 struct Comm;  // RCCL state (nsx_comm.hip)
 
-enum { N_SLOTS = 128 };  // device scalar slots (reduction results)
+// ---- THE table of device scalar slots (h->scal, mirrored in h->scal_host and the first N_SLOTS doubles of h->pub_host), of the mapped
+//      words behind them and of the basis sizes that give the ranges their lengths.  A slot that is not listed here is free.
+enum { N_SLOTS = 128 };                     // device scalar slots (reduction results)
+constexpr int KRYLOV_N_TMP = 30;            // SolverGMRES::AdditionalData::max_n_tmp_vectors: a cycle sweeps against dim <= KRYLOV_N_TMP - 2 vectors
+constexpr int SWEEP_SLOTS = KRYLOV_N_TMP + 1;  // a sweep writes slot0 .. slot0 + dim + 2: h(i), |w|^2 after, |w|^2 before, "the norm was summed explicitly"
+enum Slot {
+  S_POST = 0,              // [S_POST_LEN] BETWEEN solves: the collectives of the post-processing (nsx_diag.hip, nsx_forces.hip) borrow the solvers' per-solve
+                           // scratch below S_H (written before it is read in every solve: nothing is carried from one call to the next)
+  S_DH = 2,                // SolverCG: d.h
+  S_GH = 3, S_GH2 = 5,     // ... g.h of the current / the next iteration (ping-pong)
+  S_RES = 4,               // ... |g|^2: between the two g.h slots, so whichever is current, the pair that travels in one all-reduce is adjacent
+  S_LS_NORM = 7,           // the explicitly summed |w|^2 of the distributed sweep (nsx_mgs.hip)
+  S_H = 8,                 // [SWEEP_SLOTS] SolverGMRES: the sweep's coefficients
+  S_T = 39,                // |b|^2 of a relative tolerance / the scratch of norm2: next to S_NRM, the two travel to the host in one publication (Seams::rtol)
+  S_NRM = 40,              // SolverGMRES: |v|^2 of a cycle's first vector
+  S_H2 = 41,               // [SWEEP_SLOTS] ... the coefficients of a re-orthogonalisation sweep
+  S_CGP = 100,             // [S_CGP_LEN] the Schur CG's publication: steps, last residual, status, tolerance (nsx_cg.hip)
+  S_AGREE = N_SLOTS - 1,   // comm_agree_all: the sum of the ranks' objections
+};
+constexpr int S_CGP_LEN = 4, S_POST_LEN = 8;
+static_assert(S_POST + S_POST_LEN <= S_H, "the post-processing borrows scratch slots only");
+// (the test hook nsx_gram_schmidt_sweeps sweeps against up to KRYLOV_N_TMP - 1 vectors from S_H: its longest sweep ends ON S_T, which
+// holds nothing while the hook runs)
+constexpr int SLOT_RANGES[][2] = {{S_DH, 1}, {S_GH, 1}, {S_RES, 1}, {S_GH2, 1}, {S_LS_NORM, 1}, {S_H, SWEEP_SLOTS}, {S_T, 1}, {S_NRM, 1}, {S_H2, SWEEP_SLOTS},
+                                  {S_CGP, S_CGP_LEN}, {S_AGREE, 1}};
+constexpr bool slot_ranges_ok() {  // listed in ascending order, each ending where the next begins at the latest: pairwise disjoint and below N_SLOTS
+  int end = 0;
+  for (const auto &r : SLOT_RANGES) {
+    if (r[0] < end || r[1] < 1) return false;
+    end = r[0] + r[1];
+  }
+  return end <= N_SLOTS;
+}
+static_assert(slot_ranges_ok(), "scalar slot ranges overlap or leave the table");
+static_assert(S_NRM == S_T + 1, "|b|^2 and the first residual norm are one publication");
+static_assert(S_GH < S_RES && S_RES < S_GH2 && S_GH2 - S_GH == 2, "S_RES sits between the two g.h slots");
+// Mapped host words behind the slots (h->pub_host / h->pub_dev + N_SLOTS, 8 bytes each): written by kernels, read by the host without a copy
+enum PubWord {
+  PUB_FLAG = 0,        // sequence number of the last publication (wait_published)
+  PUB_MGS_ERR = 2,     // raised by a Gram-Schmidt grid that gives up
+  PUB_ILU_ERR = 3,     // raised by an ILU(0) kernel / the float conversion of F (ilu_check)
+  PUB_SCHUR_SAME = 4,  // raised when the Schur product's weights differ from the last initialisation's
+  PUB_WORDS = 8
+};
 
 }  // namespace nsx
 
@@ -519,7 +602,7 @@ struct nsx_handle {
   double *scal_host = nullptr;              // pinned mirror
   // host-visible publication of scalars without a memcpy + stream sync: the publishing kernel writes the values and then
   // a sequence number into fine-grained mapped host memory, the host polls the sequence number
-  double *pub_host = nullptr, *pub_dev = nullptr;  // [N_SLOTS] values, then the flag word
+  double *pub_host = nullptr, *pub_dev = nullptr;  // [N_SLOTS] values, then the PUB_WORDS mapped words (pub_word_host / pub_word_dev)
   unsigned long long pub_seq = 0;
   nsx::DevBuf<unsigned int> pub_counter;
   nsx::MgsState mgs;        // the modified Gram-Schmidt sweep of the GMRES drivers (nsx_mgs.hip)
@@ -528,7 +611,6 @@ struct nsx_handle {
   int n_persistent_fallbacks = 0;      // persistent kernels that timed out on this handle (nsx_solve_stats::persistent_fallbacks)
   int gmres_depth = 0;                 // GMRES nesting level of the running solve (one Gram matrix of mgs.ls_gram per level)
   bool cu_reserve_failed = false;    // the ranks tried to mask their streams and one of them could not: all are back on plain streams, nobody asks again
-  int cgd_agreed = -1;               // two-launch Schur CG: -1 not decided for the current schedules, 0 / 1 the ranks' common answer
   nsx::DevBuf<double> ext_self;           // development (NSX_EXT_SELF_P2P): operands of the self-addressed send / receive in front of the sweep's collective
   hipStream_t stream_plain = nullptr;  // the compute stream of the handle's creation once `stream` has been replaced by one with a CU mask (comm_reserve_cus)
   std::vector<hipStream_t> retired_streams;  // streams RCCL has launched on and the handle no longer uses: destroyed behind ncclCommDestroy (comm_destroy)
@@ -537,20 +619,7 @@ struct nsx_handle {
   long long n_allreduce = 0, n_halo = 0;  // collectives issued (nsx_comm_counters)
   int self_p2p = 0;                       // development (NSX_EXT_SELF_P2P, read by nsx_comm_init): self-addressed send / receive pairs in front of collectives
   int n_ext_collectives = 0;              // collectives inside a persistent grid so far (fault injection: NSX_EXT_LATE_RELEASE)
-  // persistent Schur-complement CG (nsx_cg.hip: k_cg_schur): mailbox regions, work vectors (d double-buffered, h)
-  nsx::DevBuf<unsigned long long> cg_box;
-  nsx::CgPlan cgplan;
-  nsx::DevBuf<double> cg_vec;
-  int cg_parity = 0, cg_max_wg = 0, cg_max_wg_res[2] = {0, 0};  // _res: resident-grid limits of the variants that keep the block inverses in registers (96 / 128 rows)
-  int cg_max_wg_lres[2] = {0, 0};                      // ... and of the variants that keep the operator's rows in LDS as well
-  bool cg_resident = false;                            // the last Schur CG ran with the block inverses in registers
-  bool cg_lds_resident = false;                        // ... and with the operator in LDS
-  bool cg_variant_said = false;
-  bool cg_disabled = false;
-  nsx::DevBuf<double> cgd_raw;              // ... per-block partial sums of a rank with more Schur blocks than entries of a partial-sum array (k_cgd_fold)
-  int cg_last_path = 0;                     // the last Schur CG: 0 none yet, 1 one launch per operation, 2 one persistent launch, 3 two launches per iteration
-  int cg_last_rpg = 0, cg_last_lres = 0;    // ... its persistent kernel's rows per lane group (0, 6, 8) and whether the operator sat in LDS (nsx_path_info [28], [29]); 0 when it did not run
-  nsx::DevBuf<double> cgd_vec, cgd_parts;   // distributed Schur CG in two launches per iteration (cg_schur_fused): g, h, S d, d (double-buffered, with ghosts); partial sums
+  nsx::CgState cg;          // the CG on the Schur complement (nsx_cg.hip)
   // ---- post-processing: one state block per feature (above)
   int layout_epoch = 0;     // counts the installations of a mesh / an internal layout: what is kept in the INTERNAL node numbering is rebuilt when it moves
   nsx::ForceState ff;       // nsx_forces.hip
@@ -595,6 +664,39 @@ struct LaunchScope {
 };
 
 inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+
+// The mapped word W (PubWord) as the host reads it and as a kernel writes it
+template <class T = int>
+inline volatile T *pub_word_host(nsx_handle *h, int W) { return (volatile T *)(h->pub_host + N_SLOTS + W); }
+template <class T = int>
+inline T *pub_word_dev(nsx_handle *h, int W) { return (T *)(h->pub_dev + N_SLOTS + W); }
+
+// ---- one reset per lifetime of what the Krylov drivers' state blocks (MgsState, CgState) keep beyond a solve.  Each resets what its call
+//      sites always reset, no more: a wider reset makes a later solve ask the ranks again, i.e. changes the collectives it issues.
+// comm_destroy (also in front of every new communicator).  dist_state / dist_fit / d_agreed are NOT touched here: a handle whose communicator
+// went keeps them until the next one arrives (below).  What a timed-out sweep gave up (mgs_recover: mgs.disabled, the grid limits) stays given
+// up for the handle, whatever communicator follows.
+inline void krylov_communicator_gone(nsx_handle *h) {
+  h->cu_reserve_failed = h->mgs.leave_req = false;
+  h->mgs.local_timeouts = 0;
+}
+// nsx_comm_init, nsx_comm_init_callbacks (behind comm_destroy): the paths the ranks choose together are chosen again
+inline void krylov_new_communicator(nsx_handle *h) {
+  h->mgs.dist_state = h->cg.d_agreed = -1;
+  h->mgs.dist_fit.clear();
+}
+// refresh_rank_products: sizes may have changed, what the ranks agreed on for the old ones is asked again (every rank gets here alike).
+// The Schur CG's answer follows the schedules, which are rebuilt later (ensure_schedules, with the next initialisation): two functions.
+inline void krylov_new_rank_tables(nsx_handle *h) { h->mgs.dist_fit.clear(); }
+inline void krylov_new_schedules(nsx_handle *h) { h->cg.d_agreed = -1; }
+
+struct SolveResult {
+  int status, steps;  // status: 0 success, 1 failure
+  double last;
+};
+inline int sc_check(int step, double value, double tol, int maxsteps) {  // SolverControl::check: 0 iterate, 1 success, 2 failure
+  return value <= tol ? 1 : (step >= maxsteps || std::isnan(value)) ? 2 : 0;
+}
 
 // ---- environment knobs (NSX_*): THE readers.  A reader reads when it is called, so the call site decides how long a value holds: per
 //      call (what the tests switch inside one process: the ILU, Schur CG and step variants, NSX_PF, NSX_SCHUR_CACHE), once per process (the
@@ -741,7 +843,7 @@ bool v_mgs(nsx_handle *h, Span n, double *w, int dim, double *const *vs, int slo
 // consider: also out[dim+1] = |w|^2 BEFORE the sweep (SolverGMRES' re-orthogonalisation test); a single-launch sweep then
 // normalises w only if the test does not ask for a second sweep.
 void v_axpy_multi(nsx_handle *h, Span n, double *x, int k, double *const *vs, const double *coef_host);
-// x = x0 + sum (x0 == nullptr: x = sum, then optionally x = -y + x) in one launch that only writes x; k <= 32
+// x = x0 + sum (x0 == nullptr: x = sum, then optionally x = -y + x) in one launch that only writes x; k <= one launch's worth (MultiArgs: KRYLOV_N_TMP + 2)
 void v_axpy_multi_into(nsx_handle *h, Span n, double *x, const double *x0, const double *y, int k, double *const *vs, const double *coef_host);
 void finalize_slots(nsx_handle *h, int slot0, int count);
 // for kernels that leave nb <= 512 per-workgroup partial sums of a scalar themselves: where to put them, and the
@@ -781,8 +883,10 @@ MgsPick mgs_pick(int n, const int *caps, int n_inst, const int *es);
 // persistent CG on the Schur complement (nsx_cg.hip); false: not applicable here, use the launch-per-operation solver
 void build_cg_plan(nsx_handle *h);   // with the ILU schedules
 void cg_pack_values(nsx_handle *h);  // after every schur_numeric
-bool cg_schur_persistent(nsx_handle *h, double *x, const double *b, double rtol, int maxiter, int *steps, double *last, int *status);
-bool cg_schur_fused(nsx_handle *h, double *x, const double *b, double rtol, int maxiter, int *steps, double *last, int *status);  // distributed runs: two launches per iteration
+// the bool: this path ran and filled res
+bool cg_schur_persistent(nsx_handle *h, double *x, const double *b, double rtol, int maxiter, SolveResult &res);
+bool cg_schur_fused(nsx_handle *h, double *x, const double *b, double rtol, int maxiter, SolveResult &res);  // distributed runs: two launches per iteration
+int cg_dirty_words(nsx_handle *h);   // diagnostics: non-empty words of the mailbox region the next persistent solve would use
 void write_scalar(nsx_handle *h, int slot, double v);
 
 // solver (nsx_solve.hip)

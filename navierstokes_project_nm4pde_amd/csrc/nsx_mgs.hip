@@ -20,7 +20,8 @@ namespace nsx {
 // timing.  Every wait is bounded by a wall-clock timeout: a grid that is not co-resident (another stream or process holds
 // compute units) ends without touching w, and the host falls back to the launch-per-link chain (v_mgs).
 constexpr int MGS_MAX_WG = 512;
-constexpr int MGS_STEPS = 32;     // >= max_n_tmp_vectors + 1
+constexpr int MGS_STEPS = 32;     // mailbox rows / basis pointers of one sweep
+static_assert(MGS_STEPS >= KRYLOV_N_TMP + 2, "a sweep against dim vectors needs dim + 2 rows");
 constexpr size_t MGS_REGION = (size_t)MGS_STEPS * MGS_MAX_WG + MGS_STEPS;  // words per mailbox region (+ the totals)
 // after the two mailbox regions: one word per workgroup = sequence number of the last sweep whose part of w it wrote back
 // (distinct addresses: a shared counter would serialise 512 atomics at the end of every sweep)
@@ -1163,27 +1164,28 @@ static const void *mgs_fn(int m, int e) {
   }
 }
 
-static volatile int *mgs_err_word(nsx_handle *h) { return (volatile int *)(h->pub_host + N_SLOTS + 2); }  // mapped host word: raised by a grid that gives up
-
-// Both mailbox regions empty, the commit words behind them zero, the error word clear, nothing remembered about what the regions hold: a new handle's state
-static void mgs_clear_boxes(nsx_handle *h) {
+// The error word clear, nothing remembered about what the regions hold: what goes with emptied mailboxes
+static void mgs_boxes_cleared(nsx_handle *h) {
   MgsState &m = h->mgs;
-  HIP_CHECK(hipMemsetAsync(m.box.p, 0xff, 2 * MGS_BOX_REGION * sizeof(unsigned long long), h->stream));
-  HIP_CHECK(hipMemsetAsync(m.box.p + 2 * MGS_BOX_REGION, 0, MGS_TAIL * sizeof(unsigned long long), h->stream));
-  *mgs_err_word(h) = 0;
+  *pub_word_host(h, PUB_MGS_ERR) = 0;
   m.used_wg[0] = m.used_wg[1] = m.used_steps[0] = m.used_steps[1] = 0;
+}
+// Both mailbox regions empty, the commit words behind them zero, and the above: a new handle's state
+static void mgs_clear_boxes(nsx_handle *h) {
+  h->mgs.box.clear(h->stream);
+  mgs_boxes_cleared(h);
 }
 // workgroups that had written their part of w back in sweep `seq` (the streams are idle)
 static unsigned int mgs_committed(nsx_handle *h, unsigned long long seq) {
   std::vector<unsigned long long> tail(MGS_TAIL, 0);
-  HIP_CHECK(hipMemcpy(tail.data(), h->mgs.box.p + 2 * MGS_BOX_REGION, MGS_TAIL * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  HIP_CHECK(hipMemcpy(tail.data(), h->mgs.box.tail(), MGS_TAIL * sizeof(unsigned long long), hipMemcpyDeviceToHost));
   unsigned int committed = 0;
   for (unsigned long long v : tail) committed += v == seq;
   return committed;
 }
 
 void mgs_setup(nsx_handle *h) {
-  if (h->mgs.box.p || h->mgs.disabled) return;
+  if (h->mgs.box.allocated() || h->mgs.disabled) return;
   h->mgs.max_wg = 0;
   if (!env_on("NSX_MGS")) {
     h->mgs.disabled = true;
@@ -1191,30 +1193,26 @@ void mgs_setup(nsx_handle *h) {
   }
   // links per exchange: 0 = all of them (k_mgs_one, the default), 1 = deal.II's chain link by link (k_mgs), 2..5 = k_mgs_blk
   h->mgs.links = std::max(0, std::min(5, env_int("NSX_MGS_LINKS", 0)));
-  int cus = 0;
-  HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->prm.device));
-  h->mgs.box.alloc(2 * MGS_BOX_REGION + MGS_TAIL);
+  h->mgs.box.alloc(MGS_BOX_REGION, MGS_TAIL);
   mgs_clear_boxes(h);
   const int es[3] = {8, 10, h->mgs.links == 0 ? 12 : 20};
   // NSX_MGS_MAXWG caps every grid limit (tests: a small mesh then needs the instantiations a large one does)
   auto capped = [](int limit) { return env_set("NSX_MGS_MAXWG") ? std::max(1, mgs_maxwg_cap(limit)) : limit; };
   for (int k = 0; k < 3; ++k) {
-    int per_cu = 0;
-    HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, mgs_fn(h->mgs.links, es[k]), 256, 0));
-    h->mgs.max_wg_e[k] = capped(std::min(MGS_MAX_WG, per_cu * cus));
-    if (nsx_debug()) fprintf(stderr, "[nsx] mgs sweep (%d links per exchange, %d entries per thread): %d CUs x %d resident workgroups\n", h->mgs.links, es[k], cus, per_cu);
+    const ResidentGrid g = resident_grid(h, mgs_fn(h->mgs.links, es[k]), 256);
+    h->mgs.max_wg_e[k] = capped(std::min(MGS_MAX_WG, g.slots()));
+    if (nsx_debug()) fprintf(stderr, "[nsx] mgs sweep (%d links per exchange, %d entries per thread): %d CUs x %d resident workgroups\n", h->mgs.links, es[k], g.cus, g.per_cu);
   }
   h->mgs.max_wg = h->mgs.max_wg_e[1];
   // distributed instantiations: the collective's own kernels (RCCL's all-reduce, the two one-thread kernels around it) must find a
   // place on the device WHILE the grid is resident and waiting for them: an eighth of the slots (at least 32) stays free
   const int es_one[3] = {8, 10, 12};
   for (int k = 0; k < 3; ++k) {
-    int per_cu = 0;
-    HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, mgs_one_fn(es_one[k], true), 256, 0));
-    const int slots = per_cu * cus;
+    const ResidentGrid g = resident_grid(h, mgs_one_fn(es_one[k], true), 256);
+    const int slots = g.slots();
     h->mgs.max_wg_dist[k] = capped(std::max(0, std::min(MGS_MAX_WG, slots - std::max(32, slots / 8))));
     // on a compute stream that leaves one CU per XCD to the collective's kernel: every shader engine counts as the one that lost a CU
-    h->mgs.dist_cap_reserved[k] = capped(std::max(0, std::min(MGS_MAX_WG, per_cu * (cus - 32))));
+    h->mgs.dist_cap_reserved[k] = capped(std::max(0, std::min(MGS_MAX_WG, g.per_cu * (g.cus - 32))));
   }
   h->mgs.ext_vals.alloc(2 * MGS_EXT_VALS);
   h->mgs.ext_vals.zero(h->stream);
@@ -1227,21 +1225,21 @@ void mgs_setup(nsx_handle *h) {
 // stragglers, empty the mailboxes, clear the error words and use the launch-per-link chain from now on.  Returns how many
 // workgroups had already written their part of w (0: w is untouched and the sweep can simply be redone by the chain).
 static unsigned int mgs_recover(nsx_handle *h, unsigned long long failed_seq) {
-  HIP_CHECK(hipStreamSynchronize(h->stream));
-  if (h->comm_stream) HIP_CHECK(hipStreamSynchronize(h->comm_stream));
-  if (h->mgs.ext_vals.p) {
-    h->mgs.ext_vals.zero(h->stream);
-    h->mgs.ext_words.zero(h->stream);
-    h->mgs.ext_expected = 0;
-  }
-  h->mgs.max_wg_dist[0] = h->mgs.max_wg_dist[1] = h->mgs.max_wg_dist[2] = 0;
-  h->mgs.dist_fit.clear();
-  const unsigned int committed = mgs_committed(h, failed_seq);
-  mgs_clear_boxes(h);
-  h->mgs.max_wg = h->mgs.max_wg_e[0] = h->mgs.max_wg_e[1] = h->mgs.max_wg_e[2] = 0;
-  h->mgs.disabled = true;
-  h->n_persistent_fallbacks++;
-  fprintf(stderr, "[nsx] warning: the persistent Gram-Schmidt sweep timed out (grid not co-resident): this handle uses one launch per link from now on\n");
+  MgsState &m = h->mgs;
+  unsigned int committed = 0;
+  grid_gave_up(h, m.box, true, "Gram-Schmidt sweep", "link", [&] {
+    if (m.ext_vals.p) {
+      m.ext_vals.zero(h->stream);
+      m.ext_words.zero(h->stream);
+      m.ext_expected = 0;
+    }
+    m.max_wg_dist[0] = m.max_wg_dist[1] = m.max_wg_dist[2] = 0;
+    m.dist_fit.clear();
+    committed = mgs_committed(h, failed_seq);
+    mgs_boxes_cleared(h);
+    m.max_wg = m.max_wg_e[0] = m.max_wg_e[1] = m.max_wg_e[2] = 0;
+    m.disabled = true;
+  });
   return committed;
 }
 
@@ -1265,8 +1263,7 @@ static void mgs_chain(nsx_handle *h, Span sp, double *w, int dim, double *const 
 constexpr int LS_C = 8;       // basis vectors per pass of the dot kernel
 constexpr int LS_VALS = 64;   // r_j at j, Gram row at 32 + i, |w|^2 before the sweep at 63
 constexpr int LS_BLOCKS = 2048;  // most workgroups of the dot kernel (partial sums per value)
-constexpr int N_TMP_MAX = 32;
-enum { S_LS_NORM = 7 };          // scalar slot of the explicit |w|^2 of the distributed sweep (free in nsx_solve.hip's table)
+constexpr int N_TMP_MAX = KRYLOV_N_TMP + 2;
 
 __global__ __launch_bounds__(256) void k_ls_dots(int n, int split, int gap, const double *__restrict__ w, MgsArgs V, int dim, double *__restrict__ partial) {
   __shared__ double sh[4][2 * LS_C + 1];
@@ -1480,7 +1477,7 @@ static int ilu_mgs_entries(nsx_handle *h, Span sp, int dim, const double *gram) 
   // The default therefore stays with the separate kernels and rounds 3-4's history.
   const bool wanted = ilu_mgs_wanted();
   const IluSchedule &s = h->schedF;
-  if (!wanted || h->comm || h->mgs.disabled || !h->mgs.box.p || h->mgs.links != 0 || !gram || dim + 2 > MGS_STEPS) return 0;
+  if (!wanted || h->comm || h->mgs.disabled || !h->mgs.box.allocated() || h->mgs.links != 0 || !gram || dim + 2 > MGS_STEPS) return 0;
   if (sp.n != h->n_u || sp.split != sp.n || sp.gap != 0 || (h->dim != 2 && h->dim != 3)) return 0;
   if (!s.packed_ok || s.levelled || s.stream_ncomp != h->dim || s.stream_epl != 2 || s.n_waves < 1 || s.n_waves > MGS_MAX_WG) return 0;
   if (ilu_lanes_pf() != 8) return 0;  // (the fused kernel keeps 8 slabs in flight)
@@ -1491,14 +1488,11 @@ static int ilu_mgs_entries(nsx_handle *h, Span sp, int dim, const double *gram) 
   if (h->mgs.ilu_cap[k] < 0 || h->mgs.ilu_cap_rows != s.max_wave_rows) {  // resident-grid limit with this schedule's LDS request
     if (h->mgs.ilu_cap_rows != s.max_wave_rows) h->mgs.ilu_cap[0] = h->mgs.ilu_cap[1] = h->mgs.ilu_cap[2] = -1;
     h->mgs.ilu_cap_rows = s.max_wave_rows;
-    int cus = 0, per_cu = 0;
-    HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->prm.device));
     const size_t shm = ilu_mgs_lds_doubles((s.max_wave_rows + 64) * h->dim, e) * sizeof(double);
     if (shm > 80 * 1024) h->mgs.ilu_cap[k] = 0;
     else {
       if (shm > 64 * 1024) HIP_CHECK(hipFuncSetAttribute(ilu_mgs_fn(h->dim, e), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));  // (160 KB per CU on gfx950; the runtime's default limit per workgroup is 64 KB)
-      HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, ilu_mgs_fn(h->dim, e), 256, shm));
-      h->mgs.ilu_cap[k] = mgs_maxwg_cap(std::min(MGS_MAX_WG, per_cu * cus));
+      h->mgs.ilu_cap[k] = mgs_maxwg_cap(std::min(MGS_MAX_WG, resident_grid(h, ilu_mgs_fn(h->dim, e), 256, shm).slots()));
     }
     if (nsx_debug())
       fprintf(stderr, "[nsx] triangular solves + sweep in one launch (%d entries per thread, %zu B of LDS): %d resident workgroups for %d waves of the solve\n", e, shm,
@@ -1599,7 +1593,7 @@ static MgsPlan mgs_plan(nsx_handle *h, Span sp, int dim, const double *gram, int
 // one launch + all-reduce per link, as the reference's MPI run does.  Without a Gram cache (or too many vectors for it) the chain as well.
 static void mgs_fallback(nsx_handle *h, Span sp, double *w, int dim, double *const *vs, int slot0, double *out, bool consider, double *gram, bool two_pass) {
   if (h->mgs.ls_mode < 0) h->mgs.ls_mode = env_int("NSX_MGS_LOWSYNC", 2);  // read once per handle: 0 chain, 1 two collectives, 2 one
-  if (two_pass && h->mgs.ls_mode && gram && dim <= 31) mgs_lowsync(h, sp, w, dim, vs, slot0, out, consider, gram);
+  if (two_pass && h->mgs.ls_mode && gram && dim <= KRYLOV_N_TMP + 1) mgs_lowsync(h, sp, w, dim, vs, slot0, out, consider, gram);
   else mgs_chain(h, sp, w, dim, vs, slot0, out, consider);
 }
 
@@ -1650,12 +1644,13 @@ static double *mgs_launch(nsx_handle *h, const MgsPlan &p, Span sp, double *w, i
   MgsArgs V;
   for (int i = 0; i < MGS_STEPS; ++i) V.v[i] = i < dim ? vs[i] : nullptr;
   int n_ = n, split = sp.split, gap = sp.gap, dim_ = dim, norm_ = normalize ? 1 : 0, consider_ = consider ? 1 : 0;
-  unsigned long long *box = m.box.p + (size_t)m.parity * MGS_BOX_REGION, *box_next = m.box.p + (size_t)(1 - m.parity) * MGS_BOX_REGION;
+  const int parity = m.box.parity;
+  unsigned long long *box = m.box.cur(), *box_next = m.box.other();
   double *sout = h->scal.p + slot0, *pub_vals = h->pub_dev + slot0;
-  unsigned long long *pub_flag = (unsigned long long *)(h->pub_dev + N_SLOTS), seq_ = seq;
-  int *err = (int *)(h->pub_dev + N_SLOTS + 2);  // mapped host word
-  unsigned long long *tail = m.box.p + 2 * MGS_BOX_REGION;
-  int reset_wg = m.used_wg[1 - m.parity], reset_steps = m.used_steps[1 - m.parity], reset_words = reset_wg * reset_steps;
+  unsigned long long *pub_flag = pub_word_dev<unsigned long long>(h, PUB_FLAG), seq_ = seq;
+  int *err = pub_word_dev(h, PUB_MGS_ERR);  // mapped host word
+  unsigned long long *tail = m.box.tail();
+  int reset_wg = m.used_wg[1 - parity], reset_steps = m.used_steps[1 - parity], reset_words = reset_wg * reset_steps;
   int drop_wg = h->gx_drop_wg;
   double *gram_ = gram, guard_ = mgs_norm_guard(h);
   double *ext_vals_this = nullptr;
@@ -1710,10 +1705,10 @@ static double *mgs_launch(nsx_handle *h, const MgsPlan &p, Span sp, double *w, i
     HIP_CHECK(hipLaunchKernel(fn, dim3(nwg), dim3(256), args, 0, h->stream));
     used_steps = (cdiv(dim, M) + 1) * (M + M * (M - 1) / 2 + 1) * nwg;
   }
-  m.used_wg[m.parity] = used_wg;
-  m.used_steps[m.parity] = used_steps;
-  m.used_wg[1 - m.parity] = m.used_steps[1 - m.parity] = 0;
-  m.parity ^= 1;
+  m.used_wg[parity] = used_wg;
+  m.used_steps[parity] = used_steps;
+  m.used_wg[1 - parity] = m.used_steps[1 - parity] = 0;
+  m.box.flip();
   for (int i = 0; i <= dim + 1; ++i) h->slot_nb[slot0 + i] = 0;
   return ext_vals_this;
 }
@@ -1790,7 +1785,7 @@ bool v_mgs(nsx_handle *h, Span sp, double *w, int dim, double *const *vs, int sl
   const bool ran_ahead = normalize && !consider && after_launch;
   if (ran_ahead) (*after_launch)();
   wait_published(h, seq);
-  if (*mgs_err_word(h)) {  // the grid gave up (a bounded wait ran out) and left w as it was
+  if (*pub_word_host(h, PUB_MGS_ERR)) {  // the grid gave up (a bounded wait ran out) and left w as it was
     if (!(p.dist && mgs_finish_late(h, sp, w, dim, vs, slot0, out, consider, gram, ext_vals, seq))) {
       const unsigned int committed = mgs_recover(h, seq);
       if (committed != 0) NSX_THROW(NSX_ERR_HIP, "Gram-Schmidt sweep: %u workgroups had written w when another one timed out", committed);
@@ -1829,15 +1824,7 @@ bool v_mgs(nsx_handle *h, Span sp, double *w, int dim, double *const *vs, int sl
 
 // diagnostics (nsx_persistent_state): words of the region the next sweep would use that are not empty.  A healthy handle keeps
 // that region empty (every launch clears the other region for its successor); after a time-out mgs_recover clears both.
-int mgs_dirty_words(nsx_handle *h) {
-  if (!h->mgs.box.p) return 0;
-  std::vector<unsigned long long> w(MGS_BOX_REGION);
-  HIP_CHECK(hipStreamSynchronize(h->stream));
-  HIP_CHECK(hipMemcpy(w.data(), h->mgs.box.p + (size_t)h->mgs.parity * MGS_BOX_REGION, MGS_BOX_REGION * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-  int dirty = 0;
-  for (unsigned long long v : w) dirty += v != GX_EMPTY;
-  return dirty;
-}
+int mgs_dirty_words(nsx_handle *h) { return h->mgs.box.dirty_words(h); }
 
 }  // namespace nsx
 
@@ -1846,9 +1833,9 @@ int mgs_dirty_words(nsx_handle *h) {
 // normalised.  norm_guard >= 0 replaces the threshold below which the Gram formula for |w'|^2 is refused (0: always the formula,
 // 1e300: always the explicitly summed norm); < 0 keeps the handle's.  For the tests of that formula (tests/test_gpu_errors.py).
 extern "C" int nsx_gram_schmidt_cycle(nsx_handle *h, int n, int m, double *vectors, double norm_guard, double *coeffs, double *norms2) {
-  if (m < 1 || m > 30) return NSX_ERR_ARG;
-  double before[32];
-  int normalized[32];
+  if (m < 1 || m > nsx::KRYLOV_N_TMP) return NSX_ERR_ARG;
+  double before[nsx::KRYLOV_N_TMP + 2];
+  int normalized[nsx::KRYLOV_N_TMP + 2];
   return nsx_gram_schmidt_sweeps(h, n, n, 0, m, vectors, norm_guard, 0, coeffs, norms2, before, normalized);  // Span(n), consider = false, normalize = true
 }
 
@@ -1860,7 +1847,7 @@ extern "C" int nsx_gram_schmidt_cycle(nsx_handle *h, int n, int m, double *vecto
 // sweeps.  For tests/test_gpu_mgs_sweep.py.
 extern "C" int nsx_gram_schmidt_sweeps(nsx_handle *h, int n, int split, int gap, int m, double *vectors, double norm_guard, int flags, double *coeffs,
                                        double *norms2, double *norms2_before, int *normalized) {
-  if (!h || !vectors || !coeffs || !norms2 || !norms2_before || !normalized || n < 1 || m < 1 || m > 30 || split < 0 || split > n || gap < 0 ||
+  if (!h || !vectors || !coeffs || !norms2 || !norms2_before || !normalized || n < 1 || m < 1 || m > nsx::KRYLOV_N_TMP || split < 0 || split > n || gap < 0 ||
       (flags & ~3) != 0 || (split == n && gap != 0))
     return NSX_ERR_ARG;
   NSX_TRY(h)
@@ -1877,14 +1864,14 @@ extern "C" int nsx_gram_schmidt_sweeps(nsx_handle *h, int n, int split, int gap,
   h->mgs.guard_override = norm_guard;
   try {
     const nsx::Span sp(n, split, gap);
-    nsx::v_dot(h, sp, v[0].p, v[0].p, 40);
-    norms2[0] = norms2_before[0] = nsx::read_scalar(h, 40);
+    nsx::v_dot(h, sp, v[0].p, v[0].p, nsx::S_NRM);
+    norms2[0] = norms2_before[0] = nsx::read_scalar(h, nsx::S_NRM);
     normalized[0] = 0;
     nsx::v_scale(h, sp, v[0].p, 1.0 / std::sqrt(norms2[0]));
     for (int k = 1; k < m; ++k) {
-      double *vs[32], out[34];
+      double *vs[nsx::KRYLOV_N_TMP + 2], out[nsx::KRYLOV_N_TMP + 4];
       for (int i = 0; i < k; ++i) vs[i] = v[i].p;
-      const bool done = nsx::v_mgs(h, sp, v[k].p, k, vs, 8, normalize, out, nullptr, consider, h->mgs.ls_gram.p);
+      const bool done = nsx::v_mgs(h, sp, v[k].p, k, vs, nsx::S_H, normalize, out, nullptr, consider, h->mgs.ls_gram.p);
       for (int i = 0; i < k; ++i) coeffs[(size_t)k * m + i] = out[i];
       norms2[k] = out[k];
       norms2_before[k] = consider ? out[k + 1] : 0.0;

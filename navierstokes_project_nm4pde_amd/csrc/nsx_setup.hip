@@ -444,7 +444,7 @@ static void refresh_rank_products(nsx_handle *h) {
   h->sched_dirty = true;
   h->prec_ready = false;
   h->schur_valid = false;  // the Schur ILU blocks follow the tables
-  h->mgs.dist_fit.clear();  // sizes may have changed: what the ranks agreed on for the old ones is asked again (every rank gets here alike)
+  krylov_new_rank_tables(h);
 }
 
 void ensure_schedules(nsx_handle *h) {
@@ -460,7 +460,7 @@ void ensure_schedules(nsx_handle *h) {
   const bool denseS = env_on("NSX_DENSE_S");
   setup_ilu_schedule(h, h->gS.host, sb, h->schedS, bpwS, denseS, 1);
   build_cg_plan(h);
-  h->cgd_agreed = -1;  // path choices that the ranks make together are made again for the new schedules
+  krylov_new_schedules(h);  // path choices that the ranks make together are made again for the new schedules
   h->sched_dirty = false;
 }
 
@@ -618,8 +618,8 @@ int nsx_create(const nsx_params *p, nsx_handle **out) {
     h->scal.zero(h->stream);
     h->red_partial.alloc((size_t)N_SLOTS * 1024);
     HIP_CHECK(hipHostMalloc((void **)&h->scal_host, N_SLOTS * sizeof(double), hipHostMallocDefault));
-    HIP_CHECK(hipHostMalloc((void **)&h->pub_host, (N_SLOTS + 8) * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));
-    memset(h->pub_host, 0, (N_SLOTS + 8) * sizeof(double));
+    HIP_CHECK(hipHostMalloc((void **)&h->pub_host, (N_SLOTS + PUB_WORDS) * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));
+    memset(h->pub_host, 0, (N_SLOTS + PUB_WORDS) * sizeof(double));
     HIP_CHECK(hipHostGetDevicePointer((void **)&h->pub_dev, h->pub_host, 0));
     h->pub_counter.alloc(1);
     h->pub_counter.zero(h->stream);

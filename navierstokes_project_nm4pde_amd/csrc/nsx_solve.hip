@@ -47,12 +47,6 @@ struct Tmp {
 
 using Op = std::function<void(double *dst, const double *src)>;
 
-struct SolveResult {
-  int status;  // 0 success, 1 failure
-  int steps;
-  double last;
-};
-
 // Distributed runs: hold back the all-reduces of finished reductions for the lifetime of the scope and send them merged when
 // it ends (defer_reductions).  On unwinding (an exception between the two calls) nothing is sent any more, but the handle must
 // not stay in the deferring state: later solves would consume rank-local sums without an error.
@@ -74,17 +68,9 @@ struct DeferScope {
   }
 };
 
-static int sc_check(int step, double value, double tol, int maxsteps) {  // SolverControl::check: 0 iterate, 1 success, 2 failure
-  if (value <= tol) return 1;
-  if (step >= maxsteps || std::isnan(value)) return 2;
-  return 0;
-}
-
 static double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
-constexpr int N_TMP = 30;  // SolverGMRES::AdditionalData::max_n_tmp_vectors
-enum { S_H = 8 /* 8..8+N_TMP */, S_NRM = 40, S_H2 = 41 /* re-orthogonalisation coefficients 41..41+N_TMP */, S_DH = 2, S_GH = 3, S_RES = 4, S_GH2 = 5 /* S_RES sits between the two g.h slots: whichever is current, the pair is adjacent */,
-       S_T = 39 /* |b|^2 of a relative tolerance: next to S_NRM, the two travel to the host in one publication (Seams::rtol) */ };
+constexpr int N_TMP = KRYLOV_N_TMP;  // (the scalar slots: nsx_internal.hpp)
 
 // The seams between an inner solve and the vector operations its caller wraps around it (NSX_STEP_FUSED, prec_vmult): what the solver
 // does in launches it has anyway instead of the caller in launches of its own.  Every one leaves bit for bit the doubles of the
@@ -102,29 +88,37 @@ struct Seams {
   bool neg_done = false;             // out: neg_out holds -neg_out + x
 };
 
+// What the caller of gmres() knows about its operands
+struct GmresOpts {
+  // a freshly created Epetra vector is zero.  That only matters when the preconditioner READS its destination (aSIMPLE takes it as the
+  // initial guess of its inner solve, Prec.hpp:271), i.e. for the outer solve; the inner solves' operators (SpMV, ILU) overwrite every
+  // owned entry, so their temporaries are handed out as they come from the pool.
+  bool zero_new = false;
+  // the caller has just zeroed x (Prec.hpp:401): the residual b - A x of the first cycle is b without touching the matrix (deal.II forms
+  // it through vmult + sadd; -1 * (A 0) + b gives the same numbers).
+  bool x_is_zero = false;
+  // the preconditioner is a plain kernel (ILU), not a solver with host round trips of its own: the operator AND the preconditioner of the
+  // next iteration are then enqueued behind the Gram-Schmidt sweep, before its coefficients are waited for.  (Fusing the two into one
+  // launch per rank block -- four waves for the block's rows of A x, then one wave for the sweeps -- was tried: 100 us against 35 + 35,
+  // the workgroups of the product hold LDS and registers the sweeping waves of other blocks need.)
+  bool plain_P = false;
+  // P is the velocity ILU(0) of the last initialisation (the inner solves on F): its triangular solves then run INSIDE the launch of the
+  // sweep that follows them (v_mgs with ilu_rhs, k_ilu_mgs) where the layout allows it -- the preconditioned vector never travels
+  // through memory between the two; only the operator of the next iteration is enqueued ahead.
+  bool P_is_ilu_F = false;
+};
+
 // SolverGMRES<VectorType>::solve (left preconditioning, default residual).
-// zero_new: a freshly created Epetra vector is zero.  That only matters when the preconditioner READS its destination
-// (aSIMPLE takes it as the initial guess of its inner solve, Prec.hpp:271), i.e. for the outer solve; the inner solves'
-// operators (SpMV, ILU) overwrite every owned entry, so their temporaries are handed out as they come from the pool.
-// x_is_zero: the caller has just zeroed x (Prec.hpp:401): the residual b - A x of the first cycle is b without touching the matrix
-// (deal.II forms it through vmult + sadd; -1 * (A 0) + b gives the same numbers).
-// plain_P: the preconditioner is a plain kernel (ILU), not a solver with host round trips of its own: the operator AND the
-// preconditioner of the next iteration are then enqueued behind the Gram-Schmidt sweep, before its coefficients are waited for.
-// (Fusing the two into one launch per rank block — four waves for the block's rows of A x, then one wave for the sweeps — was
-// tried: 100 us against 35 + 35, the workgroups of the product hold LDS and registers the sweeping waves of other blocks need.)
-// P_is_ilu_F: P is the velocity ILU(0) of the last initialisation (the inner solves on F): its triangular solves then run INSIDE the
-// launch of the sweep that follows them (v_mgs with ilu_rhs, k_ilu_mgs) where the layout allows it -- the preconditioned vector never
-// travels through memory between the two; only the operator of the next iteration is enqueued ahead.
-static SolveResult gmres(nsx_handle *h, const Op &A, double *x, const double *b, const Op &P, Span n, int len, double tol, int maxiter,
-                         bool zero_new = false, bool x_is_zero = false, bool plain_P = false, bool P_is_ilu_F = false, Seams *sm = nullptr) {
+static SolveResult gmres(nsx_handle *h, const Op &A, double *x, const double *b, const Op &P, Span n, int len, double tol, int maxiter, const GmresOpts &o = {},
+                         Seams *sm = nullptr) {
+  bool x_is_zero = o.x_is_zero;
   SolveResult res{1, 0, 0.0};
-  const bool zero_start = x_is_zero;
   bool first_cycle = true;
   std::vector<std::unique_ptr<Tmp>> tmp(N_TMP);
   auto vec = [&](int i) -> double * {
     if (!tmp[i]) {
       tmp[i] = std::make_unique<Tmp>(h, len);
-      if (zero_new) v_zero(h, len, tmp[i]->p());
+      if (o.zero_new) v_zero(h, len, tmp[i]->p());
     }
     return tmp[i]->p();
   };
@@ -145,7 +139,7 @@ static SolveResult gmres(nsx_handle *h, const Op &A, double *x, const double *b,
     gram = h->mgs.ls_gram.p + (size_t)depth.d * 1024;
   }
   // (in place needs the lane-owner stream: its kernel loads the right-hand side rows into LDS before it writes anything)
-  const bool ilu_conv = P_is_ilu_F && h->inner_precision == NSX_INNER_FP64 /* the fused kernel reads the double stream only */ && !h->comm && h->schedF.packed_ok && !h->schedF.levelled && h->schedF.stream_ncomp == h->dim &&
+  const bool ilu_conv = o.P_is_ilu_F && h->inner_precision == NSX_INNER_FP64 /* the fused kernel reads the double stream only */ && !h->comm && h->schedF.packed_ok && !h->schedF.levelled && h->schedF.stream_ncomp == h->dim &&
                         ilu_mgs_wanted();  // opt-in: see ilu_mgs_entries (nsx_mgs.hip)
   double H[N_TMP][N_TMP - 1];
   double gamma[N_TMP], ci[N_TMP - 1], si[N_TMP - 1], hh[N_TMP + 2], h2[N_TMP + 2];
@@ -172,7 +166,6 @@ static SolveResult gmres(nsx_handle *h, const Op &A, double *x, const double *b,
     if (first_cycle && sm && sm->rtol >= 0.0) {
       double two[2];
       read_scalars(h, S_T, 2, two);
-      static_assert(S_NRM == S_T + 1, "one publication");
       tol = sm->rtol * std::sqrt(two[0]);
       rho = std::sqrt(two[1]);
     } else rho = std::sqrt(read_scalar(h, S_NRM));
@@ -225,7 +218,7 @@ static SolveResult gmres(nsx_handle *h, const Op &A, double *x, const double *b,
           if (ilu_conv) {  // the next iteration's product goes straight into its own vector; its preconditioner runs inside the next sweep's launch
             A(vec(inner + 2), vv);
             ahead = 1;
-          } else if (plain_P && ahead_mode == 2) {  // operator AND preconditioner of the next iteration are plain kernels that depend on vv alone
+          } else if (o.plain_P && ahead_mode == 2) {  // operator AND preconditioner of the next iteration are plain kernels that depend on vv alone
             apply_AP(vec(inner + 2), vv);
             ahead = 2;
           } else {   // the outer solve's preconditioner runs Krylov solves of its own (host round trips, the same scalar slots): only A
@@ -277,7 +270,7 @@ static SolveResult gmres(nsx_handle *h, const Op &A, double *x, const double *b,
     }
     double *vs[N_TMP];
     for (int i = 0; i < dim; ++i) vs[i] = vec(i);
-    if (sm && zero_start && first_cycle) {  // x is zero and has not been stored: the sum alone, and the caller's sadd with it if this is the end
+    if (sm && o.x_is_zero && first_cycle) {  // x is zero and has not been stored: the sum alone, and the caller's sadd with it if this is the end
       double *out = (sm->neg_out && state != 0) ? sm->neg_out : x;
       v_axpy_multi_into(h, n, out, nullptr, out == x ? nullptr : sm->neg_out, dim, vs, y);
       if (out == x) sm->x_written = true;
@@ -372,12 +365,11 @@ static Op schur_ilu(nsx_handle *h) {
 // persistent launch where the layout allows it (nsx_cg.hip), else two launches per iteration, else the launch-per-operation solver
 // above.  The preconditioners' vmult and the test hook nsx_schur_cg both solve through here.
 static SolveResult schur_cg(nsx_handle *h, double rtol, int maxit, double *x, const double *b) {
-  int steps = 0, status = 0;
-  double last = 0.0;
-  h->cg_last_rpg = h->cg_last_lres = 0;
-  if (cg_schur_persistent(h, x, b, rtol, maxit, &steps, &last, &status)) return SolveResult{status, steps, last};
-  if (cg_schur_fused(h, x, b, rtol, maxit, &steps, &last, &status)) return SolveResult{status, steps, last};  // distributed, or too many blocks for a resident grid: two launches per iteration
-  h->cg_last_path = 1;
+  SolveResult res{0, 0, 0.0};
+  h->cg.last_rpg = h->cg.last_lres = 0;
+  if (cg_schur_persistent(h, x, b, rtol, maxit, res)) return res;
+  if (cg_schur_fused(h, x, b, rtol, maxit, res)) return res;  // distributed, or too many blocks for a resident grid: two launches per iteration
+  h->cg.last_path = 1;
   const Op Sm = schur_product(h), PS = schur_ilu(h);
   OpDot PSdot = [h](double *d, const double *s, int slot) { return ilu_solve(h, h->gS, h->schedS, h->luS.p, s, d, 1, "ilu_solve_S", slot); };
   return cg(h, Sm, x, b, PS, h->n_p, h->len_p, rtol * norm2(h, h->n_p, b), maxit, &PSdot);
@@ -398,7 +390,7 @@ __global__ void k_same_and_keep(int n, const double *__restrict__ w, double *__r
 static bool schur_inputs_unchanged(nsx_handle *h, int type) {
   const bool cache = env_on("NSX_SCHUR_CACHE");  // read per call: bench.py times both schedules on one handle
   const int n = h->len_u;  // owned + ghost weights
-  volatile int *flag = (volatile int *)(h->pub_host + N_SLOTS + 4);
+  volatile int *flag = pub_word_host(h, PUB_SCHUR_SAME);
   const bool had = h->schur_valid && h->schur_type == type && (int)h->schur_w_prev.n == n;
   if (!had) {
     h->schur_w_prev.alloc(n);
@@ -408,7 +400,7 @@ static bool schur_inputs_unchanged(nsx_handle *h, int type) {
   }
   comm_halo_u(h, h->schur_w.p);
   *flag = 0;
-  hipLaunchKernelGGL(k_same_and_keep, dim3(cdiv(n, 256)), dim3(256), 0, h->stream, n, h->schur_w.p, h->schur_w_prev.p, (int *)(h->pub_dev + N_SLOTS + 4));
+  hipLaunchKernelGGL(k_same_and_keep, dim3(cdiv(n, 256)), dim3(256), 0, h->stream, n, h->schur_w.p, h->schur_w_prev.p, pub_word_dev(h, PUB_SCHUR_SAME));
   HIP_CHECK(hipStreamSynchronize(h->stream));
   // a distributed run rebuilds every time: the ranks would have to agree on the answer first (the rebuild contains collectives)
   return cache && !h->comm && *flag == 0;
@@ -513,11 +505,14 @@ void prec_vmult(nsx_handle *h, int type, double tol, int maxit, double *dst, con
   // SolverGMRES on F with tolerance tol * |b| and the velocity ILU(0).  sm (fused): |b|^2 is enqueued here and collected with the
   // solve's first residual norm, the residual of a cycle comes from the product's own launch, and what else the caller has set in sm
   auto solve_F = [&](double *x, const double *b, bool x_is_zero, Seams *sm) {
-    if (!sm) return count(st, true, gmres(h, Fm, x, b, PF, n_u, len_u, tol * norm2(h, n_u, b), maxit, false, x_is_zero, true, true));
+    GmresOpts o;
+    o.x_is_zero = x_is_zero;
+    o.plain_P = o.P_is_ilu_F = true;
+    if (!sm) return count(st, true, gmres(h, Fm, x, b, PF, n_u, len_u, tol * norm2(h, n_u, b), maxit, o));
     sm->rtol = tol;
     sm->A_resid = &Fr;
     v_dot(h, n_u, b, b, S_T);
-    count(st, true, gmres(h, Fm, x, b, PF, n_u, len_u, 0.0, maxit, false, x_is_zero, true, true, sm));
+    count(st, true, gmres(h, Fm, x, b, PF, n_u, len_u, 0.0, maxit, o, sm));
   };
   // the first velocity solve of Yosida / SIMPLE: F x = src_u from x = src_u.  Fused, x is dst_u and only written: the first product
   // reads src_u, the first update writes dst_u = src_u + sum
@@ -585,7 +580,7 @@ void prec_vmult(nsx_handle *h, int type, double tol, int maxit, double *dst, con
     if (fused) {                                                                               // :287-289
       ss.rtol = tol;
       v_dot(h, n_p, tmp_p.p(), tmp_p.p(), S_T);
-      count(st, false, gmres(h, Sm, dst_p, tmp_p.p(), PS, n_p, len_p, 0.0, maxit, false, false, false, false, &ss));
+      count(st, false, gmres(h, Sm, dst_p, tmp_p.p(), PS, n_p, len_p, 0.0, maxit, {}, &ss));
     } else count(st, false, gmres(h, Sm, dst_p, tmp_p.p(), PS, n_p, len_p, tol * norm2(h, n_p, tmp_p.p()), maxit));
     v_scale_vec(h, n_u, dst_u, h->diag_D.p);                                                   // :294
     v_scale(h, n_p, dst_p, 1. / 1.0);                                                          // :298, alpha = 1 (:328)
@@ -646,8 +641,9 @@ void solve_time_step(nsx_handle *h, int type, double tol, double inner_rtol, int
   // converges as it stands), the owned pressure entries by the copy of src_p the Schur CG starts from; ghost entries are written by the
   // halo exchange in front of every product that reads them, and the BLAS-1 spans skip the gap between the two owned parts.  The
   // operator's own temporary is overwritten row by row by the block product.
-  const bool zero_new = !fused || type == NSX_PREC_ASIMPLE || type == NSX_PREC_AYOSIDA;
-  SolveResult r = gmres(h, A, h->sol_owned.p, h->rhs.p, P, n, h->len_blk, tol, maxiter, zero_new);  // NS3D.cpp:574
+  GmresOpts o;
+  o.zero_new = !fused || type == NSX_PREC_ASIMPLE || type == NSX_PREC_AYOSIDA;
+  SolveResult r = gmres(h, A, h->sol_owned.p, h->rhs.p, P, n, h->len_blk, tol, maxiter, o);  // NS3D.cpp:574
   v_copy(h, h->len_blk, h->sol.p, h->sol_owned.p);  // solution = solution_owned (NS3D.cpp:638): copy + ghost import
   comm_halo_u(h, h->sol.p);
   comm_halo_p(h, h->sol.p + h->off_p);

@@ -576,7 +576,7 @@ void convert_F_f32(nsx_handle *h) {
   const int64_t n = h->gA.nnz();
   h->vF32.alloc((size_t)n);
   LaunchScope ls(h, "F_to_f32", 12.0 * (double)n);
-  if (n > 0) hipLaunchKernelGGL(k_to_f32, dim3(cdiv(n, 256)), dim3(256), 0, h->stream, n, h->vF.p, h->vF32.p, (int *)(h->pub_dev + N_SLOTS + 3));
+  if (n > 0) hipLaunchKernelGGL(k_to_f32, dim3(cdiv(n, 256)), dim3(256), 0, h->stream, n, h->vF.p, h->vF32.p, pub_word_dev(h, PUB_ILU_ERR));
 }
 
 // ------------------------------------------------------------------ diagonals
