@@ -1,14 +1,21 @@
-// nsx_setup.hip — handle life cycle and the host-side setup products of libnsx:
-// sparsity graphs (reference NavierStokes3D.cpp:109-124), cell geometry, deterministic gather maps,
-// per-rank ILU(0) level schedules (Ifpack overlap-0 semantics) and the Schur pattern
-// (EpetraExt::MatrixMatrix::Multiply structural product, reference Preconditioners.hpp:144,248,358,468).
+// nsx_setup.hip — handle life cycle and the order of events of the set-up: what is planned, uploaded and allocated when a mesh,
+// rank tables or a layout arrive.  The combinatorics are host headers, pure functions on Csr and vectors that this file calls and
+// whose results it uploads: sparsity graphs and the Schur pattern (host/graph.hpp: reference NavierStokes3D.cpp:109-124 and the
+// structural product of EpetraExt::MatrixMatrix::Multiply, Preconditioners.hpp:144,248,358,468), deterministic gather maps
+// (host/gather_map.hpp), per-rank ILU(0) level schedules (host/ilu_levels.hpp, host/ilu_stream.hpp: Ifpack overlap-0 semantics,
+// SURVEY.md D4), the chunks and launch tables of the staged SpMV (host/spmv_plan.hpp) and the internal layout (host/layout.hpp).
+// Kept here: argument checks and connectivity, cell geometry, the knob reads and path choices, error codes, debug lines, and the one
+// kernel, k_perm_vec, behind the caller-order <-> internal-order staging of vectors.
 #include <algorithm>
 #include <cmath>
 #include <numeric>
 
 #include "nsx_internal.hpp"
+#include "../host/gather_map.hpp"
+#include "../host/ilu_levels.hpp"
 #include "../host/ilu_stream.hpp"
 #include "../host/layout.hpp"
+#include "../host/spmv_plan.hpp"
 
 using namespace nsx;
 
@@ -32,399 +39,159 @@ static void upload_csr(nsx_handle *h, DevCsr &d, bool square) {
 // contributions of every cell-local pair (r,c) to CSR entry (rows[r], cols[c]); src = plane*stride*n_cells + cell
 static void build_gather(nsx_handle *h, const Csr &g, int n_cells, int per_r, const int32_t *cell_r, int per_c,
                          const int32_t *cell_c, int plane_stride, bool plane_rc_swapped, GatherMap &gm) {
-  const int64_t nnz = g.nnz();
-  std::vector<int32_t> ptr(nnz + 1, 0);
-  std::vector<int32_t> epos((size_t)n_cells * per_r * per_c);
-  for (int c = 0; c < n_cells; ++c)
-    for (int a = 0; a < per_r; ++a)
-      for (int b = 0; b < per_c; ++b) {
-        const int32_t row = cell_r[(size_t)c * per_r + a];
-        if (row >= g.n_rows) {  // ghost row: assembled by its owner
-          epos[((size_t)c * per_r + a) * per_c + b] = -1;
-          continue;
-        }
-        const int32_t e = find_in_row(g, row, cell_c[(size_t)c * per_c + b]);
-        if (e < 0) NSX_THROW(NSX_ERR_ARG, "internal: cell pair not in graph");
-        epos[((size_t)c * per_r + a) * per_c + b] = e;
-        ptr[e + 1]++;
-      }
-  for (int64_t e = 0; e < nnz; ++e) ptr[e + 1] += ptr[e];
-  std::vector<int32_t> src(ptr[nnz]);
-  std::vector<int32_t> fill(ptr.begin(), ptr.end() - 1);
-  for (int c = 0; c < n_cells; ++c)
-    for (int a = 0; a < per_r; ++a)
-      for (int b = 0; b < per_c; ++b) {
-        const int32_t e = epos[((size_t)c * per_r + a) * per_c + b];
-        if (e < 0) continue;
-        const int64_t plane = plane_rc_swapped ? ((int64_t)b * per_r + a) : ((int64_t)a * per_c + b);
-        const int64_t off = plane * plane_stride * n_cells + c;
-        if (off > INT32_MAX) NSX_THROW(NSX_ERR_UNSUPPORTED, "mesh too large for int32 gather offsets");
-        src[fill[e]++] = (int32_t)off;
-      }
-  gm.n_out = nnz;
-  gm.n_src = (int64_t)src.size();
-  gm.ptr.upload(ptr, h->stream);
-  gm.src.upload(src, h->stream);
+  const GatherLists l = build_gather_map(g, n_cells, per_r, cell_r, per_c, cell_c, plane_stride, plane_rc_swapped);
+  if (l.status == GATHER_PAIR_NOT_IN_GRAPH) NSX_THROW(NSX_ERR_ARG, "internal: cell pair not in graph");
+  if (l.status == GATHER_OFFSET_OVERFLOW) NSX_THROW(NSX_ERR_UNSUPPORTED, "mesh too large for int32 gather offsets");
+  gm.n_out = g.nnz();
+  gm.n_src = (int64_t)l.src.size();
+  gm.ptr.upload(l.ptr, h->stream);
+  gm.src.upload(l.src, h->stream);
 }
 
-void setup_ilu_schedule(nsx_handle *h, const Csr &g, const std::vector<int32_t> &bptr, IluSchedule &s, int blocks_per_wave, bool allow_dense, int ncomp) {
-  const int nb = (int)bptr.size() - 1;
-  s.n_blocks = nb;
-  s.block_ptr_h = bptr;
-  s.max_rows = 0;
-  s.path = IluSchedule::Path();
-  std::vector<int32_t> lev(g.n_rows, 0);
-  std::vector<int32_t> f_ptr{0}, f_rows, b_ptr{0}, b_rows, off_f(nb + 1, 0), off_b(nb + 1, 0);
-  f_rows.reserve(g.n_rows);
-  b_rows.reserve(g.n_rows);
-  s.max_levels = 0;
-  std::vector<std::vector<int32_t>> buckets;
+// ---- blocks beyond what one wave (packed stream) or one workgroup can hold: merged level lists, one launch per level
+static void use_levelled(nsx_handle *h, const Csr &g, const IluLevels &lv, IluSchedule &s) {
+  for (int pass = 0; pass < 2; ++pass) {
+    const MergedLevels m = merge_levels(g, lv, pass == 1);
+    (pass == 0 ? s.gl_f_ptr_h : s.gl_b_ptr_h) = m.ptr;
+    (pass == 0 ? s.gl_f_rows : s.gl_b_rows).upload(m.rows, h->stream);
+    (pass == 0 ? s.gl_f_rec : s.gl_b_rec).upload(m.rec, h->stream);
+  }
+  s.block_ptr.upload(s.block_ptr_h, h->stream);
+  if (nsx_debug())
+    fprintf(stderr, "[nsx] ilu schedule: rows %d blocks %d max_rows %d -> levelled, %d levels\n", g.n_rows, s.n_blocks, s.max_rows, s.max_levels);
+}
+
+// ---- explicit block inverses.  Worth it when the blocks are few, small and deep: the dense matrices of all blocks
+// together (sum n_b^2) must not cost more traffic than the chain of the sparse sweep costs time.  Used for the Schur
+// matrix (one component, ~100-row blocks with ~95 dependency levels); the velocity blocks stay sparse.
+static void use_dense_inverses(nsx_handle *h, IluSchedule &s) {
+  const int nb = s.n_blocks;
+  std::vector<int64_t> off(nb + 1, 0);
   for (int b = 0; b < nb; ++b) {
-    const int r0 = bptr[b], r1 = bptr[b + 1];
-    s.max_rows = std::max(s.max_rows, r1 - r0);
-    for (int pass = 0; pass < 2; ++pass) {
-      int nl = 0;
-      if (pass == 0) {
-        for (int i = r0; i < r1; ++i) {
-          int l = 0;
-          for (int k = g.rowptr[i]; k < g.rowptr[i + 1]; ++k) {
-            const int j = g.colind[k];
-            if (j >= i) break;
-            if (j >= r0) l = std::max(l, lev[j] + 1);
-          }
-          lev[i] = l;
-          nl = std::max(nl, l + 1);
-        }
-      } else {
-        for (int i = r1 - 1; i >= r0; --i) {
-          int l = 0;
-          for (int k = g.rowptr[i + 1] - 1; k >= g.rowptr[i]; --k) {
-            const int j = g.colind[k];
-            if (j <= i) break;
-            if (j < r1) l = std::max(l, lev[j] + 1);
-          }
-          lev[i] = l;
-          nl = std::max(nl, l + 1);
-        }
-      }
-      if (r1 == r0) nl = 0;
-      buckets.assign(nl, {});
-      for (int i = r0; i < r1; ++i) buckets[lev[i]].push_back(i);
-      auto &ptr = pass == 0 ? f_ptr : b_ptr;
-      auto &rows = pass == 0 ? f_rows : b_rows;
-      for (int l = 0; l < nl; ++l) {
-        rows.insert(rows.end(), buckets[l].begin(), buckets[l].end());
-        ptr.push_back((int32_t)rows.size());
-      }
-      (pass == 0 ? off_f : off_b)[b + 1] = (int32_t)ptr.size() - 1;
-      s.max_levels = std::max(s.max_levels, nl);
-    }
+    const int64_t n = s.block_ptr_h[b + 1] - s.block_ptr_h[b];
+    off[b + 1] = off[b] + n * n;
   }
-  s.in_block_nnz = 0;
-  for (int b = 0; b < nb; ++b)
-    for (int i = bptr[b]; i < bptr[b + 1]; ++i)
-      for (int q = g.rowptr[i]; q < g.rowptr[i + 1]; ++q) s.in_block_nnz += g.colind[q] >= bptr[b] && g.colind[q] < bptr[b + 1];
-  // ---- the in-block part of every row is one contiguous range of its (sorted) entries: [in_lo, in_hi); in_cptr: running count of
-  //      in-block entries (the compact numbering k_ilu_factor_lds stages a block with)
-  std::vector<int32_t> lo(g.n_rows), hi(g.n_rows);
+  // (blocks of at most 256 rows -- what the Schur CG kernels take -- cost at most 256 entries per row whatever the mesh size: no limit on their total;
+  // the 10.6 M-DoF mesh on one GPU has 4 833 blocks of <= 96 rows, 42 M entries = 335 MB)
+  const int64_t limit = env_i64("NSX_DENSE_MAX", (int64_t)32 << 20);  // entries (256 MB)
+  if (off[nb] > 0 && (off[nb] <= limit || (s.max_rows <= 256 && !env_set("NSX_DENSE_MAX"))) && s.max_rows <= 4096) {
+    s.dense = true;
+    s.dn_entries = off[nb];
+    s.dn_off.upload(off, h->stream);
+    s.dn_P.alloc((size_t)off[nb]);
+    if (nsx_debug()) fprintf(stderr, "[nsx] ilu schedule: explicit block inverses, %lld entries (%.1f MB)\n", (long long)off[nb], 8e-6 * off[nb]);
+  }
+}
+
+// ---- the packed stream of the solve kernel (host/ilu_stream.hpp, k_ilu_solve_lanes).  Building it is list scheduling per wave plus
+// an upload the size of the factor.
+static void use_lane_stream(nsx_handle *h, const Csr &g, IluSchedule &s, int blocks_per_wave, int ncomp) {
+  IluStream st;
+  const int ept = std::max(1, std::min(4, env_int("NSX_ILU_EPT", 2)));
+  build_ilu_stream(g, s.block_ptr_h, std::max(1, blocks_per_wave), ncomp, 2, st, ept);
+  s.stream_ncomp = ncomp;
+  s.stream_epl = st.epl;
+  s.blocks_per_wave = blocks_per_wave;
+  s.n_waves = st.n_waves;
+  s.max_wave_rows = st.max_wave_rows;
+  s.n_slabs = st.n_slabs;
+  s.packed_ok = st.ok;
+  if (nsx_debug())
+    fprintf(stderr, "[nsx] ilu schedule: rows %d blocks %d max_rows %d levels(max) %d lane-owner stream: %d waves (%d blocks each), %d entries per tick, slabs %lld (max/wave %lld) fill %.2f, "
+                    "%.1f MB, in-block entries %lld, LDS rows/wave <= %d%s\n",
+            g.n_rows, s.n_blocks, s.max_rows, s.max_levels, st.n_waves, blocks_per_wave, st.epl, (long long)st.n_slabs, (long long)st.max_wave_slabs,
+            (double)st.used_slots / (double)std::max<int64_t>(1, st.n_slabs * 64 * st.epl), 1e-6 * (double)st.n_slabs * 64 * (8 * st.epl + 4 * ilu_meta_words(st.epl)),
+            (long long)st.in_block_nnz, st.max_wave_rows, st.ok ? "" : " (too many: not used)");
+  s.pk_row_ptr.upload(st.row_ptr, h->stream);
+  s.pk_rows.upload(st.rows, h->stream);
   {
-    std::vector<int32_t> cptr(g.n_rows + 1, 0);
-    s.max_block_nnz = 0;
-    for (int b = 0; b < nb; ++b) {
-      for (int i = bptr[b]; i < bptr[b + 1]; ++i) {
-        const int32_t *cb = g.colind.data() + g.rowptr[i], *ce = g.colind.data() + g.rowptr[i + 1];
-        lo[i] = (int32_t)(std::lower_bound(cb, ce, bptr[b]) - g.colind.data());
-        hi[i] = (int32_t)(std::lower_bound(cb, ce, bptr[b + 1]) - g.colind.data());
-        cptr[i + 1] = cptr[i] + (hi[i] - lo[i]);
-      }
-      s.max_block_nnz = std::max(s.max_block_nnz, cptr[bptr[b + 1]] - cptr[bptr[b]]);
-    }
-    std::vector<int32_t> cpos((size_t)cptr[g.n_rows]);
-    for (int i = 0; i < g.n_rows; ++i)
-      for (int p = lo[i]; p < hi[i]; ++p) cpos[cptr[i] + (p - lo[i])] = p;
-    s.in_lo.upload(lo, h->stream);
-    s.in_hi.upload(hi, h->stream);
-    s.in_cptr.upload(cptr, h->stream);
-    s.in_cpos.upload(cpos, h->stream);
-    // blocks in order of descending work: the factorisation's workgroups are dispatched in this order, the big blocks first
-    std::vector<int32_t> order(nb);
-    for (int b = 0; b < nb; ++b) order[b] = b;
-    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return cptr[bptr[x + 1]] - cptr[bptr[x]] > cptr[bptr[y + 1]] - cptr[bptr[y]]; });
-    s.fac_order.upload(order, h->stream);
+    std::vector<int32_t> slot(g.n_rows);
+    for (size_t k = 0; k < st.rows.size(); ++k) slot[st.rows[k]] = (int32_t)k;
+    s.pk_dinv_slot.upload(slot, h->stream);
   }
-  // ---- blocks beyond what one wave (packed stream) or one workgroup can hold: merged level lists, one launch per level
+  s.pk_slab_ptr.upload(st.slab_ptr, h->stream);
+  s.pk_meta.upload(reinterpret_cast<const int32_t *>(st.meta.data()), st.meta.size(), h->stream);
+  s.pk_slot_of.upload(st.slot_of, h->stream);
+  s.pk_val.alloc((size_t)(st.n_slabs + ILU_STREAM_PAD) * 64 * st.epl);
+  s.pk_val.zero(h->stream);
+  s.pk_val32.release();  // the float twin of the stream is laid out again by the next factorisation that wants it
+  s.stream_f32 = false;
+  s.pk_dinv.alloc(g.n_rows);
+}
+
+// plan (host/ilu_levels.hpp), upload what every path reads, then the one path the schedule takes
+void setup_ilu_schedule(nsx_handle *h, const Csr &g, const std::vector<int32_t> &bptr, IluSchedule &s, int blocks_per_wave, bool allow_dense, int ncomp) {
+  const IluLevels lv = build_ilu_levels(g, bptr);
+  s.n_blocks = (int)bptr.size() - 1;
+  s.block_ptr_h = bptr;
+  s.path = IluSchedule::Path();
+  s.max_rows = lv.max_rows;
+  s.max_levels = lv.max_levels;
+  s.in_block_nnz = lv.in_block_nnz;
+  s.max_block_nnz = lv.max_block_nnz;
+  s.in_lo.upload(lv.in_lo, h->stream);
+  s.in_hi.upload(lv.in_hi, h->stream);
+  s.in_cptr.upload(lv.in_cptr, h->stream);
+  s.in_cpos.upload(lv.in_cpos, h->stream);
+  s.fac_order.upload(lv.fac_order, h->stream);  // the factorisation's workgroups are dispatched in this order, the big blocks first
   const int levelled_min = env_int("NSX_LEVELLED_MIN", 4096);
   s.levelled = s.max_rows > levelled_min;
   s.packed_ok = false;
   s.dense = false;
-  if (s.levelled) {
-    for (int pass = 0; pass < 2; ++pass) {
-      const auto &ptr = pass == 0 ? f_ptr : b_ptr;
-      const auto &rows = pass == 0 ? f_rows : b_rows;
-      const auto &off = pass == 0 ? off_f : off_b;
-      std::vector<int32_t> gptr(s.max_levels + 1, 0), grows(rows.size());
-      for (int b = 0; b < nb; ++b)
-        for (int l = off[b]; l < off[b + 1]; ++l) gptr[l - off[b] + 1] += ptr[l + 1] - ptr[l];
-      for (int l = 0; l < s.max_levels; ++l) gptr[l + 1] += gptr[l];
-      std::vector<int32_t> fill(gptr.begin(), gptr.end() - 1);
-      for (int b = 0; b < nb; ++b)
-        for (int l = off[b]; l < off[b + 1]; ++l)
-          for (int q = ptr[l]; q < ptr[l + 1]; ++q) grows[fill[l - off[b]]++] = rows[q];
-      (pass == 0 ? s.gl_f_ptr_h : s.gl_b_ptr_h) = gptr;
-      (pass == 0 ? s.gl_f_rows : s.gl_b_rows).upload(grows, h->stream);
-      // one record per row in level order -- {row, first entry, end of entries, diagonal} of the sweep's triangle -- so that a level
-      // kernel learns everything about its row in ONE coalesced load (it used to chase rows -> diag, in_lo/in_hi -> entries)
-      std::vector<int32_t> rec(4 * grows.size());
-      for (size_t r = 0; r < grows.size(); ++r) {
-        const int i = grows[r], d = find_in_row(g, i, i);
-        rec[4 * r + 0] = i;
-        rec[4 * r + 1] = pass == 0 ? lo[i] : d + 1;
-        rec[4 * r + 2] = pass == 0 ? d : hi[i];
-        rec[4 * r + 3] = d;
-      }
-      (pass == 0 ? s.gl_f_rec : s.gl_b_rec).upload(rec, h->stream);
-    }
-    s.block_ptr.upload(bptr, h->stream);
-    if (nsx_debug())
-      fprintf(stderr, "[nsx] ilu schedule: rows %d blocks %d max_rows %d -> levelled, %d levels\n", g.n_rows, nb, s.max_rows, s.max_levels);
-    return;
-  }
+  if (s.levelled) return use_levelled(h, g, lv, s);
   s.block_ptr.upload(bptr, h->stream);
-  s.fwd_lvl_ptr.upload(f_ptr, h->stream);
-  s.fwd_rows.upload(f_rows, h->stream);
-  s.bwd_lvl_ptr.upload(b_ptr, h->stream);
-  s.bwd_rows.upload(b_rows, h->stream);
-  s.blk_lvl_off.upload(off_f, h->stream);
-  s.blk_lvl_off_b.upload(off_b, h->stream);
-
-  // ---- explicit block inverses.  Worth it when the blocks are few, small and deep: the dense matrices of all blocks
-  // together (sum n_b^2) must not cost more traffic than the chain of the sparse sweep costs time.  Used for the Schur
-  // matrix (one component, ~100-row blocks with ~95 dependency levels); the velocity blocks stay sparse.
-  s.dense = false;
-  if (allow_dense && ncomp == 1) {
-    std::vector<int64_t> off(nb + 1, 0);
-    for (int b = 0; b < nb; ++b) {
-      const int64_t n = bptr[b + 1] - bptr[b];
-      off[b + 1] = off[b] + n * n;
-    }
-    // (blocks of at most 256 rows -- what the Schur CG kernels take -- cost at most 256 entries per row whatever the mesh size: no limit on their total;
-    // the 10.6 M-DoF mesh on one GPU has 4 833 blocks of <= 96 rows, 42 M entries = 335 MB)
-    const int64_t limit = env_i64("NSX_DENSE_MAX", (int64_t)32 << 20);  // entries (256 MB)
-    if (off[nb] > 0 && (off[nb] <= limit || (s.max_rows <= 256 && !env_set("NSX_DENSE_MAX"))) && s.max_rows <= 4096) {
-      s.dense = true;
-      s.dn_entries = off[nb];
-      s.dn_off.upload(off, h->stream);
-      s.dn_P.alloc((size_t)off[nb]);
-      if (nsx_debug()) fprintf(stderr, "[nsx] ilu schedule: explicit block inverses, %lld entries (%.1f MB)\n", (long long)off[nb], 8e-6 * off[nb]);
-    }
-  }
-  // ---- the packed stream of the solve kernel (host/ilu_stream.hpp, k_ilu_solve_lanes) -- unless it would never be used: the
-  // schedule is served by the explicit block inverses above (the Schur matrix), or its largest block alone does not fit the 16-bit
-  // LDS addresses of the stream (few large ranks: up to 4096-row blocks run through the workgroup-per-block kernel).  Building it
-  // is list scheduling per wave plus an upload the size of the factor; slot_of stays null, so the factorisation kernels skip the
-  // stream writes.
+  s.fwd_lvl_ptr.upload(lv.fwd.lvl_ptr, h->stream);
+  s.fwd_rows.upload(lv.fwd.rows, h->stream);
+  s.bwd_lvl_ptr.upload(lv.bwd.lvl_ptr, h->stream);
+  s.bwd_rows.upload(lv.bwd.rows, h->stream);
+  s.blk_lvl_off.upload(lv.fwd.blk_off, h->stream);
+  s.blk_lvl_off_b.upload(lv.bwd.blk_off, h->stream);
+  if (allow_dense && ncomp == 1) use_dense_inverses(h, s);
+  // The lane-owner stream -- unless it would never be used: the schedule is served by the explicit block inverses (the Schur matrix),
+  // or its largest block alone does not fit the 16-bit LDS addresses of the stream (few large ranks: up to 4096-row blocks run through
+  // the workgroup-per-block kernel).  slot_of stays null then, so the factorisation kernels skip the stream writes.
   const bool stream_fits = ((size_t)s.max_rows + 64) * sizeof(double) * ncomp <= 65536;
   s.n_waves = 0;
   s.n_slabs = 0;
   s.stream_ncomp = 0;
-  if (!s.dense && stream_fits) {
-    IluStream st;
-    const int ept = std::max(1, std::min(4, env_int("NSX_ILU_EPT", 2)));
-    build_ilu_stream(g, bptr, std::max(1, blocks_per_wave), ncomp, 2, st, ept);
-    s.stream_ncomp = ncomp;
-    s.stream_epl = st.epl;
-    s.blocks_per_wave = blocks_per_wave;
-    s.n_waves = st.n_waves;
-    s.max_wave_rows = st.max_wave_rows;
-    s.n_slabs = st.n_slabs;
-    s.packed_ok = st.ok;
-    if (nsx_debug())
-      fprintf(stderr, "[nsx] ilu schedule: rows %d blocks %d max_rows %d levels(max) %d lane-owner stream: %d waves (%d blocks each), %d entries per tick, slabs %lld (max/wave %lld) fill %.2f, "
-                      "%.1f MB, in-block entries %lld, LDS rows/wave <= %d%s\n",
-              g.n_rows, nb, s.max_rows, s.max_levels, st.n_waves, blocks_per_wave, st.epl, (long long)st.n_slabs, (long long)st.max_wave_slabs,
-              (double)st.used_slots / (double)std::max<int64_t>(1, st.n_slabs * 64 * st.epl), 1e-6 * (double)st.n_slabs * 64 * (8 * st.epl + 4 * ilu_meta_words(st.epl)),
-              (long long)st.in_block_nnz, st.max_wave_rows, st.ok ? "" : " (too many: not used)");
-    s.pk_row_ptr.upload(st.row_ptr, h->stream);
-    s.pk_rows.upload(st.rows, h->stream);
-    {
-      std::vector<int32_t> slot(g.n_rows);
-      for (size_t k = 0; k < st.rows.size(); ++k) slot[st.rows[k]] = (int32_t)k;
-      s.pk_dinv_slot.upload(slot, h->stream);
-    }
-    s.pk_slab_ptr.upload(st.slab_ptr, h->stream);
-    s.pk_meta.upload(reinterpret_cast<const int32_t *>(st.meta.data()), st.meta.size(), h->stream);
-    s.pk_slot_of.upload(st.slot_of, h->stream);
-    s.pk_val.alloc((size_t)(st.n_slabs + ILU_STREAM_PAD) * 64 * st.epl);
-    s.pk_val.zero(h->stream);
-    s.pk_val32.release();  // the float twin of the stream is laid out again by the next factorisation that wants it
-    s.stream_f32 = false;
-    s.pk_dinv.alloc(g.n_rows);
-  }
-
+  if (!s.dense && stream_fits) use_lane_stream(h, g, s, blocks_per_wave, ncomp);
 }
 
-// chunks = [bounds[c], bounds[c+1])
-// n_own: columns below it are owned by this handle (one GPU: all of them)
+// chunks = [bounds[c], bounds[c+1]); n_own: columns below it are owned by this handle (one GPU: all of them).  Same kernel, same lanes,
+// same sums per row with one launch table (one GPU) as with two (distributed: host/spmv_plan.hpp).
 void build_blocked(nsx_handle *h, const Csr &g, const std::vector<int32_t> &bounds, SpmvBlocked &b, int n_own) {
-  b.n_chunks = (int)bounds.size() - 1;
-  std::vector<int32_t> cptr((size_t)b.n_chunks + 1, 0), ucols, tmp;
-  std::vector<uint16_t> lidx(g.nnz());
-  b.max_ucols = b.max_rows = 0;
-  for (int c = 0; c < b.n_chunks; ++c) {
-    const int r0 = bounds[c], r1 = bounds[c + 1];
-    b.max_rows = std::max(b.max_rows, r1 - r0);
-    tmp.assign(g.colind.begin() + g.rowptr[r0], g.colind.begin() + g.rowptr[r1]);
-    std::sort(tmp.begin(), tmp.end());
-    tmp.erase(std::unique(tmp.begin(), tmp.end()), tmp.end());
-    if (tmp.size() > 65535) NSX_THROW(NSX_ERR_UNSUPPORTED, "blocked SpMV: chunk touches more than 65535 columns");
-    for (int p = g.rowptr[r0]; p < g.rowptr[r1]; ++p)
-      lidx[p] = (uint16_t)(std::lower_bound(tmp.begin(), tmp.end(), g.colind[p]) - tmp.begin());
-    ucols.insert(ucols.end(), tmp.begin(), tmp.end());
-    cptr[c + 1] = (int32_t)ucols.size();
-    b.max_ucols = std::max<int>(b.max_ucols, (int)tmp.size());
-  }
-  b.ucols_total = (double)ucols.size();
-  // launch tables.  One-GPU handles: one table over all chunks.  Distributed handles (n_own < number of columns): the chunks whose
-  // staged columns are all owned go into the first table -- launched while the ghost exchange is in flight -- and the chunks that stage
-  // a ghost column into the second one, launched behind it (the Epetra_Import + local multiply of every vmult, Preconditioners.hpp:382,405).
-  // Same kernel, same lanes, same sums per row as on one GPU.
-  auto make_desc = [&](const std::vector<int32_t> &chunks, DevBuf<int32_t> &out, int &grid, std::vector<int32_t> *order) {
-    // XCD k takes the chunks [cut[k], cut[k+1]) of the list: boundaries where the running non-zero count passes k / 8 of the total
-    const int nc = (int)chunks.size();
-    auto cnnz = [&](int c) { return (int64_t)(g.rowptr[bounds[c + 1]] - g.rowptr[bounds[c]]); };
-    int64_t total = 0;
-    for (int c : chunks) total += cnnz(c);
-    int cut[9];
-    cut[0] = 0;
-    int64_t run = 0;
-    for (int k = 1, j = 0; k <= 8; ++k) {
-      while (j < nc && (run + cnnz(chunks[j])) * 8 <= total * k) run += cnnz(chunks[j++]);
-      cut[k] = k == 8 ? nc : j;
-    }
-    int per_xcd = 0;
-    for (int k = 0; k < 8; ++k) per_xcd = std::max(per_xcd, cut[k + 1] - cut[k]);
-    grid = 8 * per_xcd;
-    if (order) order->assign((size_t)grid, -1);
-    std::vector<int32_t> desc((size_t)grid * 4, 0), list;
-    const bool largest_first = h->spmv_largest_first;
-    for (int k = 0; k < 8; ++k) {
-      list.assign(chunks.begin() + cut[k], chunks.begin() + cut[k + 1]);
-      if (largest_first) std::stable_sort(list.begin(), list.end(), [&](int32_t a, int32_t c) { return cnnz(a) > cnnz(c); });
-      for (size_t j = 0; j < list.size(); ++j) {
-        const int blk = (int)j * 8 + k, c = list[j];
-        if (order) (*order)[blk] = c;
-        desc[4 * (size_t)blk + 0] = cptr[c];
-        desc[4 * (size_t)blk + 1] = cptr[c + 1] - cptr[c];
-        desc[4 * (size_t)blk + 2] = bounds[c];
-        desc[4 * (size_t)blk + 3] = bounds[c + 1];
-      }
-    }
-    out.upload(desc, h->stream);
-  };
-  {
-    std::vector<int32_t> first, second;
-    int64_t nnz_second = 0;
-    for (int c = 0; c < b.n_chunks; ++c) {
-      const bool ghost = cptr[c + 1] > cptr[c] && ucols[(size_t)cptr[c + 1] - 1] >= n_own;  // the list is sorted: its last entry is the largest column
-      (ghost ? second : first).push_back(c);
-      if (ghost) nnz_second += g.rowptr[bounds[c + 1]] - g.rowptr[bounds[c]];
-    }
-    make_desc(first, b.desc, b.grid, &b.order);
-    b.n_chunks_if = (int)second.size();
-    b.grid_if = 0;
-    b.frac_if = g.nnz() ? (double)nnz_second / (double)g.nnz() : 0.0;
-    if (!second.empty()) make_desc(second, b.desc_if, b.grid_if, nullptr);
-  }
+  ChunkTable t = build_chunk_table(g, bounds, n_own, h->spmv_largest_first);
+  if (!t.ok) NSX_THROW(NSX_ERR_UNSUPPORTED, "blocked SpMV: chunk touches more than 65535 columns");
+  b.n_chunks = t.n_chunks;
+  b.max_ucols = t.max_ucols;
+  b.max_rows = t.max_rows;
+  b.ucols_total = (double)t.ucols.size();
+  b.desc.upload(t.desc, h->stream);
+  b.grid = t.grid;
+  b.order = std::move(t.order);
+  b.n_chunks_if = t.n_chunks_if;
+  b.grid_if = t.grid_if;
+  b.frac_if = t.frac_if;
+  if (b.n_chunks_if) b.desc_if.upload(t.desc_if, h->stream);
   b.crow.upload(bounds, h->stream);
-  b.cptr.upload(cptr, h->stream);
-  b.ucols.upload(ucols, h->stream);
-  b.lidx.upload(lidx, h->stream);
+  b.cptr.upload(t.cptr, h->stream);
+  b.ucols.upload(t.ucols, h->stream);
+  b.lidx.upload(t.lidx, h->stream);
   if (nsx_debug())
     fprintf(stderr, "[nsx] blocked spmv: rows %d chunks %d (max %d rows; %d of them stage a ghost column: %.1f %% of the non-zeros) unique cols/chunk avg %.0f max %d (nnz/unique %.1f)\n",
             g.n_rows, b.n_chunks, b.max_rows, b.n_chunks_if, 100.0 * b.frac_if, b.ucols_total / std::max(1, b.n_chunks), b.max_ucols, (double)g.nnz() / b.ucols_total);
 }
 
-// Chunk boundaries of the LDS-staged SpMV.  With a rank table the chunks are unions of consecutive rank blocks: a rank's rows
-// are the nodes of one subdomain, so a chunk that ends where a subdomain ends stages fewer columns than one that straddles
-// three subdomains (6.3 instead of 5.5 non-zeros per staged entry at one ~85-row rank per chunk).  Small chunks win: two or
-// three ranks per chunk stage even less (7.9) but measured slower (38 and 43 against 34 us: fewer, longer workgroups).
-// Without a rank table, or with ranks too large for a chunk: a fixed row count.
+// chunk boundaries of the velocity product from the rank table (host/spmv_plan.hpp has the three regimes)
 static std::vector<int32_t> spmv_chunks(nsx_handle *h) {
-  const int n = h->gA.host.n_rows;
   const int target = std::max(16, std::min(448, env_int("NSX_SPMV_R", 130)));
-  std::vector<int32_t> bounds{0};
-  const std::vector<int32_t> &rk = h->rank_u_h;
-  const bool by_rank = env_on("NSX_SPMV_BY_RANK") && rk.size() > 2 &&
-                       (double)n / (double)(rk.size() - 1) <= target;
-  // ranks larger than a chunk (fewer, larger virtual ranks: --ranks 2048 has ~170 rows per block) are cut into equal parts of at most
-  // `target` rows: a chunk still ends where a subdomain ends
-  const bool split_ranks = !by_rank && env_on("NSX_SPMV_BY_RANK") && rk.size() > 2 &&
-                           (double)n / (double)(rk.size() - 1) <= 4.0 * target;
-  if (by_rank) {
-    int start = 0;
-    for (size_t r = 1; r < rk.size(); ++r) {
-      // close the chunk in front of a rank that would take it past the target (a single oversized rank is cut below)
-      if (rk[r] - start > target && rk[r - 1] > start) {
-        bounds.push_back(rk[r - 1]);
-        start = rk[r - 1];
-      }
-    }
-    bounds.push_back(n);
-  } else if (split_ranks) {
-    for (size_t r = 0; r + 1 < rk.size(); ++r) {
-      const int rows = rk[r + 1] - rk[r];
-      if (rows <= 0) continue;
-      const int parts = (rows + target - 1) / target;
-      for (int q = 1; q <= parts; ++q) bounds.push_back(rk[r] + (int)((int64_t)rows * q / parts));
-    }
-    if (bounds.back() != n) bounds.push_back(n);
-  } else {
-    for (int r = 128; r < n; r += 128) bounds.push_back(r);
-    bounds.push_back(n);
-  }
-  // no chunk above 448 rows (the kernel's row-pointer buffer)
-  std::vector<int32_t> out{0};
-  for (size_t c = 1; c < bounds.size(); ++c) {
-    while (bounds[c] - out.back() > 448) out.push_back(out.back() + 224);
-    if (bounds[c] > out.back()) out.push_back(bounds[c]);
-  }
-  return out;
+  return chunk_bounds(h->gA.host.n_rows, h->rank_u_h, target, env_on("NSX_SPMV_BY_RANK"));
 }
 
 void build_schur_graph(nsx_handle *h) {
   // structural product block(1,0) * block(0,1); block(0,1) has the transposed pattern of block(1,0), and block(1,0)
   // is stored for every local (owned + ghost) pressure row, so the product is formed from B and B^T alone
-  const Csr &B = h->gB.host;
-  std::vector<int32_t> tp((size_t)h->N2_loc + 1, 0), tr(B.nnz());
-  for (int64_t k = 0; k < B.nnz(); ++k) tp[B.colind[k] + 1]++;
-  for (int i = 0; i < h->N2_loc; ++i) tp[i + 1] += tp[i];
-  {
-    std::vector<int32_t> fill(tp.begin(), tp.end() - 1);
-    for (int j = 0; j < B.n_rows; ++j)
-      for (int k = B.rowptr[j]; k < B.rowptr[j + 1]; ++k) tr[fill[B.colind[k]]++] = j;
-  }
-  Csr S;
-  S.n_rows = h->NP;
-  S.n_cols = h->NP_loc;
-  S.rowptr.assign((size_t)h->NP + 1, 0);
-  std::vector<int32_t> mark(h->NP_loc, -1), cols;
-  for (int i = 0; i < h->NP; ++i) {
-    cols.clear();
-    for (int kb = B.rowptr[i]; kb < B.rowptr[i + 1]; ++kb) {
-      const int k = B.colind[kb];
-      for (int q = tp[k]; q < tp[k + 1]; ++q) {
-        const int j = tr[q];
-        if (mark[j] != i) {
-          mark[j] = i;
-          cols.push_back(j);
-        }
-      }
-    }
-    std::sort(cols.begin(), cols.end());
-    S.colind.insert(S.colind.end(), cols.begin(), cols.end());
-    S.rowptr[i + 1] = (int32_t)S.colind.size();
-  }
-  h->gS.host = std::move(S);
+  h->gS.host = structural_product(h->gB.host, h->NP, h->NP_loc);
   upload_csr(h, h->gS, true);
   h->vSchur.alloc(h->gS.nnz());
   h->luS.alloc(h->gS.nnz());
@@ -480,28 +247,50 @@ static void perm_launch(nsx_handle *h, int which, double *caller_dev, double *in
   if (n) hipLaunchKernelGGL(k_perm_vec, dim3(cdiv(n, 256)), dim3(256), 0, h->stream, n, ncomp, (which == 0 ? h->perm2_d : h->perm1_d).p, caller_dev, internal_dev, to_internal ? 1 : 0);
 }
 
-void part_from_caller(nsx_handle *h, int which, double *dev, const double *host) {
-  const int n = which == 0 ? h->n_u : h->n_p;
+// n doubles between a host array of the caller and the parts of a device vector, on a single-process handle.  Without a layout the
+// parts are contiguous from parts[0].dev on and take one copy; with one the copy goes through io_stage, where the parts lie one
+// behind the other, and k_perm_vec moves every part.  One synchronisation: host arrays are borrowed for the call only.
+struct IoPart {
+  int which;  // 0 velocity, 1 pressure
+  double *dev;
+};
+
+static void io_from_caller(nsx_handle *h, const double *host, size_t n, std::initializer_list<IoPart> parts) {
   if (!h->layout_on) {
-    HIP_CHECK(hipMemcpyAsync(dev, host, (size_t)n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(hipMemcpyAsync(parts.begin()->dev, host, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
   } else {
     h->io_stage.alloc((size_t)h->n_u + h->n_p);
-    HIP_CHECK(hipMemcpyAsync(h->io_stage.p, host, (size_t)n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    perm_launch(h, which, h->io_stage.p, dev, true);
+    HIP_CHECK(hipMemcpyAsync(h->io_stage.p, host, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    double *stage = h->io_stage.p;
+    for (const IoPart &p : parts) {
+      perm_launch(h, p.which, stage, p.dev, true);
+      stage += p.which == 0 ? h->n_u : h->n_p;
+    }
   }
-  HIP_CHECK(hipStreamSynchronize(h->stream));  // host arrays are borrowed for the call only
+  HIP_CHECK(hipStreamSynchronize(h->stream));
+}
+
+static void io_to_caller(nsx_handle *h, double *host, size_t n, std::initializer_list<IoPart> parts) {
+  if (!h->layout_on) {
+    HIP_CHECK(hipMemcpyAsync(host, parts.begin()->dev, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  } else {
+    h->io_stage.alloc((size_t)h->n_u + h->n_p);
+    double *stage = h->io_stage.p;
+    for (const IoPart &p : parts) {
+      perm_launch(h, p.which, stage, p.dev, false);
+      stage += p.which == 0 ? h->n_u : h->n_p;
+    }
+    HIP_CHECK(hipMemcpyAsync(host, h->io_stage.p, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  }
+  HIP_CHECK(hipStreamSynchronize(h->stream));
+}
+
+void part_from_caller(nsx_handle *h, int which, double *dev, const double *host) {
+  io_from_caller(h, host, which == 0 ? h->n_u : h->n_p, {{which, dev}});
 }
 
 void part_to_caller(nsx_handle *h, int which, const double *dev, double *host) {
-  const int n = which == 0 ? h->n_u : h->n_p;
-  if (!h->layout_on) {
-    HIP_CHECK(hipMemcpyAsync(host, dev, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  } else {
-    h->io_stage.alloc((size_t)h->n_u + h->n_p);
-    perm_launch(h, which, h->io_stage.p, const_cast<double *>(dev), false);
-    HIP_CHECK(hipMemcpyAsync(host, h->io_stage.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  }
-  HIP_CHECK(hipStreamSynchronize(h->stream));
+  io_to_caller(h, host, which == 0 ? h->n_u : h->n_p, {{which, const_cast<double *>(dev)}});
 }
 
 // One pressure vector, any handle.  Single-process: n_p entries in the caller's numbering (part_from_caller).  Distributed: host is
@@ -524,18 +313,7 @@ void pressure_to_caller(nsx_handle *h, const double *dev, double *host) {
 
 void vec_from_caller(nsx_handle *h, double *dev, const double *host, bool with_ghosts) {
   const int dim = h->dim;
-  if (!h->dist) {
-    if (!h->layout_on) {
-      HIP_CHECK(hipMemcpyAsync(dev, host, ((size_t)h->n_u + h->n_p) * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    } else {
-      h->io_stage.alloc((size_t)h->n_u + h->n_p);
-      HIP_CHECK(hipMemcpyAsync(h->io_stage.p, host, ((size_t)h->n_u + h->n_p) * sizeof(double), hipMemcpyHostToDevice, h->stream));
-      perm_launch(h, 0, h->io_stage.p, dev, true);
-      perm_launch(h, 1, h->io_stage.p + h->n_u, dev + h->off_p, true);
-    }
-    HIP_CHECK(hipStreamSynchronize(h->stream));
-    return;
-  }
+  if (!h->dist) return io_from_caller(h, host, (size_t)h->n_u + h->n_p, {{0, dev}, {1, dev + h->off_p}});
   std::vector<double> loc(h->len_blk, 0.0);
   for (int i = 0; i < h->N2; ++i)
     for (int c = 0; c < dim; ++c) loc[(size_t)dim * node_to_internal(h, i) + c] = host[(size_t)dim * (h->goff_u + i) + c];
@@ -551,18 +329,7 @@ void vec_from_caller(nsx_handle *h, double *dev, const double *host, bool with_g
 
 void vec_to_caller(nsx_handle *h, const double *dev, double *host) {
   const int dim = h->dim;
-  if (!h->dist) {
-    if (!h->layout_on) {
-      HIP_CHECK(hipMemcpyAsync(host, dev, ((size_t)h->n_u + h->n_p) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    } else {
-      h->io_stage.alloc((size_t)h->n_u + h->n_p);
-      perm_launch(h, 0, h->io_stage.p, const_cast<double *>(dev), false);
-      perm_launch(h, 1, h->io_stage.p + h->n_u, const_cast<double *>(dev) + h->off_p, false);
-      HIP_CHECK(hipMemcpyAsync(host, h->io_stage.p, ((size_t)h->n_u + h->n_p) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    }
-    HIP_CHECK(hipStreamSynchronize(h->stream));
-    return;
-  }
+  if (!h->dist) return io_to_caller(h, host, (size_t)h->n_u + h->n_p, {{0, const_cast<double *>(dev)}, {1, const_cast<double *>(dev) + h->off_p}});
   std::vector<double> loc(h->len_blk);
   HIP_CHECK(hipMemcpyAsync(loc.data(), dev, loc.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIP_CHECK(hipStreamSynchronize(h->stream));

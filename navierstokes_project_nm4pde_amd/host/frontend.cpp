@@ -1230,60 +1230,120 @@ const int32_t *nsxh_rank_view_send_p_nodes(const nsxh_rank_view *v) { return v->
 }  // extern "C"
 
 // ------------------------------------------------------------------ post-processing (N4: output side of the reference)
+// ---- the VTK text files.  One piece per file, every cell with vertices of its own (NumberOfPoints = cells * vertices), so PointData
+// arrays are written from a value per (cell, vertex).
+namespace {
+
+// <directory>/ made like mkdir -p; the path to put in front of a file name
+std::string output_dir(const char *directory) {
+  std::string dir(directory);
+  if (!dir.empty() && dir.back() != '/') dir += '/';
+  for (size_t pos = 1; pos < dir.size(); ++pos)
+    if (dir[pos] == '/') ::mkdir(dir.substr(0, pos).c_str(), 0777);
+  return dir;
+}
+
+bool open_text(std::ofstream &f, const std::string &path) {
+  f.open(path);
+  f << std::setprecision(17);
+  return (bool)f;
+}
+
+struct VtuPiece {
+  std::ofstream f;
+  const nsxh_dofs *d;
+  int dim, nv, nc;
+
+  // file prologue up to the first PointData array: points, connectivity, offsets, types
+  bool open(const nsxh_dofs *dofs, const std::string &path) {
+    d = dofs;
+    dim = d->dim, nv = dim + 1, nc = d->n_cells;
+    if (!open_text(f, path)) return false;
+    f << "<?xml version=\"1.0\"?>\n<VTKFile type=\"UnstructuredGrid\" version=\"0.1\" byte_order=\"LittleEndian\">\n<UnstructuredGrid>\n"
+      << "<Piece NumberOfPoints=\"" << (int64_t)nc * nv << "\" NumberOfCells=\"" << nc << "\">\n";
+    f << "<Points>\n<DataArray type=\"Float64\" NumberOfComponents=\"3\" format=\"ascii\">\n";
+    for (int c = 0; c < nc; ++c)
+      for (int v = 0; v < nv; ++v) {
+        const double *x = d->cell_coords.data() + ((size_t)c * nv + v) * dim;
+        f << x[0] << ' ' << x[1] << ' ' << (dim == 3 ? x[2] : 0.0) << '\n';
+      }
+    f << "</DataArray>\n</Points>\n<Cells>\n<DataArray type=\"Int32\" Name=\"connectivity\" format=\"ascii\">\n";
+    for (int64_t k = 0; k < (int64_t)nc * nv; ++k) f << k << ((k + 1) % nv ? ' ' : '\n');
+    f << "</DataArray>\n<DataArray type=\"Int32\" Name=\"offsets\" format=\"ascii\">\n";
+    for (int c = 1; c <= nc; ++c) f << (int64_t)c * nv << (c % 16 ? ' ' : '\n');
+    f << "\n</DataArray>\n<DataArray type=\"UInt8\" Name=\"types\" format=\"ascii\">\n";
+    for (int c = 1; c <= nc; ++c) f << (dim == 3 ? 10 : 5) << (c % 32 ? ' ' : '\n');  // VTK_TETRA / VTK_TRIANGLE
+    f << "\n</DataArray>\n</Cells>\n<PointData Scalars=\"scalars\">\n";
+    return true;
+  }
+  // dof `k` of vertex v of cell c (k < dim: velocity component, k == dim: pressure), and the P2 node of the vertex
+  int32_t dof(int c, int v, int k) const { return d->cell_dofs[(size_t)c * d->dpc + (size_t)(dim + 1) * v + k]; }
+  size_t node(int c, int v) const { return (size_t)(dof(c, v, 0) / dim); }
+
+  // One PointData array from value(c, v, k).  ncomp > 0: NumberOfComponents is written and every vertex takes a line;
+  // ncomp == 0: a scalar without the attribute, every cell takes a line.
+  template <class F>
+  void array(const char *name, int ncomp, F value) {
+    f << "<DataArray type=\"Float64\" Name=\"" << name << "\"";
+    if (ncomp) f << " NumberOfComponents=\"" << ncomp << "\"";
+    f << " format=\"ascii\">\n";
+    for (int c = 0; c < nc; ++c)
+      for (int v = 0; v < nv; ++v) {
+        for (int k = 0; k + 1 < ncomp; ++k) f << value(c, v, k) << ' ';
+        f << value(c, v, std::max(ncomp, 1) - 1) << (ncomp || v + 1 == nv ? '\n' : ' ');
+      }
+    f << "</DataArray>\n";
+  }
+  // a vector of the mesh's dimension per P2 node as three components, the third 0 in 2D
+  void vector3(const char *name, const double *a) {
+    array(name, 3, [&](int c, int v, int k) { return k < dim ? a[node(c, v) * dim + k] : 0.0; });
+  }
+  void partitioning() {
+    const int32_t *sub = d->mesh->subdomain.empty() ? nullptr : d->mesh->subdomain.data();
+    array("partitioning", 0, [&](int c, int, int) { return sub ? sub[c] : 0; });
+  }
+  bool close() {
+    f << "</PointData>\n</Piece>\n</UnstructuredGrid>\n</VTKFile>\n";
+    f.close();
+    return (bool)f;
+  }
+};
+
+// the .pvtu that names one piece and its arrays: (name, components), 0 components = a scalar without the attribute
+bool write_pvtu(const std::string &path, const std::string &piece, std::initializer_list<std::pair<const char *, int>> arrays) {
+  std::ofstream pv(path);
+  if (!pv) return false;
+  pv << "<?xml version=\"1.0\"?>\n<VTKFile type=\"PUnstructuredGrid\" version=\"0.1\" byte_order=\"LittleEndian\">\n"
+     << "<PUnstructuredGrid GhostLevel=\"0\">\n<PPointData Scalars=\"scalars\">\n";
+  for (const auto &a : arrays) {
+    pv << "<PDataArray type=\"Float64\" Name=\"" << a.first << "\"";
+    if (a.second) pv << " NumberOfComponents=\"" << a.second << "\"";
+    pv << " format=\"ascii\"/>\n";
+  }
+  pv << "</PPointData>\n<PPoints>\n<PDataArray type=\"Float64\" NumberOfComponents=\"3\"/>\n</PPoints>\n"
+     << "<Piece Source=\"" << piece << "\"/>\n</PUnstructuredGrid>\n</VTKFile>\n";
+  return (bool)pv;
+}
+
+// velocity, pressure and partitioning of a solution vector: what nsxh_write_vtu and nsxh_write_vtu_fields share
+void solution_arrays(VtuPiece &p, const double *solution) {
+  p.array("velocity", 3, [&](int c, int v, int k) { return k < p.dim ? solution[p.dof(c, v, k)] : 0.0; });
+  p.array("pressure", 0, [&](int c, int v, int) { return solution[p.dof(c, v, p.dim)]; });
+  p.partitioning();
+}
+
+}  // namespace
+
 extern "C" {
 
 int nsxh_write_vtu(const nsxh_dofs *d, const double *solution, const char *directory, const char *basename, unsigned counter) {
   if (!d || !solution || !directory || !basename) return -1;
-  const int dim = d->dim, nv = dim + 1, nc = d->n_cells;
-  std::string dir(directory);
-  if (!dir.empty() && dir.back() != '/') dir += '/';
-  for (size_t pos = 1; pos < dir.size(); ++pos)  // mkdir -p
-    if (dir[pos] == '/') ::mkdir(dir.substr(0, pos).c_str(), 0777);
-  const std::string stem = std::string(basename) + "_" + std::to_string(counter);
-  const std::string piece = stem + ".0.vtu";
-  std::ofstream f(dir + piece);
-  if (!f) return -1;
-  f << std::setprecision(17);
-  const int32_t *sub = d->mesh->subdomain.empty() ? nullptr : d->mesh->subdomain.data();
-  f << "<?xml version=\"1.0\"?>\n<VTKFile type=\"UnstructuredGrid\" version=\"0.1\" byte_order=\"LittleEndian\">\n<UnstructuredGrid>\n"
-    << "<Piece NumberOfPoints=\"" << (int64_t)nc * nv << "\" NumberOfCells=\"" << nc << "\">\n";
-  f << "<Points>\n<DataArray type=\"Float64\" NumberOfComponents=\"3\" format=\"ascii\">\n";
-  for (int c = 0; c < nc; ++c)
-    for (int v = 0; v < nv; ++v) {
-      const double *x = d->cell_coords.data() + ((size_t)c * nv + v) * dim;
-      f << x[0] << ' ' << x[1] << ' ' << (dim == 3 ? x[2] : 0.0) << '\n';
-    }
-  f << "</DataArray>\n</Points>\n<Cells>\n<DataArray type=\"Int32\" Name=\"connectivity\" format=\"ascii\">\n";
-  for (int64_t k = 0; k < (int64_t)nc * nv; ++k) f << k << ((k + 1) % nv ? ' ' : '\n');
-  f << "</DataArray>\n<DataArray type=\"Int32\" Name=\"offsets\" format=\"ascii\">\n";
-  for (int c = 1; c <= nc; ++c) f << (int64_t)c * nv << (c % 16 ? ' ' : '\n');
-  f << "\n</DataArray>\n<DataArray type=\"UInt8\" Name=\"types\" format=\"ascii\">\n";
-  for (int c = 1; c <= nc; ++c) f << (dim == 3 ? 10 : 5) << (c % 32 ? ' ' : '\n');  // VTK_TETRA / VTK_TRIANGLE
-  f << "\n</DataArray>\n</Cells>\n<PointData Scalars=\"scalars\">\n";
-  f << "<DataArray type=\"Float64\" Name=\"velocity\" NumberOfComponents=\"3\" format=\"ascii\">\n";
-  for (int c = 0; c < nc; ++c)
-    for (int v = 0; v < nv; ++v) {
-      const int32_t *cd = d->cell_dofs.data() + (size_t)c * d->dpc + (size_t)(dim + 1) * v;
-      f << solution[cd[0]] << ' ' << solution[cd[1]] << ' ' << (dim == 3 ? solution[cd[2]] : 0.0) << '\n';
-    }
-  f << "</DataArray>\n<DataArray type=\"Float64\" Name=\"pressure\" format=\"ascii\">\n";
-  for (int c = 0; c < nc; ++c)
-    for (int v = 0; v < nv; ++v) f << solution[d->cell_dofs[(size_t)c * d->dpc + (size_t)(dim + 1) * v + dim]] << (v + 1 == nv ? '\n' : ' ');
-  f << "</DataArray>\n<DataArray type=\"Float64\" Name=\"partitioning\" format=\"ascii\">\n";
-  for (int c = 0; c < nc; ++c)
-    for (int v = 0; v < nv; ++v) f << (sub ? sub[c] : 0) << (v + 1 == nv ? '\n' : ' ');
-  f << "</DataArray>\n</PointData>\n</Piece>\n</UnstructuredGrid>\n</VTKFile>\n";
-  f.close();
-  std::ofstream pv(dir + stem + ".pvtu");
-  if (!pv) return -1;
-  pv << "<?xml version=\"1.0\"?>\n<VTKFile type=\"PUnstructuredGrid\" version=\"0.1\" byte_order=\"LittleEndian\">\n"
-     << "<PUnstructuredGrid GhostLevel=\"0\">\n<PPointData Scalars=\"scalars\">\n"
-     << "<PDataArray type=\"Float64\" Name=\"velocity\" NumberOfComponents=\"3\" format=\"ascii\"/>\n"
-     << "<PDataArray type=\"Float64\" Name=\"pressure\" format=\"ascii\"/>\n"
-     << "<PDataArray type=\"Float64\" Name=\"partitioning\" format=\"ascii\"/>\n</PPointData>\n"
-     << "<PPoints>\n<PDataArray type=\"Float64\" NumberOfComponents=\"3\"/>\n</PPoints>\n"
-     << "<Piece Source=\"" << piece << "\"/>\n</PUnstructuredGrid>\n</VTKFile>\n";
-  return pv ? 0 : -1;
+  const std::string dir = output_dir(directory), stem = std::string(basename) + "_" + std::to_string(counter), piece = stem + ".0.vtu";
+  VtuPiece p;
+  if (!p.open(d, dir + piece)) return -1;
+  solution_arrays(p, solution);
+  p.close();
+  return write_pvtu(dir + stem + ".pvtu", piece, {{"velocity", 3}, {"pressure", 0}, {"partitioning", 0}}) ? 0 : -1;
 }
 
 // nsxh_write_vtu's files with two more PointData arrays behind "partitioning": "vorticity" and "q_criterion", taken at the cell vertices from
@@ -1292,67 +1352,14 @@ int nsxh_write_vtu(const nsxh_dofs *d, const double *solution, const char *direc
 int nsxh_write_vtu_fields(const nsxh_dofs *d, const double *solution, const double *vorticity, int n_vorticity, const double *q_criterion,
                           const char *directory, const char *basename, unsigned counter) {
   if (!d || !solution || !vorticity || !q_criterion || !directory || !basename || (n_vorticity != 1 && n_vorticity != 3)) return -1;
-  const int dim = d->dim, nv = dim + 1, nc = d->n_cells;
-  std::string dir(directory);
-  if (!dir.empty() && dir.back() != '/') dir += '/';
-  for (size_t pos = 1; pos < dir.size(); ++pos)  // mkdir -p
-    if (dir[pos] == '/') ::mkdir(dir.substr(0, pos).c_str(), 0777);
-  const std::string stem = std::string(basename) + "_" + std::to_string(counter);
-  const std::string piece = stem + ".0.vtu";
-  std::ofstream f(dir + piece);
-  if (!f) return -1;
-  f << std::setprecision(17);
-  const int32_t *sub = d->mesh->subdomain.empty() ? nullptr : d->mesh->subdomain.data();
-  f << "<?xml version=\"1.0\"?>\n<VTKFile type=\"UnstructuredGrid\" version=\"0.1\" byte_order=\"LittleEndian\">\n<UnstructuredGrid>\n"
-    << "<Piece NumberOfPoints=\"" << (int64_t)nc * nv << "\" NumberOfCells=\"" << nc << "\">\n";
-  f << "<Points>\n<DataArray type=\"Float64\" NumberOfComponents=\"3\" format=\"ascii\">\n";
-  for (int c = 0; c < nc; ++c)
-    for (int v = 0; v < nv; ++v) {
-      const double *x = d->cell_coords.data() + ((size_t)c * nv + v) * dim;
-      f << x[0] << ' ' << x[1] << ' ' << (dim == 3 ? x[2] : 0.0) << '\n';
-    }
-  f << "</DataArray>\n</Points>\n<Cells>\n<DataArray type=\"Int32\" Name=\"connectivity\" format=\"ascii\">\n";
-  for (int64_t k = 0; k < (int64_t)nc * nv; ++k) f << k << ((k + 1) % nv ? ' ' : '\n');
-  f << "</DataArray>\n<DataArray type=\"Int32\" Name=\"offsets\" format=\"ascii\">\n";
-  for (int c = 1; c <= nc; ++c) f << (int64_t)c * nv << (c % 16 ? ' ' : '\n');
-  f << "\n</DataArray>\n<DataArray type=\"UInt8\" Name=\"types\" format=\"ascii\">\n";
-  for (int c = 1; c <= nc; ++c) f << (dim == 3 ? 10 : 5) << (c % 32 ? ' ' : '\n');  // VTK_TETRA / VTK_TRIANGLE
-  f << "\n</DataArray>\n</Cells>\n<PointData Scalars=\"scalars\">\n";
-  f << "<DataArray type=\"Float64\" Name=\"velocity\" NumberOfComponents=\"3\" format=\"ascii\">\n";
-  for (int c = 0; c < nc; ++c)
-    for (int v = 0; v < nv; ++v) {
-      const int32_t *cd = d->cell_dofs.data() + (size_t)c * d->dpc + (size_t)(dim + 1) * v;
-      f << solution[cd[0]] << ' ' << solution[cd[1]] << ' ' << (dim == 3 ? solution[cd[2]] : 0.0) << '\n';
-    }
-  f << "</DataArray>\n<DataArray type=\"Float64\" Name=\"pressure\" format=\"ascii\">\n";
-  for (int c = 0; c < nc; ++c)
-    for (int v = 0; v < nv; ++v) f << solution[d->cell_dofs[(size_t)c * d->dpc + (size_t)(dim + 1) * v + dim]] << (v + 1 == nv ? '\n' : ' ');
-  f << "</DataArray>\n<DataArray type=\"Float64\" Name=\"partitioning\" format=\"ascii\">\n";
-  for (int c = 0; c < nc; ++c)
-    for (int v = 0; v < nv; ++v) f << (sub ? sub[c] : 0) << (v + 1 == nv ? '\n' : ' ');
-  f << "</DataArray>\n<DataArray type=\"Float64\" Name=\"vorticity\" NumberOfComponents=\"" << n_vorticity << "\" format=\"ascii\">\n";
-  for (int c = 0; c < nc; ++c)
-    for (int v = 0; v < nv; ++v) {
-      const size_t node = (size_t)(d->cell_dofs[(size_t)c * d->dpc + (size_t)(dim + 1) * v] / dim);
-      for (int k = 0; k < n_vorticity; ++k) f << vorticity[node * n_vorticity + k] << (k + 1 == n_vorticity ? '\n' : ' ');
-    }
-  f << "</DataArray>\n<DataArray type=\"Float64\" Name=\"q_criterion\" format=\"ascii\">\n";
-  for (int c = 0; c < nc; ++c)
-    for (int v = 0; v < nv; ++v) f << q_criterion[d->cell_dofs[(size_t)c * d->dpc + (size_t)(dim + 1) * v] / dim] << (v + 1 == nv ? '\n' : ' ');
-  f << "</DataArray>\n</PointData>\n</Piece>\n</UnstructuredGrid>\n</VTKFile>\n";
-  f.close();
-  std::ofstream pv(dir + stem + ".pvtu");
-  if (!pv) return -1;
-  pv << "<?xml version=\"1.0\"?>\n<VTKFile type=\"PUnstructuredGrid\" version=\"0.1\" byte_order=\"LittleEndian\">\n"
-     << "<PUnstructuredGrid GhostLevel=\"0\">\n<PPointData Scalars=\"scalars\">\n"
-     << "<PDataArray type=\"Float64\" Name=\"velocity\" NumberOfComponents=\"3\" format=\"ascii\"/>\n"
-     << "<PDataArray type=\"Float64\" Name=\"pressure\" format=\"ascii\"/>\n"
-     << "<PDataArray type=\"Float64\" Name=\"partitioning\" format=\"ascii\"/>\n"
-     << "<PDataArray type=\"Float64\" Name=\"vorticity\" NumberOfComponents=\"" << n_vorticity << "\" format=\"ascii\"/>\n"
-     << "<PDataArray type=\"Float64\" Name=\"q_criterion\" format=\"ascii\"/>\n</PPointData>\n"
-     << "<PPoints>\n<PDataArray type=\"Float64\" NumberOfComponents=\"3\"/>\n</PPoints>\n"
-     << "<Piece Source=\"" << piece << "\"/>\n</PUnstructuredGrid>\n</VTKFile>\n";
-  return pv ? 0 : -1;
+  const std::string dir = output_dir(directory), stem = std::string(basename) + "_" + std::to_string(counter), piece = stem + ".0.vtu";
+  VtuPiece p;
+  if (!p.open(d, dir + piece)) return -1;
+  solution_arrays(p, solution);
+  p.array("vorticity", n_vorticity, [&](int c, int v, int k) { return vorticity[p.node(c, v) * n_vorticity + k]; });
+  p.array("q_criterion", 0, [&](int c, int v, int) { return q_criterion[p.node(c, v)]; });
+  p.close();
+  return write_pvtu(dir + stem + ".pvtu", piece, {{"velocity", 3}, {"pressure", 0}, {"partitioning", 0}, {"vorticity", n_vorticity}, {"q_criterion", 0}}) ? 0 : -1;
 }
 
 // The running statistics on the mesh of nsxh_write_vtu, <directory>/<basename>.vtu: the arrays of nsx_stats_get (indexed by P2 node; the mean
@@ -1360,62 +1367,21 @@ int nsxh_write_vtu_fields(const nsxh_dofs *d, const double *solution, const doub
 int nsxh_write_vtu_stats(const nsxh_dofs *d, const double *mean_u, const double *mean_p, const double *rms_u, const double *stress, const double *tke,
                          const char *directory, const char *basename) {
   if (!d || !mean_u || !mean_p || !rms_u || !stress || !tke || !directory || !basename) return -1;
-  const int dim = d->dim, nv = dim + 1, nc = d->n_cells, nsym = dim * (dim + 1) / 2;
-  std::string dir(directory);
-  if (!dir.empty() && dir.back() != '/') dir += '/';
-  for (size_t pos = 1; pos < dir.size(); ++pos)  // mkdir -p
-    if (dir[pos] == '/') ::mkdir(dir.substr(0, pos).c_str(), 0777);
-  std::ofstream f(dir + basename + ".vtu");
-  if (!f) return -1;
-  f << std::setprecision(17);
-  const int32_t *sub = d->mesh->subdomain.empty() ? nullptr : d->mesh->subdomain.data();
-  auto node = [&](int c, int v) { return (size_t)(d->cell_dofs[(size_t)c * d->dpc + (size_t)(dim + 1) * v] / dim); };
-  auto vector3 = [&](const char *name, const double *a) {
-    f << "<DataArray type=\"Float64\" Name=\"" << name << "\" NumberOfComponents=\"3\" format=\"ascii\">\n";
-    for (int c = 0; c < nc; ++c)
-      for (int v = 0; v < nv; ++v) {
-        const double *x = a + node(c, v) * dim;
-        f << x[0] << ' ' << x[1] << ' ' << (dim == 3 ? x[2] : 0.0) << '\n';
-      }
-    f << "</DataArray>\n";
-  };
-  f << "<?xml version=\"1.0\"?>\n<VTKFile type=\"UnstructuredGrid\" version=\"0.1\" byte_order=\"LittleEndian\">\n<UnstructuredGrid>\n"
-    << "<Piece NumberOfPoints=\"" << (int64_t)nc * nv << "\" NumberOfCells=\"" << nc << "\">\n";
-  f << "<Points>\n<DataArray type=\"Float64\" NumberOfComponents=\"3\" format=\"ascii\">\n";
-  for (int c = 0; c < nc; ++c)
-    for (int v = 0; v < nv; ++v) {
-      const double *x = d->cell_coords.data() + ((size_t)c * nv + v) * dim;
-      f << x[0] << ' ' << x[1] << ' ' << (dim == 3 ? x[2] : 0.0) << '\n';
-    }
-  f << "</DataArray>\n</Points>\n<Cells>\n<DataArray type=\"Int32\" Name=\"connectivity\" format=\"ascii\">\n";
-  for (int64_t k = 0; k < (int64_t)nc * nv; ++k) f << k << ((k + 1) % nv ? ' ' : '\n');
-  f << "</DataArray>\n<DataArray type=\"Int32\" Name=\"offsets\" format=\"ascii\">\n";
-  for (int c = 1; c <= nc; ++c) f << (int64_t)c * nv << (c % 16 ? ' ' : '\n');
-  f << "\n</DataArray>\n<DataArray type=\"UInt8\" Name=\"types\" format=\"ascii\">\n";
-  for (int c = 1; c <= nc; ++c) f << (dim == 3 ? 10 : 5) << (c % 32 ? ' ' : '\n');  // VTK_TETRA / VTK_TRIANGLE
-  f << "\n</DataArray>\n</Cells>\n<PointData Scalars=\"scalars\">\n";
-  vector3("mean_velocity", mean_u);
-  f << "<DataArray type=\"Float64\" Name=\"mean_pressure\" format=\"ascii\">\n";
-  for (int c = 0; c < nc; ++c)
-    for (int v = 0; v < nv; ++v) f << mean_p[d->cell_dofs[(size_t)c * d->dpc + (size_t)(dim + 1) * v + dim] - d->n2 * dim] << (v + 1 == nv ? '\n' : ' ');
-  f << "</DataArray>\n";
-  vector3("rms_velocity", rms_u);
-  f << "<DataArray type=\"Float64\" Name=\"reynolds_stress\" NumberOfComponents=\"6\" format=\"ascii\">\n";
-  for (int c = 0; c < nc; ++c)
-    for (int v = 0; v < nv; ++v) {
-      const double *s = stress + node(c, v) * nsym;  // xx, yy, [zz,] xy[, xz, yz] -> XX YY ZZ XY YZ XZ
-      if (dim == 3) f << s[0] << ' ' << s[1] << ' ' << s[2] << ' ' << s[3] << ' ' << s[5] << ' ' << s[4] << '\n';
-      else f << s[0] << ' ' << s[1] << " 0 " << s[2] << " 0 0\n";
-    }
-  f << "</DataArray>\n<DataArray type=\"Float64\" Name=\"tke\" format=\"ascii\">\n";
-  for (int c = 0; c < nc; ++c)
-    for (int v = 0; v < nv; ++v) f << tke[node(c, v)] << (v + 1 == nv ? '\n' : ' ');
-  f << "</DataArray>\n<DataArray type=\"Float64\" Name=\"partitioning\" format=\"ascii\">\n";
-  for (int c = 0; c < nc; ++c)
-    for (int v = 0; v < nv; ++v) f << (sub ? sub[c] : 0) << (v + 1 == nv ? '\n' : ' ');
-  f << "</DataArray>\n</PointData>\n</Piece>\n</UnstructuredGrid>\n</VTKFile>\n";
-  f.close();
-  return f ? 0 : -1;
+  const int dim = d->dim, nsym = dim * (dim + 1) / 2;
+  VtuPiece p;
+  if (!p.open(d, output_dir(directory) + basename + ".vtu")) return -1;
+  p.vector3("mean_velocity", mean_u);
+  p.array("mean_pressure", 0, [&](int c, int v, int) { return mean_p[p.dof(c, v, dim) - d->n2 * dim]; });
+  p.vector3("rms_velocity", rms_u);
+  // stored xx, yy, [zz,] xy[, xz, yz]; written XX YY ZZ XY YZ XZ, what 2D does not have as 0
+  static const int from3[6] = {0, 1, 2, 3, 5, 4}, from2[6] = {0, 1, -1, 2, -1, -1};
+  p.array("reynolds_stress", 6, [&](int c, int v, int k) {
+    const int s = (dim == 3 ? from3 : from2)[k];
+    return s < 0 ? 0.0 : stress[p.node(c, v) * nsym + s];
+  });
+  p.array("tke", 0, [&](int c, int v, int) { return tke[p.node(c, v)]; });
+  p.partitioning();
+  return p.close() ? 0 : -1;
 }
 
 // A lattice of nsx_set_lattice as VTK ImageData, <directory>/<basename>_<counter>.vti: the planes of nsx_get_lattice as PointData -- "velocity"
@@ -1429,13 +1395,8 @@ int nsxh_write_vti(int dim, const double *origin, const double *spacing, const i
     if (counts[d] < 1) return -1;
     n *= (size_t)counts[d];
   }
-  std::string dir(directory);
-  if (!dir.empty() && dir.back() != '/') dir += '/';
-  for (size_t pos = 1; pos < dir.size(); ++pos)  // mkdir -p
-    if (dir[pos] == '/') ::mkdir(dir.substr(0, pos).c_str(), 0777);
-  std::ofstream f(dir + std::string(basename) + "_" + std::to_string(counter) + ".vti");
-  if (!f) return -1;
-  f << std::setprecision(17);
+  std::ofstream f;
+  if (!open_text(f, output_dir(directory) + basename + "_" + std::to_string(counter) + ".vti")) return -1;
   f << "<?xml version=\"1.0\"?>\n<VTKFile type=\"ImageData\" version=\"0.1\" byte_order=\"LittleEndian\">\n<ImageData WholeExtent=\"";
   for (int d = 0; d < 3; ++d) f << "0 " << (d < dim ? counts[d] - 1 : 0) << (d < 2 ? " " : "\" Origin=\"");
   for (int d = 0; d < 3; ++d) f << (d < dim ? origin[d] : 0.0) << (d < 2 ? " " : "\" Spacing=\"");

@@ -70,4 +70,45 @@ inline int32_t find_in_row(const Csr &g, int32_t i, int32_t j) {
   return (p != e && *p == j) ? (int32_t)(p - g.colind.data()) : -1;
 }
 
+// pattern of B^T: row k (a column of B, n_cols of them) lists the rows of B that hold k, ascending
+inline Csr transpose_pattern(const Csr &B, int32_t n_cols) {
+  Csr t;
+  t.n_rows = n_cols;
+  t.n_cols = B.n_rows;
+  t.rowptr.assign((size_t)n_cols + 1, 0);
+  t.colind.resize(B.nnz());
+  for (int64_t k = 0; k < B.nnz(); ++k) t.rowptr[B.colind[k] + 1]++;
+  for (int32_t i = 0; i < n_cols; ++i) t.rowptr[i + 1] += t.rowptr[i];
+  std::vector<int32_t> fill(t.rowptr.begin(), t.rowptr.end() - 1);
+  for (int32_t j = 0; j < B.n_rows; ++j)
+    for (int32_t k = B.rowptr[j]; k < B.rowptr[j + 1]; ++k) t.colind[fill[B.colind[k]]++] = j;
+  return t;
+}
+
+// Pattern of B * B^T (EpetraExt::MatrixMatrix::Multiply, structural): rows [0, n_rows) of B against all its n_cols >= n_rows rows,
+// columns sorted.  B may hold more rows than the product (ghost rows behind the owned ones).
+inline Csr structural_product(const Csr &B, int32_t n_rows, int32_t n_cols) {
+  const Csr t = transpose_pattern(B, B.n_cols);
+  Csr S;
+  S.n_rows = n_rows;
+  S.n_cols = n_cols;
+  S.rowptr.assign((size_t)n_rows + 1, 0);
+  std::vector<int32_t> mark(n_cols, -1), cols;
+  for (int32_t i = 0; i < n_rows; ++i) {
+    cols.clear();
+    for (int32_t kb = B.rowptr[i]; kb < B.rowptr[i + 1]; ++kb)
+      for (int32_t q = t.rowptr[B.colind[kb]]; q < t.rowptr[B.colind[kb] + 1]; ++q) {
+        const int32_t j = t.colind[q];
+        if (mark[j] != i) {
+          mark[j] = i;
+          cols.push_back(j);
+        }
+      }
+    std::sort(cols.begin(), cols.end());
+    S.colind.insert(S.colind.end(), cols.begin(), cols.end());
+    S.rowptr[i + 1] = (int32_t)S.colind.size();
+  }
+  return S;
+}
+
 }  // namespace nsx
