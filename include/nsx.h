@@ -200,6 +200,29 @@ int nsx_inner_F_vmult(nsx_handle *h, double *dst, const double *src);
  * handles: length n_p of the whole mesh, globally indexed as for nsx_system_vmult; every rank calls, only the owned entries of b and x
  * are read and only the owned entries of x are written.  After nsx_prec_initialize (otherwise the usual call-order NSX_ERR_ARG). */
 int nsx_schur_cg(nsx_handle *h, double rtol, int maxiter, double *x, const double *b, int *steps, double *last_residual, int *status);
+/* Test hook: ONE SolverGMRES solve of an inner system on the caller's vectors, by the very call sites the preconditioners' vmult uses
+ * (gmres() in csrc/nsx_solve.hip: Arnoldi with the Gram-Schmidt sweep, SolverGMRES' re-orthogonalisation test on every fifth iteration,
+ * Givens rotations, restart after 28 iterations, and the seams of NSX_STEP_FUSED).
+ *   system  NSX_GMRES_F   F in the handle's inner precision with the velocity ILU(0), vectors of length n_u   (Preconditioners.hpp:173,273,382,405)
+ *           NSX_GMRES_S   negative_S_tilde with its ILU(0), vectors of length n_p (aSIMPLE, :287-289); modes PLAIN and FUSED_GUESS only
+ *   mode    NSX_GMRES_PLAIN           x = the guess; tolerance tol * |b|, |b| through a reduction and a host round trip of its own
+ *           NSX_GMRES_FUSED_GUESS     the same solve with |b|^2 collected together with the first residual norm and the residual of a cycle
+ *                                     from the product's own launch
+ *           NSX_GMRES_FUSED_FROM_X0   x = the guess, handed to the solver in a vector of its own: x itself is only written (by the first
+ *                                     update, x = x0 + sum; if the guess converges as it stands, by a copy: info[2] = 0)
+ *           NSX_GMRES_ZERO            x is zeroed and the solver told so (the first residual is b)
+ *           NSX_GMRES_FUSED_ZERO_NEG  the solver told that x is zero WITHOUT x being zeroed; if the solve ends in its first cycle, the update
+ *                                     is neg_out = -neg_out + x without x ever being stored (info[3] = 1, x comes back as it went in);
+ *                                     else x holds the solution (info[2] = 1, neg_out untouched)
+ *           | NSX_GMRES_ABS_TOL       (PLAIN, ZERO) tol is the tolerance itself: tol = 0 with maxiter = k pins iterate k (the fused modes take
+ *                                     tol * |b| on the device; tol = 0 pins there too)
+ * info[0] steps, [1] status (0 converged, 1 not), [2] x_written, [3] neg_done; last_residual as SolverControl leaves it: the estimate
+ * |gamma| inside a cycle, the true preconditioned residual at a restart.  Single-process handles (with or without a 1-rank communicator), in
+ * the caller's numbering; distributed handles are not supported (NSX_ERR_UNSUPPORTED).  After nsx_prec_initialize. */
+enum { NSX_GMRES_F = 0, NSX_GMRES_S = 1 };
+enum { NSX_GMRES_PLAIN = 0, NSX_GMRES_FUSED_GUESS, NSX_GMRES_FUSED_FROM_X0, NSX_GMRES_ZERO, NSX_GMRES_FUSED_ZERO_NEG, NSX_GMRES_ABS_TOL = 256 };
+int nsx_gmres(nsx_handle *h, int system, int mode, double tol, int maxiter, double *x, const double *b, double *neg_out, int info[4],
+              double *last_residual);
 /* Test hook: ONE sparse product of the solver on the caller's vectors, by the very function the solver calls (csrc/nsx_sparse.hip), so
  * that each product kernel can be compared with a reference on its own (tests/test_gpu_sparse.py).  dst, src and aux are host vectors of
  * length n_u + n_p of the whole mesh, globally indexed exactly as for nsx_system_vmult; x_u / x_p are the velocity / pressure part of src.
@@ -680,6 +703,61 @@ int nsx_gram_schmidt_cycle(nsx_handle *h, int n, int m, double *vectors, double 
  * 1 / sqrt(norms2[k]) afterwards ([0] = 0: vector 0 is always scaled by the hook).  coeffs, norms2, norm_guard, m <= 30: as above. */
 int nsx_gram_schmidt_sweeps(nsx_handle *h, int n, int split, int gap, int m, double *vectors, double norm_guard, int flags, double *coeffs,
                             double *norms2, double *norms2_before, int *normalized);
+
+/* Test hook: a short PROGRAM of the Krylov drivers' BLAS-1 operations (csrc/nsx_blas.hip, v_reciprocal of csrc/nsx_solve.hip) on the
+ * caller's vectors, every op by the very host function the solvers call -- so that a reduction followed by a consumer that sums its
+ * partial sums, with or without a finalisation in between, can be compared with a reference on its own (tests/test_gpu_blas1.py).
+ * vectors[m][n + gap] is in the device layout of a block vector as for nsx_gram_schmidt_sweeps (logical entry i at
+ * i + (i >= split ? gap : 0); 0 <= split <= n; split == n needs gap == 0); the gap entries are uploaded and downloaded as they are.
+ * The ops run in order on the handle's stream; out[i] is the value of op i's result slot if its `read` flag is set (read through
+ * read_scalars: the slot is final afterwards), else 0.  NSX_BLAS1_READ publishes `count` slots from `slot` on; its values are appended
+ * to scalars_out (capacity scalars_cap doubles; more is NSX_ERR_ARG) and out[i] is the first of them.
+ * Vector indices address rows of `vectors` (-1 = none, only where the table says so); slots are the solvers' scalar slots 0 .. 126; `num`
+ * / `den` = -1 where the op takes none.  The ops with a plain length (no span) need gap == 0 or a length `n` of their own: an op with
+ * n > 0 runs on the first n <= split entries of its vectors alone (a short reduction into a slot a long one has left its partial sums in).
+ *   kind                      host function            fields
+ *   NSX_BLAS1_DOT             v_dot                    slot = d . w
+ *   NSX_BLAS1_ADD_AND_DOT     v_add_and_dot            d += a value(num) v ; slot = d . w   (w == d: the kernel's self branch)
+ *   NSX_BLAS1_ADD             v_add                    d += a v
+ *   NSX_BLAS1_ADD_DEV         v_add_dev                d += a value(num) v
+ *   NSX_BLAS1_SADD            v_sadd                   d = s d + a v
+ *   NSX_BLAS1_SCALE           v_scale                  d *= a
+ *   NSX_BLAS1_SCALE_DEV_INV   v_scale_dev_inv          d *= 1 / value(den)
+ *   NSX_BLAS1_SCALE_VEC       v_scale_vec              d[i] *= v[i]                          (plain length)
+ *   NSX_BLAS1_AXPY_MULTI      v_axpy_multi             d += sum_j coef[j] vectors[vs[j]], j < k <= 40 (above 32: two launches)
+ *   NSX_BLAS1_AXPY_MULTI_INTO v_axpy_multi_into        d = (v >= 0 ? v : 0) + sum_j ..., then d = -w + d if w >= 0 (w may be d).
+ *                                                      k > 32, or v >= 0 together with w >= 0: the library's own NSX_ERR_ARG
+ *   NSX_BLAS1_CG_UPDATE       cg_update                d += alpha v ; w += alpha x ; slot = w . w, alpha = value(num) / value(den)   (plain length)
+ *   NSX_BLAS1_CG_DIRECTION    cg_direction             d = (value(num) / value(den)) d - v   (plain length)
+ *   NSX_BLAS1_RECIPROCAL      v_reciprocal             d[i] = a / v[i]                        (plain length)
+ *   NSX_BLAS1_FINALIZE        finalize_slots           slots slot .. slot + count - 1 become final (count > 64: NSX_ERR_ARG)
+ *   NSX_BLAS1_READ            read_scalars             as above (count > 64: the library's own NSX_ERR_ARG)
+ *   NSX_BLAS1_WRITE_SCALAR    write_scalar             slot = a
+ * A coefficient a value(num) / value(den) is evaluated on the device from the slots as they are: still spread over the partial sums of the
+ * reduction that wrote them, or final.  The hook leaves nothing behind: every slot counts as final again when it returns (also after an
+ * error), so a program never sees the state of an earlier one.  Single-process handles, with or without a 1-rank communicator (which
+ * forces the fixed grid of 256 partial sums per reduction; a distributed handle: NSX_ERR_UNSUPPORTED, as nsx_gmres); any time after
+ * nsx_set_mesh. */
+enum {
+  NSX_BLAS1_DOT = 0, NSX_BLAS1_ADD_AND_DOT, NSX_BLAS1_ADD, NSX_BLAS1_ADD_DEV, NSX_BLAS1_SADD, NSX_BLAS1_SCALE, NSX_BLAS1_SCALE_DEV_INV,
+  NSX_BLAS1_SCALE_VEC, NSX_BLAS1_AXPY_MULTI, NSX_BLAS1_AXPY_MULTI_INTO, NSX_BLAS1_CG_UPDATE, NSX_BLAS1_CG_DIRECTION, NSX_BLAS1_RECIPROCAL,
+  NSX_BLAS1_FINALIZE, NSX_BLAS1_READ, NSX_BLAS1_WRITE_SCALAR, NSX_BLAS1_KIND_COUNT
+};
+#define NSX_BLAS1_MAX_K 40
+typedef struct nsx_blas1_op {
+  int32_t kind;                 /* NSX_BLAS1_* */
+  int32_t d, v, w, x;           /* vector indices */
+  int32_t slot, num, den;       /* result slot; slots of the coefficient's numerator and denominator */
+  int32_t count;                /* FINALIZE, READ: length of the slot range */
+  int32_t read;                 /* != 0: read the result slot now (out[i]) */
+  int32_t n;                    /* 0: the op runs on the program's span; > 0: on the first n entries alone, a plain length (n <= split) */
+  int32_t k;                    /* multi-axpy: number of terms */
+  int32_t vs[NSX_BLAS1_MAX_K];  /* ... their vectors */
+  double a, s;                  /* host coefficients */
+  double coef[NSX_BLAS1_MAX_K]; /* multi-axpy: coefficients */
+} nsx_blas1_op;
+int nsx_blas1_run(nsx_handle *h, int n, int split, int gap, int m, double *vectors, int n_ops, const nsx_blas1_op *ops, double *out,
+                  double *scalars_out, int scalars_cap);
 
 /* ---- multi-GPU (one process per GPU, RCCL over xGMI) ---- */
 /* Replaces the MPI communicator inside Epetra (reference NavierStokes3D.hpp:93-94,102): MPI_Allreduce behind every

@@ -150,11 +150,11 @@ static SRef sref(nsx_handle *h, double c, int num, int den) {
 
 // make scal[slot0 .. slot0+count) final (one launch for the whole range)
 void finalize_slots(nsx_handle *h, int slot0, int count) {
+  if (count > 64) NSX_THROW(NSX_ERR_ARG, "internal: finalize_slots range too long");
   bool any = false;
   for (int i = 0; i < count; ++i) any = any || h->slot_nb[slot0 + i] > 0;
   if (!any) return;
   NbArgs args;
-  if (count > 64) NSX_THROW(NSX_ERR_ARG, "internal: finalize_slots range too long");
   for (int i = 0; i < count; ++i) args.nb[i] = h->slot_nb[slot0 + i];
   hipLaunchKernelGGL(k_finalize, dim3(count), dim3(256), 0, h->stream, slot0, args, h->red_partial.p, h->scal.p);
   for (int i = 0; i < count; ++i) h->slot_nb[slot0 + i] = 0;
@@ -396,7 +396,115 @@ void write_scalar(nsx_handle *h, int slot, double v) {
   HIP_CHECK(hipStreamSynchronize(h->stream));
 }
 
+void v_reciprocal(nsx_handle *h, int n, double *d, const double *s, double num);  // nsx_solve.hip
+
+// One op of nsx_blas1_run (include/nsx.h): the arguments are checked as far as they index the caller's arrays and the slot table; what the
+// host functions refuse themselves (a launch's worth of vectors, a publication's range) is left to them.
+static void blas1_op(nsx_handle *h, Span whole, int m, const std::vector<DevBuf<double>> &vec, const nsx_blas1_op &op, double *out,
+                     double *scalars_out, int scalars_cap, int &n_scalars) {
+  if (op.n < 0 || op.n > whole.split) NSX_THROW(NSX_ERR_ARG, "nsx_blas1_run: an op's own length %d (split %d)", op.n, whole.split);
+  const Span sp = op.n > 0 ? Span(op.n) : whole;
+  auto V = [&](int i, bool optional = false) -> double * {
+    if (i < 0 && optional) return nullptr;
+    if (i < 0 || i >= m) NSX_THROW(NSX_ERR_ARG, "nsx_blas1_run: vector index %d of %d", i, m);
+    return vec[i].p;
+  };
+  auto S = [&](int s, bool optional = false, int count = 1) {
+    if (s < 0 && optional) return -1;
+    if (s < 0 || count < 1 || s + count > S_AGREE) NSX_THROW(NSX_ERR_ARG, "nsx_blas1_run: slots %d .. %d + %d", s, s, count);
+    return s;
+  };
+  auto plain = [&]() {
+    if (sp.gap != 0) NSX_THROW(NSX_ERR_ARG, "nsx_blas1_run: op %d takes a plain length", op.kind);
+    return sp.n;
+  };
+  bool has_result = false;
+  switch (op.kind) {
+    case NSX_BLAS1_DOT:
+      v_dot(h, sp, V(op.d), V(op.w), S(op.slot));
+      has_result = true;
+      break;
+    case NSX_BLAS1_ADD_AND_DOT:
+      v_add_and_dot(h, sp, V(op.d), op.a, S(op.num, true), V(op.v), V(op.w), S(op.slot));
+      has_result = true;
+      break;
+    case NSX_BLAS1_ADD: v_add(h, sp, V(op.d), op.a, V(op.v)); break;
+    case NSX_BLAS1_ADD_DEV: v_add_dev(h, sp, V(op.d), op.a, S(op.num), V(op.v)); break;
+    case NSX_BLAS1_SADD: v_sadd(h, sp, V(op.d), op.s, op.a, V(op.v)); break;
+    case NSX_BLAS1_SCALE: v_scale(h, sp, V(op.d), op.a); break;
+    case NSX_BLAS1_SCALE_DEV_INV: v_scale_dev_inv(h, sp, V(op.d), S(op.den)); break;
+    case NSX_BLAS1_SCALE_VEC: v_scale_vec(h, plain(), V(op.d), V(op.v)); break;
+    case NSX_BLAS1_AXPY_MULTI:
+    case NSX_BLAS1_AXPY_MULTI_INTO: {
+      if (op.k < 0 || op.k > NSX_BLAS1_MAX_K) NSX_THROW(NSX_ERR_ARG, "nsx_blas1_run: %d terms", op.k);
+      double *vs[NSX_BLAS1_MAX_K];
+      for (int j = 0; j < op.k; ++j) vs[j] = V(op.vs[j]);
+      if (op.kind == NSX_BLAS1_AXPY_MULTI) v_axpy_multi(h, sp, V(op.d), op.k, vs, op.coef);
+      else v_axpy_multi_into(h, sp, V(op.d), V(op.v, true), V(op.w, true), op.k, vs, op.coef);
+      break;
+    }
+    case NSX_BLAS1_CG_UPDATE:
+      cg_update(h, plain(), V(op.d), V(op.v), V(op.w), V(op.x), S(op.num), S(op.den), S(op.slot));
+      has_result = true;
+      break;
+    case NSX_BLAS1_CG_DIRECTION: cg_direction(h, plain(), V(op.d), V(op.v), S(op.num), S(op.den)); break;
+    case NSX_BLAS1_RECIPROCAL: v_reciprocal(h, plain(), V(op.d), V(op.v), op.a); break;
+    case NSX_BLAS1_FINALIZE: finalize_slots(h, S(op.slot, false, op.count), op.count); break;
+    case NSX_BLAS1_READ: {
+      S(op.slot, false, op.count);
+      if (n_scalars + op.count > scalars_cap || !scalars_out) NSX_THROW(NSX_ERR_ARG, "nsx_blas1_run: scalars_out holds %d values", scalars_cap);
+      std::vector<double> vals(op.count);
+      read_scalars(h, op.slot, op.count, vals.data());
+      for (int i = 0; i < op.count; ++i) scalars_out[n_scalars++] = vals[i];
+      *out = vals[0];
+      return;
+    }
+    case NSX_BLAS1_WRITE_SCALAR:
+      write_scalar(h, S(op.slot), op.a);
+      has_result = true;
+      break;
+    default: NSX_THROW(NSX_ERR_ARG, "nsx_blas1_run: kind %d", op.kind);
+  }
+  *out = 0.0;
+  if (op.read) {
+    if (!has_result) NSX_THROW(NSX_ERR_ARG, "nsx_blas1_run: op %d has no result slot to read", op.kind);
+    read_scalars(h, op.slot, 1, out);
+  }
+}
+
 }  // namespace nsx
+
+// A program of BLAS-1 operations on the caller's vectors: see include/nsx.h.  For tests/test_gpu_blas1.py.
+extern "C" int nsx_blas1_run(nsx_handle *h, int n, int split, int gap, int m, double *vectors, int n_ops, const nsx_blas1_op *ops, double *out,
+                             double *scalars_out, int scalars_cap) {
+  if (!h || !vectors || n < 1 || m < 1 || split < 0 || split > n || gap < 0 || (split == n && gap != 0) || n_ops < 0 || (n_ops && (!ops || !out)) ||
+      scalars_cap < 0)
+    return NSX_ERR_ARG;
+  NSX_TRY(h)
+  if (!h->have_mesh) NSX_THROW(NSX_ERR_ARG, "nsx_blas1_run needs a mesh: call nsx_set_mesh first");
+  if (h->dist) NSX_THROW(NSX_ERR_UNSUPPORTED, "nsx_blas1_run works on a single-process handle only");
+  HIP_CHECK(hipSetDevice(h->prm.device));
+  const size_t len = (size_t)n + gap;
+  std::vector<nsx::DevBuf<double>> v(m);
+  for (int k = 0; k < m; ++k) v[k].upload(vectors + (size_t)k * len, len, h->stream);
+  auto forget = [&]() {
+    for (int s = 0; s < nsx::N_SLOTS; ++s) h->slot_nb[s] = 0;
+  };
+  forget();
+  try {
+    const nsx::Span sp(n, split, gap);
+    int n_scalars = 0;
+    for (int i = 0; i < n_ops; ++i) nsx::blas1_op(h, sp, m, v, ops[i], out + i, scalars_out, scalars_cap, n_scalars);
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+  } catch (...) {
+    (void)hipStreamSynchronize(h->stream);  // the vectors are released on the way out
+    forget();
+    throw;
+  }
+  forget();
+  for (int k = 0; k < m; ++k) v[k].download(vectors + (size_t)k * len, len, h->stream);
+  NSX_CATCH(h)
+}
 
 extern "C" int nsx_persistent_state(nsx_handle *h, int state[4]) {
   if (!h || !state) return NSX_ERR_ARG;

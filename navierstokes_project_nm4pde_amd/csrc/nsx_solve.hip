@@ -487,42 +487,73 @@ static void count(nsx_solve_stats *st, bool F, const SolveResult &r) {
 // (solve_time_step, nsx_prec_vmult) and handed down: whether new basis vectors are zeroed and what prec_vmult overwrites must agree.
 static bool step_fused() { return env_on("NSX_STEP_FUSED"); }
 
+// The operators of the inner GMRES solves: F in the handle's inner precision with the velocity ILU(0), negative_S_tilde with its ILU(0)
+struct InnerOps {
+  Op Fm, PF, Sm, PS;
+  ResidOp Fr;
+  explicit InnerOps(nsx_handle *h) : Sm(schur_product(h)), PS(schur_ilu(h)) {
+    const int dim = h->dim;
+    const bool f32 = h->inner_precision == NSX_INNER_FP32;
+    Fm = [h](double *d, const double *s) { spmv_F_inner(h, s, d); };
+    PF = [h, dim, f32](double *d, const double *s) {
+      int used = 0;
+      ilu_solve(h, h->gA, h->schedF, h->luF.p, s, d, dim, "ilu_solve_F", -1, f32, &used);
+      if (used) h->ilu_F_fp32_used = 1;
+    };
+    Fr = [h](double *d, const double *x, const double *b) { spmv_F_inner_resid(h, x, b, d); };
+  }
+};
+// The inner solves' call sites, shared by prec_vmult and the test hook nsx_gmres.  abs_tol >= 0 (the hook alone, unfused): the
+// tolerance itself instead of tol * |b|.
+// SolverGMRES on F with tolerance tol * |b| and the velocity ILU(0).  sm (fused): |b|^2 is enqueued here and collected with the
+// solve's first residual norm, the residual of a cycle comes from the product's own launch, and what else the caller has set in sm
+static SolveResult solve_F(nsx_handle *h, const InnerOps &io, double tol, int maxit, double *x, const double *b, bool x_is_zero, Seams *sm,
+                           double abs_tol = -1.0) {
+  const int n_u = h->n_u, len_u = h->len_u;
+  GmresOpts o;
+  o.x_is_zero = x_is_zero;
+  o.plain_P = o.P_is_ilu_F = true;
+  if (!sm) return gmres(h, io.Fm, x, b, io.PF, n_u, len_u, abs_tol >= 0.0 ? abs_tol : tol * norm2(h, n_u, b), maxit, o);
+  sm->rtol = tol;
+  sm->A_resid = &io.Fr;
+  v_dot(h, n_u, b, b, S_T);
+  return gmres(h, io.Fm, x, b, io.PF, n_u, len_u, 0.0, maxit, o, sm);
+}
+// the first velocity solve of Yosida / SIMPLE: F x = b from x = x0 (there: both src_u).  Fused, x is only written: the first product
+// reads x0, the first update writes x = x0 + sum.  x_written (optional): whether an update stored x (else it is the copy of x0)
+static SolveResult solve_F_from(nsx_handle *h, const InnerOps &io, double tol, int maxit, double *x, const double *b, const double *x0, bool fused,
+                                bool *x_written = nullptr, double abs_tol = -1.0) {
+  if (!fused) {
+    if (x_written) *x_written = true;
+    return solve_F(h, io, tol, maxit, x, b, false, nullptr, abs_tol);
+  }
+  Seams sm;
+  sm.x0 = x0;
+  const SolveResult r = solve_F(h, io, tol, maxit, x, b, false, &sm);
+  if (!sm.x_written) v_copy(h, h->n_u, x, x0);  // converged as it stands
+  if (x_written) *x_written = sm.x_written;
+  return r;
+}
+// aSIMPLE's SolverGMRES on negative_S_tilde with its ILU(0) and tolerance tol * |b| (Prec.hpp:287-289); fused: |b|^2 travels with the
+// first residual norm
+static SolveResult solve_S_gmres(nsx_handle *h, const InnerOps &io, double tol, int maxit, double *x, const double *b, bool fused, double abs_tol = -1.0) {
+  const int n_p = h->n_p, len_p = h->len_p;
+  if (!fused) return gmres(h, io.Sm, x, b, io.PS, n_p, len_p, abs_tol >= 0.0 ? abs_tol : tol * norm2(h, n_p, b), maxit);
+  Seams ss;
+  ss.rtol = tol;
+  v_dot(h, n_p, b, b, S_T);
+  return gmres(h, io.Sm, x, b, io.PS, n_p, len_p, 0.0, maxit, {}, &ss);
+}
+
 void prec_vmult(nsx_handle *h, int type, double tol, int maxit, double *dst, const double *src, nsx_solve_stats *st, bool fused) {
   if (!h->prec_ready) NSX_THROW(NSX_ERR_ARG, "preconditioner not initialised");
-  const int n_u = h->n_u, n_p = h->n_p, dim = h->dim, len_u = h->len_u, len_p = h->len_p;
+  const int n_u = h->n_u, n_p = h->n_p, len_u = h->len_u, len_p = h->len_p;
   const double *src_u = src, *src_p = src + h->off_p;
   double *dst_u = dst, *dst_p = dst + h->off_p;
-  Op Fm = [h](double *d, const double *s) { spmv_F_inner(h, s, d); };
-  const bool f32 = h->inner_precision == NSX_INNER_FP32;
-  const Op Sm = schur_product(h), PS = schur_ilu(h);
-  Op PF = [h, dim, f32](double *d, const double *s) {
-    int used = 0;
-    ilu_solve(h, h->gA, h->schedF, h->luF.p, s, d, dim, "ilu_solve_F", -1, f32, &used);
-    if (used) h->ilu_F_fp32_used = 1;
-  };
+  const InnerOps io(h);
   auto cg_S = [&](double *x, const double *b) { return schur_cg(h, tol, maxit, x, b); };  // SolverCG on negative_S_tilde with tolerance tol * |b|
-  const ResidOp Fr = [h](double *d, const double *x, const double *b) { spmv_F_inner_resid(h, x, b, d); };
-  // SolverGMRES on F with tolerance tol * |b| and the velocity ILU(0).  sm (fused): |b|^2 is enqueued here and collected with the
-  // solve's first residual norm, the residual of a cycle comes from the product's own launch, and what else the caller has set in sm
-  auto solve_F = [&](double *x, const double *b, bool x_is_zero, Seams *sm) {
-    GmresOpts o;
-    o.x_is_zero = x_is_zero;
-    o.plain_P = o.P_is_ilu_F = true;
-    if (!sm) return count(st, true, gmres(h, Fm, x, b, PF, n_u, len_u, tol * norm2(h, n_u, b), maxit, o));
-    sm->rtol = tol;
-    sm->A_resid = &Fr;
-    v_dot(h, n_u, b, b, S_T);
-    count(st, true, gmres(h, Fm, x, b, PF, n_u, len_u, 0.0, maxit, o, sm));
-  };
-  // the first velocity solve of Yosida / SIMPLE: F x = src_u from x = src_u.  Fused, x is dst_u and only written: the first product
-  // reads src_u, the first update writes dst_u = src_u + sum
-  auto solve_F_from_src = [&](double *x) {
-    if (!fused) return solve_F(x, src_u, false, nullptr);
-    Seams sm;
-    sm.x0 = src_u;
-    solve_F(x, src_u, false, &sm);
-    if (!sm.x_written) v_copy(h, n_u, x, src_u);  // converged as it stands
-  };
+  auto solve_F = [&](double *x, const double *b, bool x_is_zero, Seams *sm) { count(st, true, nsx::solve_F(h, io, tol, maxit, x, b, x_is_zero, sm)); };
+  auto solve_F_from_src = [&](double *x) { count(st, true, solve_F_from(h, io, tol, maxit, x, src_u, src_u, fused)); };
   // out = block(1,0) x - r (sign 1) or r - block(1,0) x (sign -1): fused the epilogue of the product, else add / sadd behind it
   auto B_and_sub = [&](const double *x, double *out, const double *r, int sign) {
     if (fused) return spmv_B(h, x, out, r, sign);
@@ -573,15 +604,11 @@ void prec_vmult(nsx_handle *h, int type, double tol, int maxit, double *dst, con
     v_add(h, n_u, dst_u, -1.0, tmp.p());                                                           // :203
   } else if (type == NSX_PREC_ASIMPLE) {  // Prec.hpp:254-311 (dst is the caller's vector: its content is the initial guess)
     Tmp tmp_u(h, len_u), tmp_p(h, len_p);
-    Seams sm, ss;
+    Seams sm;
     solve_F(dst_u, src_u, false, fused ? &sm : nullptr);                                       // :271-273
     B_and_sub(dst_u, dst_p, src_p, -1);                                                        // :280-281
     v_copy(h, n_p, tmp_p.p(), dst_p);                                                          // :282
-    if (fused) {                                                                               // :287-289
-      ss.rtol = tol;
-      v_dot(h, n_p, tmp_p.p(), tmp_p.p(), S_T);
-      count(st, false, gmres(h, Sm, dst_p, tmp_p.p(), PS, n_p, len_p, 0.0, maxit, {}, &ss));
-    } else count(st, false, gmres(h, Sm, dst_p, tmp_p.p(), PS, n_p, len_p, tol * norm2(h, n_p, tmp_p.p()), maxit));
+    count(st, false, solve_S_gmres(h, io, tol, maxit, dst_p, tmp_p.p(), fused));               // :287-289
     v_scale_vec(h, n_u, dst_u, h->diag_D.p);                                                   // :294
     v_scale(h, n_p, dst_p, 1. / 1.0);                                                          // :298, alpha = 1 (:328)
     spmv_G(h, dst_p, tmp_u.p(), false);                                                        // :304
@@ -793,6 +820,65 @@ int nsx_sparse_product(nsx_handle *h, int op, double *dst, const double *src, co
   }
   if (op == NSX_PROD_G_ACC) HIP_CHECK(hipMemsetAsync(yp, 0, (size_t)(h->len_blk - h->off_p) * sizeof(double), h->stream));  // aux_p is no result
   nsx::vec_to_caller(h, d.p(), dst);
+  NSX_CATCH(h)
+}
+
+// One gmres() solve on the caller's vectors by the call sites of prec_vmult (solve_F, solve_F_from, solve_S_gmres): see include/nsx.h.
+// For tests/test_gpu_gmres.py.
+int nsx_gmres(nsx_handle *h, int system, int mode, double tol, int maxiter, double *x, const double *b, double *neg_out, int info[4],
+              double *last_residual) {
+  NSX_TRY(h)
+  const bool abs_tol = (mode & NSX_GMRES_ABS_TOL) != 0;
+  const int m = mode & ~NSX_GMRES_ABS_TOL;
+  if (!x || !b || !info || !last_residual) NSX_THROW(NSX_ERR_ARG, "null argument");
+  if (system != NSX_GMRES_F && system != NSX_GMRES_S) NSX_THROW(NSX_ERR_ARG, "unknown system %d", system);
+  if (m < NSX_GMRES_PLAIN || m > NSX_GMRES_FUSED_ZERO_NEG) NSX_THROW(NSX_ERR_ARG, "unknown mode %d", m);
+  if (system == NSX_GMRES_S && m != NSX_GMRES_PLAIN && m != NSX_GMRES_FUSED_GUESS) NSX_THROW(NSX_ERR_ARG, "the Schur system is solved plain or with the fused guess only");
+  if (abs_tol && m != NSX_GMRES_PLAIN && m != NSX_GMRES_ZERO) NSX_THROW(NSX_ERR_ARG, "an absolute tolerance needs an unfused mode");
+  if (m == NSX_GMRES_FUSED_ZERO_NEG && !neg_out) NSX_THROW(NSX_ERR_ARG, "this mode needs neg_out");
+  if (!h->prec_ready) NSX_THROW(NSX_ERR_ARG, "no operators and no factors: call nsx_prec_initialize first");
+  if (h->dist) NSX_THROW(NSX_ERR_UNSUPPORTED, "nsx_gmres works on a single-process handle only");
+  HIP_CHECK(hipSetDevice(h->prm.device));
+  const int which = system == NSX_GMRES_F ? 0 : 1;
+  const int len = which == 0 ? h->len_u : h->len_p, n = which == 0 ? h->n_u : h->n_p;
+  nsx::Tmp xd(h, len), bd(h, len), x0d(h, len), yd(h, len);
+  nsx::part_from_caller(h, which, xd.p(), x);
+  nsx::part_from_caller(h, which, bd.p(), b);
+  h->defer_red = false;
+  h->pending_red.clear();
+  const nsx::InnerOps io(h);
+  const double at = abs_tol ? tol : -1.0;
+  nsx::SolveResult r{0, 0, 0.0};
+  bool x_written = true, neg_done = false;
+  if (system == NSX_GMRES_S) r = nsx::solve_S_gmres(h, io, tol, maxiter, xd.p(), bd.p(), m == NSX_GMRES_FUSED_GUESS, at);
+  else if (m == NSX_GMRES_PLAIN) r = nsx::solve_F(h, io, tol, maxiter, xd.p(), bd.p(), false, nullptr, at);
+  else if (m == NSX_GMRES_FUSED_GUESS) {
+    nsx::Seams sm;
+    r = nsx::solve_F(h, io, tol, maxiter, xd.p(), bd.p(), false, &sm);
+    x_written = sm.x_written;
+  } else if (m == NSX_GMRES_FUSED_FROM_X0) {  // the guess lives in a vector of its own; x starts as NaN: it may only be written
+    nsx::v_copy(h, n, x0d.p(), xd.p());
+    HIP_CHECK(hipMemsetAsync(xd.p(), 0xff, (size_t)n * sizeof(double), h->stream));
+    r = nsx::solve_F_from(h, io, tol, maxiter, xd.p(), bd.p(), x0d.p(), true, &x_written);
+  } else if (m == NSX_GMRES_ZERO) {
+    nsx::v_zero(h, n, xd.p());
+    r = nsx::solve_F(h, io, tol, maxiter, xd.p(), bd.p(), true, nullptr, at);
+  } else {  // x is NOT zeroed (it comes back as it went in unless an update stores it); neg_out = -neg_out + x if the solve ends in its first cycle
+    nsx::part_from_caller(h, which, yd.p(), neg_out);
+    nsx::Seams sm;
+    sm.neg_out = yd.p();
+    r = nsx::solve_F(h, io, tol, maxiter, xd.p(), bd.p(), true, &sm);
+    x_written = sm.x_written;
+    neg_done = sm.neg_done;
+    nsx::part_to_caller(h, which, yd.p(), neg_out);
+  }
+  info[0] = r.steps;
+  info[1] = r.status;
+  info[2] = x_written ? 1 : 0;
+  info[3] = neg_done ? 1 : 0;
+  *last_residual = r.last;
+  nsx::part_to_caller(h, which, xd.p(), x);
+  nsx::ilu_check(h);
   NSX_CATCH(h)
 }
 

@@ -25,7 +25,7 @@ API = [
     "nsx_profile_enable", "nsx_profile_reset", "nsx_profile_count", "nsx_profile_get", "nsx_persistent_state", "nsx_path_info", "nsx_ilu_path_info", "nsx_comm_self_halo_test", "nsx_comm_unique_id",
     "nsx_comm_init", "nsx_comm_init_callbacks", "nsx_comm_counters", "nsx_set_mesh_distributed", "nsx_set_force_faces", "nsx_compute_forces",
     "nsx_set_internal_layout", "nsx_layout_info", "nsx_layout_get", "nsx_gram_schmidt_cycle", "nsx_set_inner_precision",
-    "nsx_gram_schmidt_sweeps", "nsx_compute_diagnostics", "nsx_get_cell_diagnostic", "nsx_schur_cg",
+    "nsx_gram_schmidt_sweeps", "nsx_compute_diagnostics", "nsx_get_cell_diagnostic", "nsx_schur_cg", "nsx_blas1_run", "nsx_gmres",
     "nsx_set_probes", "nsx_get_probe_cells", "nsx_eval_probes", "nsx_set_tracers", "nsx_advect_tracers", "nsx_get_tracers",
     "nsx_sparse_product", "nsx_compute_nodal_fields", "nsx_nodal_field_components", "nsx_get_nodal_field",
     "nsx_extract_isosurface", "nsx_get_isosurface",
@@ -81,6 +81,21 @@ class FlowDiag(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+BLAS1_KINDS = ("dot", "add_and_dot", "add", "add_dev", "sadd", "scale", "scale_dev_inv", "scale_vec", "axpy_multi", "axpy_multi_into",
+               "cg_update", "cg_direction", "reciprocal", "finalize", "read", "write_scalar")   # NSX_BLAS1_*, in the header's order
+BLAS1_MAX_K = 40
+GMRES_F, GMRES_S = 0, 1                                                                           # NSX_GMRES_*: system
+GMRES_PLAIN, GMRES_FUSED_GUESS, GMRES_FUSED_FROM_X0, GMRES_ZERO, GMRES_FUSED_ZERO_NEG = range(5)  # mode
+GMRES_ABS_TOL = 256
+
+
+class Blas1Op(C.Structure):
+    """nsx_blas1_op"""
+    _fields_ = [("kind", C.c_int32), ("d", C.c_int32), ("v", C.c_int32), ("w", C.c_int32), ("x", C.c_int32), ("slot", C.c_int32),
+                ("num", C.c_int32), ("den", C.c_int32), ("count", C.c_int32), ("read", C.c_int32), ("n", C.c_int32), ("k", C.c_int32),
+                ("vs", C.c_int32 * BLAS1_MAX_K), ("a", C.c_double), ("s", C.c_double), ("coef", C.c_double * BLAS1_MAX_K)]
 
 
 class IsoSource(C.Structure):
@@ -178,6 +193,8 @@ def lib():
     L.nsx_inner_F_vmult.argtypes = [vp, _f64p, _f64p]
     L.nsx_schur_cg.argtypes = [vp, C.c_double, C.c_int, _f64p, _f64p, C.POINTER(C.c_int), _f64p, C.POINTER(C.c_int)]
     L.nsx_sparse_product.argtypes = [vp, C.c_int, _f64p, _f64p, _f64p]
+    L.nsx_gmres.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_int, _f64p, _f64p, _f64p, C.POINTER(C.c_int), _f64p]
+    L.nsx_blas1_run.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, _f64p, C.c_int, C.POINTER(Blas1Op), _f64p, _f64p, C.c_int]
     L._nsx_ready = True
     return L
 
@@ -526,6 +543,49 @@ class Nsx:
         self._ck(self.L.nsx_gram_schmidt_sweeps(self._h, n, split, int(gap), m, _d(v), float(norm_guard), int(flags), _d(coeffs), _d(norms2),
                                                 _d(before), _i(normalized)))
         return v, coeffs, norms2, before, normalized
+
+    def gmres(self, system, mode, b, x0=None, tol=1e-2, maxiter=100000, neg_out=None, abs_tol=False):
+        """nsx_gmres: one GMRES solve of an inner system (GMRES_F / GMRES_S) by the call site `mode` names, from the guess x0 (default 0).
+        Returns a dict: x, neg_out (None unless given), steps, status, x_written, neg_done, last_residual."""
+        b = _cd(b)
+        x = np.zeros_like(b) if x0 is None else _cd(x0).copy()
+        y = None if neg_out is None else _cd(neg_out).copy()
+        n = self.n_u if system == GMRES_F else self.n_p
+        assert b.shape == (n,) and x.shape == (n,) and (y is None or y.shape == (n,))
+        info, last = (C.c_int * 4)(), C.c_double()
+        self._ck(self.L.nsx_gmres(self._h, int(system), int(mode) | (GMRES_ABS_TOL if abs_tol else 0), float(tol), int(maxiter), _d(x), _d(b),
+                                  None if y is None else _d(y), info, C.byref(last)))
+        return {"x": x, "neg_out": y, "steps": int(info[0]), "status": int(info[1]), "x_written": int(info[2]), "neg_done": int(info[3]),
+                "last_residual": last.value}
+
+    def blas1_run(self, vectors, ops, split=None, gap=0):
+        """nsx_blas1_run: a program of BLAS-1 operations on vectors[m][n + gap] in the device layout of a Span(n, split, gap).  ops: a list
+        of dicts -- "kind" (a name of BLAS1_KINDS) and the fields of nsx_blas1_op that op uses (vector indices d, v, w, x and slots num,
+        den default to -1, everything else to 0; vs / coef: sequences of k entries).  Returns (vectors afterwards in the same layout,
+        out[len(ops)], the values every "read" op published, in order)."""
+        v = np.ascontiguousarray(vectors, dtype=np.float64).copy()
+        m, n = v.shape[0], v.shape[1] - int(gap)
+        split = n if split is None else int(split)
+        recs = (Blas1Op * max(1, len(ops)))()
+        n_read = 0
+        for r, op in zip(recs, ops):
+            op = dict(op)
+            r.kind = BLAS1_KINDS.index(op.pop("kind"))
+            r.d = r.v = r.w = r.x = r.num = r.den = -1
+            vs, coef = list(op.pop("vs", ())), list(op.pop("coef", ()))
+            assert len(vs) == len(coef) <= BLAS1_MAX_K
+            r.k = op.pop("k", len(vs))
+            for j, (i, c) in enumerate(zip(vs, coef)):
+                r.vs[j], r.coef[j] = int(i), float(c)
+            for key, val in op.items():
+                if key not in ("d", "v", "w", "x", "slot", "num", "den", "count", "read", "n", "a", "s"):
+                    raise KeyError(key)
+                setattr(r, key, float(val) if key in ("a", "s") else int(val))
+            if BLAS1_KINDS[r.kind] == "read":
+                n_read += max(0, r.count)
+        out, scalars = np.zeros(max(1, len(ops))), np.zeros(max(1, n_read))
+        self._ck(self.L.nsx_blas1_run(self._h, n, split, int(gap), m, _d(v), len(ops), recs, _d(out), _d(scalars), n_read))
+        return v, out[:len(ops)], scalars[:n_read]
 
     # -- forces --------------------------------------------------------------------------------
     def set_force_faces(self, cells, lfaces, ftab):
