@@ -620,6 +620,77 @@ int nsx_stats_components(nsx_handle *h, int quantity, int *n_components);
  * non-empty bins pooled. */
 int nsx_stats_get(nsx_handle *h, int quantity, int bin, double *values);
 
+/* ---- surface loads ---- */
+/* What the flow does to a boundary, from the state the handle holds: wall pressure, traction, wall shear stress and y+ at every node of a set
+ * of boundary faces, and per group of faces (typically a boundary id) area, pressure force, viscous force, torque, flow rate and pressure
+ * integral.  nsx_compute_forces (above, unchanged) returns drag and lift of one face set by a caller-supplied face quadrature and sums on
+ * the host; here no table is needed: every surface integrand of a P2/P1 state is a polynomial of degree <= 2 on a face, which the P2 nodal
+ * rule of the face integrates exactly.  csrc/nsx_surface.hip.  Forces are kinematic (density 1), as the project's.
+ * Faces: cells[f] and local_faces[f] as for nsx_set_force_faces (position in the caller's cell list, deal.II local face number);
+ * groups[f] in [0, n_groups), 1 <= n_groups <= 64.  The face opposite local vertex k has the deal.II number 3 - k in 3D and (k + 1) % 3 in 2D
+ * (the tables of the tracer section).
+ * Geometry of the face opposite local vertex k: grad lambda_k is row k of J^-1 for k >= 1 (rows counted from 1) and minus the sum of the rows
+ * (added in their order) for k = 0; the outward unit normal of the fluid domain n = -grad lambda_k / |grad lambda_k| (the direction of
+ * fe_face_values.normal_vector; up to rounding the J^-T nref of nsx_compute_forces); the height of the cell over the face d = 1 / |grad lambda_k|;
+ * the measure |f| = |det J| |grad lambda_k| m with m = 1 in 2D and 1/2 in 3D.
+ * Face nodes: the face's vertices in the order of the face -> vertex tables {0,1},{1,2},{2,0} and {0,1,2},{1,0,3},{0,2,3},{2,1,3}, then in 3D
+ * the mid-edge nodes of the face lines (v0 v1, v1 v2, v2 v0), in 2D the one mid-point: 3 nodes per face in 2D, 6 in 3D.
+ * Values at a face node, taken in the face's own cell (the one-sided wall gradient) and evaluated as nsx_eval_probes evaluates (P2 in
+ * barycentric form, reference derivatives first, J^-1 last): p the P1 value, G_ij = d_j u_i, tau = nu (G + G^T) (NSX_SURFACE_SYMMETRIC) or
+ * nu G (NSX_SURFACE_GRADIENT); the traction the fluid exerts on the boundary t = p n - tau n; the wall shear stress
+ * s = -(tau n - (n . tau n) n); the shear magnitude |s|; y+ = sqrt(|s|) d / nu (all zeros when nu <= 0; at faces only).
+ * Surface nodes: a distinct (group, P2 node) pair among the face nodes -- a node on the seam of two groups is two surface nodes, one per
+ * group -- numbered by ascending group, then ascending P2 node id in the caller's numbering.  nsx_get_surface_layout: nodes[s] the P2 node
+ * (caller's numbering; global on a distributed handle), node_groups[s], face_nodes[f][j] the surface node of face node j of face f,
+ * areas[f] = |f|; any pointer may be NULL.
+ * Recovery at a surface node: Vbar(s) = sum_f |f| V_f(x_s) / sum_f |f| over the faces of that group that hold the node, in ascending position
+ * in the caller's face list, both sums folded left to right in double: pressure, traction and shear.  The shear magnitude at a node is that of
+ * the averaged shear, the normal is sum_f |f| n_f normalised.
+ * Totals per group by the P2 nodal rule of the face: weights |f| (1/6, 1/6, 4/6) in 2D (vertices, mid-point); |f| / 3 on the three mid-edge
+ * nodes and 0 on the vertices in 3D.  A face's weighted terms are added in the order of its nodes; the faces of a group are folded in a
+ * fixed tree over the caller's order whose shape depends on the face counts alone.  No atomics: bitwise reproducible, independent of
+ * nsx_set_ranks and nsx_set_internal_layout.
+ * Fields (nsx_get_surface_field): NSX_SURFACE_PRESSURE [1], _TRACTION [dim], _SHEAR [dim], _SHEAR_MAGNITUDE [1], _NORMAL [dim], _YPLUS [1].
+ * at = NSX_SURFACE_AT_FACES: values[n_faces][nodes per face][n_components], faces in the caller's order (the normal is the face's at each of
+ * its nodes); at = NSX_SURFACE_AT_NODES: values[n_surface_nodes][n_components].
+ * The calls read state only (the ghosted `solution`, current after nsx_set_solution and nsx_solve_time_step): a following solve computes
+ * bitwise what it would have computed without them.  nsx_get_surface_field returns the values of the last nsx_compute_surface and does not
+ * recompute after a later solve.  A state value that is not finite propagates to exactly the face nodes whose cell holds it and to the
+ * surface nodes and group totals built from them; the call still returns NSX_OK.  The set survives nsx_set_ranks and
+ * nsx_set_internal_layout; a new nsx_set_mesh(_distributed) drops it; n_faces = 0 clears it.
+ * Distributed handles: the caller passes the boundary faces of the rank's cell list in ascending global face order, at least those of its
+ * layer-1 cells.  A face enters the totals on the rank that counts its cell (the rule of the flow diagnostics).  nsx_compute_surface with
+ * totals costs exactly one all-reduce (every rank gets the sums of all ranks), with totals = NULL none; no call issues a ghost exchange.
+ * Values at nodes are filled for the surface nodes whose P2 node the rank owns (the rest 0) and are bitwise those of a single-process
+ * handle; values at faces are filled for every face passed.
+ * Errors: NSX_ERR_ARG for a null handle, a call before tables or mesh, a get / info / compute call without a set, a get before a compute,
+ * a compute before the handle holds a state, a bad cell, local face, group, n_groups, form, `which` or `at`, NSX_SURFACE_YPLUS at nodes, a
+ * centre that is not finite, a null output where one is required, a (cell, face) pair given twice; NSX_ERR_UNSUPPORTED for a (dim, n_p2)
+ * other than (2, 6) / (3, 10).  A refused call writes nothing and leaves an earlier set and its results readable. */
+enum { NSX_SURFACE_SYMMETRIC = 0, NSX_SURFACE_GRADIENT = 1 };       /* viscous stress tau = nu (G + G^T) | nu G,  G_ij = d_j u_i */
+enum { NSX_SURFACE_AT_FACES = 0, NSX_SURFACE_AT_NODES = 1 };
+enum { NSX_SURFACE_PRESSURE = 0, NSX_SURFACE_TRACTION, NSX_SURFACE_SHEAR, NSX_SURFACE_SHEAR_MAGNITUDE, NSX_SURFACE_NORMAL, NSX_SURFACE_YPLUS,
+       NSX_SURFACE_FIELD_COUNT };
+typedef struct {
+  double area;                 /* sum |f| */
+  double force_pressure[3];    /* int p n               (entries >= dim are 0) */
+  double force_viscous[3];     /* -int tau n */
+  double torque[3];            /* int (x - centre) x t ; 2D: torque[2] only */
+  double flux;                 /* int u . n */
+  double pressure_integral;    /* int p */
+  int64_t n_faces;             /* faces counted (all ranks) */
+} nsx_surface_totals;
+
+/* Installs the face set (n_faces = 0: clears it). */
+int nsx_set_surface(nsx_handle *h, int n_faces, const int32_t *cells, const int32_t *local_faces, const int32_t *groups /* NULL: all 0 */,
+                    int n_groups, int form, const double *centre /*[dim]; NULL: origin*/);
+int nsx_surface_info(nsx_handle *h, int info[4]);   /* n_faces, n_groups, n_surface_nodes, nodes per face (3 | 6) */
+int nsx_get_surface_layout(nsx_handle *h, int32_t *nodes, int32_t *node_groups, int32_t *face_nodes, double *areas);
+/* Evaluates every face node and surface node of the set from the state the handle holds; the totals of every group if asked for. */
+int nsx_compute_surface(nsx_handle *h, nsx_surface_totals *totals /*[n_groups]; may be NULL*/);
+int nsx_surface_field_components(nsx_handle *h, int which, int *n_components);
+int nsx_get_surface_field(nsx_handle *h, int which, int at, double *values);
+
 /* ---- measurement ---- */
 /* Per-kernel HIP-event timing of the hot path (bench.py roofline): enable, run, then read name/count/total-ms. */
 int nsx_profile_enable(nsx_handle *h, int on);

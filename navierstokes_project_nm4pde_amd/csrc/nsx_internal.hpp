@@ -18,6 +18,8 @@
 //                  the nodal results), built on demand (the isosurface extraction: nsx_iso.hip; IsoState)
 //   stats planes   per phase bin and owned node, in the caller's numbering: mean and co-moment of velocity and pressure (the running statistics:
 //                  nsx_stats.hip; StatsState)
+//   surface tables per boundary face of the installed set, sorted by group: cell, local face, normal, height, measure, node positions; the patch
+//                  lists of the surface nodes in tiles of 64; planes of the last results (the surface loads: nsx_surface.hip; SurfaceState)
 //   gather maps    per CSR entry the list of (local entry, cell) contributions -> deterministic assembly, no atomics
 #pragma once
 #include <hip/hip_runtime.h>
@@ -477,6 +479,40 @@ struct StatsState {
   void mesh_changed() { clear(); }  // a new mesh drops the accumulation
 };
 
+// Surface loads (nsx_surface.hip).  Faces and surface nodes are in the caller's cell and node numbering: the set and its results outlive a
+// new layout / rank table, not a new mesh.  "sorted": the faces stable-sorted by group (host/surface_patch.hpp).
+struct SurfaceState {
+  bool set = false, valid = false;  // a set is installed; the planes hold the values of a finished nsx_compute_surface on it
+  int n_faces = 0, n_groups = 0, n_nodes = 0, npf = 0, form = 0, tiles = 0;
+  int64_t entries = 0;              // entries of ent, padding included
+  double centre[3] = {0, 0, 0};
+  std::vector<int32_t> order, face_nodes, node_group, slot_of;  // sorted position -> caller's face, [n_faces][npf] surface node, [n_nodes] each
+  std::vector<int32_t> nodes;       // [n_nodes] P2 node in the caller's (global) numbering
+  std::vector<uint8_t> owned;       // [n_nodes] 1 = this handle owns the P2 node
+  std::vector<double> areas;        // [n_faces] caller's order
+  std::vector<std::vector<int32_t>> fold_blocks;  // per level of the fold {first, last + 1, group} of every block
+  DevBuf<int32_t> cells, lf;        // [n_faces] sorted: cell (caller's cell list), local vertex the face lies opposite of
+  DevBuf<double> fgeo;              // SoA [dim + 2][n_faces] sorted: outward unit normal, height of the cell over the face, measure
+  DevBuf<double> fx;                // SoA [dim][npf][n_faces] sorted: position of every face node
+  DevBuf<int32_t> tile_ptr, ent, fold_tab;  // patch lists in tiles of 64 surface nodes; the block tables of the fold, level after level
+  DevBuf<double> fvals;             // SoA [surface_face_planes(dim)][npf][n_faces] sorted: the values at the face nodes
+  DevBuf<double> nvals;             // SoA [surface_node_planes(dim)][64 tiles] in slot order: the values at the surface nodes
+  DevBuf<double> contrib, fold;     // SoA [surface_total_planes(dim)][n_faces] per-face contributions to the totals; the levels of their fold
+  void clear() {
+    set = valid = false;
+    n_faces = n_groups = n_nodes = npf = form = tiles = 0;
+    entries = 0;
+    centre[0] = centre[1] = centre[2] = 0.0;
+    for (auto *v : {&order, &face_nodes, &node_group, &slot_of, &nodes}) v->clear();
+    owned.clear();
+    areas.clear();
+    fold_blocks.clear();
+    for (auto *b : {&cells, &lf, &tile_ptr, &ent, &fold_tab}) b->release();
+    for (auto *b : {&fgeo, &fx, &fvals, &nvals, &contrib, &fold}) b->release();
+  }
+  void mesh_changed() { clear(); }  // a new mesh drops the set and its results
+};
+
 struct Comm;  // RCCL state (nsx_comm.hip)
 
 // ---- THE table of device scalar slots (h->scal, mirrored in h->scal_host and the first N_SLOTS doubles of h->pub_host), of the mapped
@@ -630,6 +666,7 @@ struct nsx_handle {
   nsx::IsoState iso;        // nsx_iso.hip
   nsx::LatticeState lattice;  // nsx_lattice.hip
   nsx::StatsState stats;    // nsx_stats.hip
+  nsx::SurfaceState surface;  // nsx_surface.hip
   // ---- profiling
   bool prof_on = false;
   std::map<std::string, nsx::ProfEntry> prof;
@@ -759,6 +796,7 @@ inline void post_mesh_changed(nsx_handle *h) {
   h->iso.mesh_changed();
   h->lattice.mesh_changed();
   h->stats.mesh_changed();
+  h->surface.mesh_changed();
 }
 
 // sparse (nsx_sparse.hip)

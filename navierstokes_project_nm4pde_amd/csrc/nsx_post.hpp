@@ -1,6 +1,6 @@
-// nsx_post.hpp — what the post-processing files share (nsx_diag, nsx_probe, nsx_tracer, nsx_nodal, nsx_iso, nsx_lattice, nsx_stats): the affine cell map, the P2
+// nsx_post.hpp — what the post-processing files share (nsx_diag, nsx_probe, nsx_tracer, nsx_nodal, nsx_iso, nsx_lattice, nsx_stats, nsx_surface): the affine cell map, the P2
 // shape functions in barycentric form, the push-forward of a reference gradient, the space check and the layout of the nodal results.
-// Their state lives in nsx_internal.hpp (DiagState ... StatsState), and so does the guard of their C entries (NSX_TRY / NSX_CATCH).
+// Their state lives in nsx_internal.hpp (DiagState ... SurfaceState), and so does the guard of their C entries (NSX_TRY / NSX_CATCH).
 #pragma once
 #include "nsx_internal.hpp"
 

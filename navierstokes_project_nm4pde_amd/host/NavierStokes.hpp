@@ -130,6 +130,7 @@ public:
       ck(nsx_set_tracers(h, n_tracers, seeds.data(), -1.0));
     }
     if (!lattice_counts.empty()) setup_lattice();
+    if (surface_csv) setup_surface();
   }
 
   void solve() {  // NavierStokes3D.cpp:687-741
@@ -152,6 +153,7 @@ public:
       if (probes_csv) write_pressure_difference(time_step, time);
       if (n_tracers > 0) write_tracers(time_step, time);
       if (stats_first > 0 && time_step >= (unsigned int)stats_first) accumulate_statistics();
+      if (surface_csv) write_surface_loads(time);
       // NavierStokes3D.cpp:725-726, as written: an EXACT floating-point comparison of the accumulated time with T - deltat (true or false
       // by the rounding of the additions; the reference's own run decides it the same way, so the mirror does not "repair" it)
       if (dim == 3 && time == T - deltat) compute_pressure_difference();
@@ -220,6 +222,7 @@ public:
       } else if (nsxh_write_vtu(dofs, x.data(), directory, output_file_name.c_str(), time_step))
         throw std::runtime_error("cannot write " + output_file_name);
       if (!lattice_counts.empty()) write_lattice(time_step, directory);
+      if (surface_csv) write_surface_distribution(time_step, directory);
       out() << "Output written to " << output_file_name << std::endl;
     }
     if (dim == 2 && write_csv) {
@@ -409,6 +412,68 @@ protected:
       throw std::runtime_error("cannot write the lattice file");
   }
 
+  // opt-in surface loads (NSX_SURFACE=1): every boundary face, grouped by boundary id 0 .. 3 (inlet, outlet, walls, obstacle), symmetric
+  // viscous stress, torque about the cylinder's axis; installed once (nsx_set_surface)
+  void setup_surface() {
+    const int nbf = nsxh_mesh_n_bfaces(mesh);
+    const int32_t *ids = nsxh_mesh_bface_ids(mesh), *bc = nsxh_mesh_bface_cells(mesh);
+    std::vector<int32_t> fc, fl, fg;
+    for (int f = 0; f < nbf; ++f) {
+      if (ids[f] < 0 || ids[f] > 3) continue;
+      fc.push_back(bc[f]);
+      fl.push_back(local_face(f));
+      fg.push_back(ids[f]);
+    }
+    const double axis3[3] = {0.5, 0.2, 0.205}, axis2[2] = {0.2, 0.2};
+    ck(nsx_set_surface(h, (int)fc.size(), fc.data(), fl.data(), fg.data(), 4, NSX_SURFACE_SYMMETRIC, dim == 3 ? axis3 : axis2));
+    std::ofstream file(dim == 3 ? "surface_loads_3D.csv" : "surface_loads_2D.csv", std::ios::trunc);  // a run starts its series anew
+    if (!file.is_open()) throw std::runtime_error("cannot write the surface loads file");
+  }
+
+  // ... every time step appends to surface_loads_{2D,3D}.csv: time, pressure force [dim], viscous force [dim] and torque [3 | 1] on the
+  // obstacle, flow rate through the inlet, flow rate through the outlet (nsx_compute_surface: one fold on the device, 4 groups downloaded)
+  void write_surface_loads(const double time) const {
+    nsx_surface_totals t[4];
+    ck(nsx_compute_surface(h, t));
+    char row[640];
+    int n = snprintf(row, sizeof(row), "%.17g", time);
+    for (int d = 0; d < dim; ++d) n += snprintf(row + n, sizeof(row) - n, ",%.17g", t[3].force_pressure[d]);
+    for (int d = 0; d < dim; ++d) n += snprintf(row + n, sizeof(row) - n, ",%.17g", t[3].force_viscous[d]);
+    for (int d = dim == 3 ? 0 : 2; d < 3; ++d) n += snprintf(row + n, sizeof(row) - n, ",%.17g", t[3].torque[d]);
+    snprintf(row + n, sizeof(row) - n, ",%.17g,%.17g\n", t[0].flux, t[1].flux);
+    std::ofstream file(dim == 3 ? "surface_loads_3D.csv" : "surface_loads_2D.csv", std::ios::app);
+    if (!file.is_open()) throw std::runtime_error("cannot write the surface loads file");
+    file << row;
+  }
+
+  // ... and every output() writes surface-navier-stokes-{2D,3D}_<step>.csv beside the VTU, one row per surface node of the obstacle:
+  // position [dim], normal [dim], pressure, wall shear stress [dim]
+  void write_surface_distribution(const unsigned int time_step, const char *directory) const {
+    int info[4];
+    ck(nsx_surface_info(h, info));
+    const size_t ns = (size_t)info[2];
+    std::vector<int32_t> nodes(ns), groups(ns);
+    std::vector<double> normal(ns * dim), pressure(ns), shear(ns * dim);
+    ck(nsx_get_surface_layout(h, nodes.data(), groups.data(), nullptr, nullptr));
+    ck(nsx_compute_surface(h, nullptr));
+    ck(nsx_get_surface_field(h, NSX_SURFACE_NORMAL, NSX_SURFACE_AT_NODES, normal.data()));
+    ck(nsx_get_surface_field(h, NSX_SURFACE_PRESSURE, NSX_SURFACE_AT_NODES, pressure.data()));
+    ck(nsx_get_surface_field(h, NSX_SURFACE_SHEAR, NSX_SURFACE_AT_NODES, shear.data()));
+    std::ofstream file(std::string(directory) + (dim == 3 ? "surface-navier-stokes-3D_" : "surface-navier-stokes-2D_") + std::to_string(time_step) + ".csv");
+    if (!file.is_open()) throw std::runtime_error("cannot write the surface distribution file");
+    const double *sp = nsxh_support_points(dofs);
+    char row[640];
+    for (size_t s = 0; s < ns; ++s) {
+      if (groups[s] != 3) continue;
+      int n = 0;
+      for (int d = 0; d < dim; ++d) n += snprintf(row + n, sizeof(row) - n, "%.17g,", sp[(size_t)nodes[s] * dim * dim + d]);  // velocity dof dim * node
+      for (int d = 0; d < dim; ++d) n += snprintf(row + n, sizeof(row) - n, "%.17g,", normal[s * dim + d]);
+      n += snprintf(row + n, sizeof(row) - n, "%.17g", pressure[s]);
+      for (int d = 0; d < dim; ++d) n += snprintf(row + n, sizeof(row) - n, ",%.17g", shear[s * dim + d]);
+      file << row << "\n";
+    }
+  }
+
   static std::vector<int32_t> parse_counts(const char *text) {  // "nx,ny[,nz]"; anything else: one entry 0, which setup_lattice refuses
     std::vector<int32_t> counts;
     if (!text || !*text) return counts;
@@ -424,28 +489,31 @@ protected:
     return counts;
   }
 
-  void setup_force_faces() {  // faces with boundary id 3 and the face-quadrature tables (FEFaceValues of compute_forces)
+  int local_face(const int f) const {  // deal.II local face number of boundary face f in its cell (-1: none, which libnsx refuses)
     static const int TETF[4][3] = {{0, 1, 2}, {1, 0, 3}, {0, 2, 3}, {2, 1, 3}};
     static const int TRIF[3][2] = {{0, 1}, {1, 2}, {2, 0}};
+    const int32_t *bf = nsxh_mesh_bfaces(mesh), *cv = nsxh_mesh_cells(mesh) + (size_t)nsxh_mesh_bface_cells(mesh)[f] * (dim + 1);
+    for (int lf = 0; lf <= dim; ++lf) {
+      int match = 0;
+      for (int k = 0; k < dim; ++k) {
+        const int32_t v = cv[dim == 3 ? TETF[lf][k] : TRIF[lf][k]];
+        for (int q = 0; q < dim; ++q) match += v == bf[(size_t)f * dim + q];
+      }
+      if (match == dim) return lf;
+    }
+    return -1;
+  }
+
+  void setup_force_faces() {  // faces with boundary id 3 and the face-quadrature tables (FEFaceValues of compute_forces)
     const int nbf = nsxh_mesh_n_bfaces(mesh);
-    const int32_t *bf = nsxh_mesh_bfaces(mesh), *ids = nsxh_mesh_bface_ids(mesh), *bc = nsxh_mesh_bface_cells(mesh);
-    const int32_t *cells = nsxh_mesh_cells(mesh);
+    const int32_t *ids = nsxh_mesh_bface_ids(mesh), *bc = nsxh_mesh_bface_cells(mesh);
     std::vector<int32_t> fc, fl;
     for (int f = 0; f < nbf; ++f) {
       if (ids[f] != 3) continue;
-      const int32_t *cv = cells + (size_t)bc[f] * (dim + 1);
-      for (int lf = 0; lf <= dim; ++lf) {
-        int match = 0;
-        for (int k = 0; k < dim; ++k) {
-          const int32_t v = cv[dim == 3 ? TETF[lf][k] : TRIF[lf][k]];
-          for (int q = 0; q < dim; ++q) match += v == bf[(size_t)f * dim + q];
-        }
-        if (match == dim) {
-          fc.push_back(bc[f]);
-          fl.push_back(lf);
-          break;
-        }
-      }
+      const int lf = local_face(f);
+      if (lf < 0) continue;
+      fc.push_back(bc[f]);
+      fl.push_back(lf);
     }
     nsxh_tables *t = nsxh_tables_create(dim, 1, 0);
     ck(nsx_set_force_faces(h, (int)fc.size(), fc.data(), fl.data(), nsxh_tables_n_qf(t), nsxh_tables_N2(t), nsxh_tables_dN2(t),
@@ -477,6 +545,12 @@ protected:
   const bool probes_csv = std::getenv("NSX_PROBES") && std::string(std::getenv("NSX_PROBES")) == "1";
   const bool fields_vtu = std::getenv("NSX_FIELDS") && std::string(std::getenv("NSX_FIELDS")) == "1";
   const std::vector<int32_t> lattice_counts = parse_counts(std::getenv("NSX_LATTICE"));
+  static bool surface_wanted() {  // NSX_SURFACE: unset = off, 1 = on, anything else is an error
+    const char *e = std::getenv("NSX_SURFACE");
+    if (e && std::string(e) != "1") throw std::runtime_error("NSX_SURFACE: set it to 1 to write the surface loads, or leave it unset (got \"" + std::string(e) + "\")");
+    return e != nullptr;
+  }
+  const bool surface_csv = surface_wanted();
   double lattice_origin[3] = {0.0, 0.0, 0.0}, lattice_spacing[3] = {1.0, 1.0, 1.0};
   const int stats_first = std::getenv("NSX_STATS") ? std::max(0, std::atoi(std::getenv("NSX_STATS"))) : 0;  // first time step of the statistics (0: none)
   bool stats_open = false;

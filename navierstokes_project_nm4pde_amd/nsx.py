@@ -31,6 +31,7 @@ API = [
     "nsx_extract_isosurface", "nsx_get_isosurface",
     "nsx_set_lattice", "nsx_get_lattice_cells", "nsx_eval_lattice", "nsx_get_lattice",
     "nsx_stats_begin", "nsx_stats_accumulate", "nsx_stats_info", "nsx_stats_components", "nsx_stats_get",
+    "nsx_set_surface", "nsx_surface_info", "nsx_get_surface_layout", "nsx_compute_surface", "nsx_surface_field_components", "nsx_get_surface_field",
 ]
 # declared in include/nsx.h as well, but with a capital letter in its name, which the header scan of tests/test_abi.py (lower case only)
 # does not see: kept beside the list that scan is compared with; build() checks both
@@ -54,6 +55,11 @@ LATTICE_VELOCITY, LATTICE_PRESSURE, LATTICE_GRADIENT, LATTICE_NODAL = 1, 2, 4, 8
 STATS_VELOCITY, STATS_PRESSURE = 1, 2
 (STATS_MEAN_U, STATS_COMOMENT_U, STATS_STRESS_U, STATS_RMS_U, STATS_TKE, STATS_MEAN_P, STATS_COMOMENT_P, STATS_VAR_P, STATS_RMS_P,
  STATS_QUANTITY_COUNT) = range(10)
+# nsx_set_surface: form of the viscous stress; nsx_get_surface_field: where, and which field (NSX_SURFACE_*)
+SURFACE_SYMMETRIC, SURFACE_GRADIENT = 0, 1
+SURFACE_AT_FACES, SURFACE_AT_NODES = 0, 1
+(SURFACE_PRESSURE, SURFACE_TRACTION, SURFACE_SHEAR, SURFACE_SHEAR_MAGNITUDE, SURFACE_NORMAL, SURFACE_YPLUS,
+ SURFACE_FIELD_COUNT) = range(7)
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, _f64p, C.c_int)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(_f64p), C.POINTER(C.c_int),
@@ -81,6 +87,15 @@ class FlowDiag(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class SurfaceTotals(C.Structure):
+    """nsx_surface_totals"""
+    _fields_ = [("area", C.c_double), ("force_pressure", C.c_double * 3), ("force_viscous", C.c_double * 3), ("torque", C.c_double * 3),
+                ("flux", C.c_double), ("pressure_integral", C.c_double), ("n_faces", C.c_int64)]
+
+    def as_dict(self):
+        return {k: (np.array(getattr(self, k)) if k in ("force_pressure", "force_viscous", "torque") else getattr(self, k)) for k, _ in self._fields_}
 
 
 BLAS1_KINDS = ("dot", "add_and_dot", "add", "add_dev", "sadd", "scale", "scale_dev_inv", "scale_vec", "axpy_multi", "axpy_multi_into",
@@ -189,6 +204,12 @@ def lib():
     L.nsx_stats_info.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int64), _f64p]
     L.nsx_stats_components.argtypes = [vp, C.c_int, C.POINTER(C.c_int)]
     L.nsx_stats_get.argtypes = [vp, C.c_int, C.c_int, _f64p]
+    L.nsx_set_surface.argtypes = [vp, C.c_int, _i32p, _i32p, _i32p, C.c_int, C.c_int, _f64p]
+    L.nsx_surface_info.argtypes = [vp, C.POINTER(C.c_int)]
+    L.nsx_get_surface_layout.argtypes = [vp, _i32p, _i32p, _i32p, _f64p]
+    L.nsx_compute_surface.argtypes = [vp, C.POINTER(SurfaceTotals)]
+    L.nsx_surface_field_components.argtypes = [vp, C.c_int, C.POINTER(C.c_int)]
+    L.nsx_get_surface_field.argtypes = [vp, C.c_int, C.c_int, _f64p]
     L.nsx_set_inner_precision.argtypes = [vp, C.c_int]
     L.nsx_inner_F_vmult.argtypes = [vp, _f64p, _f64p]
     L.nsx_schur_cg.argtypes = [vp, C.c_double, C.c_int, _f64p, _f64p, C.POINTER(C.c_int), _f64p, C.POINTER(C.c_int)]
@@ -771,6 +792,64 @@ class Nsx:
         self._ck(self.L.nsx_stats_components(self._h, int(quantity), C.byref(nc)))
         out = np.zeros((self.n_u // self.dim if quantity < STATS_MEAN_P else self.n_p, nc.value))
         self._ck(self.L.nsx_stats_get(self._h, int(quantity), int(bin), _d(out)))
+        return out
+
+    # -- surface loads -------------------------------------------------------------------------
+    def set_surface(self, cells, local_faces, groups=None, n_groups=None, form=SURFACE_SYMMETRIC, centre=None):
+        """nsx_set_surface: boundary faces (position in the cell list, deal.II local face number) in groups (None: all 0; n_groups None:
+        largest group + 1), the form of the viscous stress and the centre of the torque (None: origin).  No faces: clears the set.
+        problem.boundary_faces() gives the three arrays.  In a multi-process run `cells` are global cell ids in ascending face order and the
+        faces of the cells this rank's view holds are kept (self.surface_faces: their positions in the list handed in)."""
+        cells, lf = np.asarray(cells), np.asarray(local_faces)
+        gr = None if groups is None else _ci(groups)
+        if n_groups is None:
+            n_groups = 1 if gr is None or len(gr) == 0 else int(gr.max()) + 1
+        if self.world > 1:
+            pos = {int(c): i for i, c in enumerate(self.view["cell_ids"])}
+            keep = np.array([k for k, c in enumerate(cells) if int(c) in pos], dtype=np.int64)
+            self.surface_faces = keep
+            cells, lf = np.array([pos[int(c)] for c in cells[keep]], dtype=np.int32), lf[keep]
+            gr = None if gr is None else _ci(gr[keep])
+        cells, lf = _ci(cells), _ci(lf)
+        cen = None if centre is None else _cd(centre)
+        self._ck(self.L.nsx_set_surface(self._h, len(cells), _i(cells), _i(lf), None if gr is None else _i(gr), int(n_groups), int(form),
+                                        None if cen is None else _d(cen)))
+
+    def surface_info(self):
+        """dict: n_faces, n_groups, n_nodes (surface nodes), nodes_per_face (nsx_surface_info)"""
+        v = (C.c_int * 4)()
+        self._ck(self.L.nsx_surface_info(self._h, v))
+        return {"n_faces": int(v[0]), "n_groups": int(v[1]), "n_nodes": int(v[2]), "nodes_per_face": int(v[3])}
+
+    def surface_layout(self):
+        """dict: nodes [n_nodes] (P2 node of every surface node, caller's numbering), node_groups [n_nodes], face_nodes
+        [n_faces][nodes_per_face] (surface node of every face node), areas [n_faces] (nsx_get_surface_layout)"""
+        i = self.surface_info()
+        nodes, groups = np.zeros(i["n_nodes"], dtype=np.int32), np.zeros(i["n_nodes"], dtype=np.int32)
+        fn, areas = np.zeros((i["n_faces"], i["nodes_per_face"]), dtype=np.int32), np.zeros(i["n_faces"])
+        self._ck(self.L.nsx_get_surface_layout(self._h, _i(nodes), _i(groups), _i(fn), _d(areas)))
+        return {"nodes": nodes, "node_groups": groups, "face_nodes": fn, "areas": areas}
+
+    def compute_surface(self, totals=True):
+        """nsx_compute_surface: evaluates every face node and surface node of the set from the state the handle holds; returns the totals
+        of every group as a list of dicts (area, force_pressure [3], force_viscous [3], torque [3], flux, pressure_integral, n_faces), or
+        None with totals=False (a distributed handle then issues no collective)."""
+        if not totals:
+            self._ck(self.L.nsx_compute_surface(self._h, None))
+            return None
+        t = (SurfaceTotals * self.surface_info()["n_groups"])()
+        self._ck(self.L.nsx_compute_surface(self._h, t))
+        return [g.as_dict() for g in t]
+
+    def surface_field(self, which, at=SURFACE_AT_NODES):
+        """one field (SURFACE_*) of the last compute_surface(): [n_faces][nodes_per_face][n_components] at = SURFACE_AT_FACES (faces in
+        the caller's order), [n_nodes][n_components] at = SURFACE_AT_NODES (nsx_get_surface_field).  Distributed handles: the surface nodes
+        whose P2 node the rank owns are filled, the rest 0."""
+        nc = C.c_int(0)
+        self._ck(self.L.nsx_surface_field_components(self._h, int(which), C.byref(nc)))
+        i = self.surface_info()
+        out = np.zeros((i["n_faces"], i["nodes_per_face"], nc.value) if at == SURFACE_AT_FACES else (i["n_nodes"], nc.value))
+        self._ck(self.L.nsx_get_surface_field(self._h, int(which), int(at), _d(out)))
         return out
 
     # -- export --------------------------------------------------------------------------------

@@ -255,6 +255,23 @@ def obstacle_faces(mesh, boundary_id=3):
     return cells, lf
 
 
+def boundary_faces(mesh, ids=None):
+    """(cells, local_faces, groups) of every boundary face whose id is in `ids` (None: all ids of the mesh, ascending), faces in the
+    mesh's boundary-face order, group = position of the face's id in `ids`: what Nsx.set_surface takes.  Generalises obstacle_faces."""
+    faces = _TET_FACES if mesh.dim == 3 else _TRI_FACES
+    ids = sorted(set(int(b) for b in mesh.bface_ids)) if ids is None else [int(b) for b in ids]
+    group_of = {b: g for g, b in enumerate(ids)}
+    sel = np.array([k for k, b in enumerate(mesh.bface_ids) if int(b) in group_of], dtype=np.int64)
+    cells = np.asarray(mesh.bface_cells)[sel].astype(np.int32)
+    lf, groups = np.empty(len(sel), dtype=np.int32), np.empty(len(sel), dtype=np.int32)
+    for k, bf in enumerate(sel):
+        cv = mesh.cells[cells[k]]
+        fset = set(mesh.bfaces[bf].tolist())
+        lf[k] = next(i for i, fv in enumerate(faces) if {int(cv[j]) for j in fv} == fset)
+        groups[k] = group_of[int(mesh.bface_ids[bf])]
+    return cells, lf, groups
+
+
 def force_coefficients(dim, drag, lift, mean_v, rho=1.0, D=0.1, H=0.41):
     """c_D, c_L: 2F/(rho U^2 D H) in 3D (NavierStokes3D.cpp:835-842), 2F/(U^2 D) in 2D (NavierStokes2D.cpp:849-853)."""
     den = rho * mean_v * mean_v * D * H if dim == 3 else mean_v * mean_v * D
