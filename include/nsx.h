@@ -246,6 +246,21 @@ int nsx_gmres(nsx_handle *h, int system, int mode, double tol, int maxiter, doub
 enum { NSX_PROD_F = 0, NSX_PROD_F_INNER, NSX_PROD_F_RESID, NSX_PROD_MASS, NSX_PROD_B, NSX_PROD_B_MINUS_R, NSX_PROD_R_MINUS_B, NSX_PROD_G,
        NSX_PROD_G_ACC, NSX_PROD_S, NSX_PROD_SADDLE, NSX_PROD_COUNT };
 int nsx_sparse_product(nsx_handle *h, int op, double *dst, const double *src, const double *aux);
+/* Test hook: one vector of the per-step preconditioner set-up as the last nsx_prec_initialize left it on the device, so that the diagonal,
+ * its reciprocals, the lumped mass, the Schur weights and the Dirichlet mask can be compared with a reference on their own
+ * (tests/test_gpu_prec_setup.py).  values: a host vector of length n_u of the whole mesh in the caller's numbering, laid out as the velocity
+ * part of nsx_get_rhs; a distributed handle writes only its owned entries.  Read-only: a copy, no kernel beyond the one that undoes an
+ * internal layout.
+ *   NSX_PREC_VEC_D          D: diag(mass_matrix) (Yosida) or diag(F) (SIMPLE, aSIMPLE, aYosida), replicated on the dim components
+ *   NSX_PREC_VEC_D_INV      1 / D
+ *   NSX_PREC_VEC_NEG_D_INV  -1 / D
+ *   NSX_PREC_VEC_LUMP_M     -1 / sum_j |M_ij|: written by an aYosida initialisation only, otherwise what the last one left (0 at first)
+ *   NSX_PREC_VEC_SCHUR_W    the weights of the Schur product, w = -V * mask, V = -1 / D (aYosida: lump_M)
+ *   NSX_PREC_VEC_DIRMASK    1 = free, 0 = row constrained by nsx_apply_boundary_values since the last nsx_assemble
+ * NSX_ERR_ARG: null values, unknown `which`, before nsx_prec_initialize (DIRMASK: before the first assembly). */
+enum { NSX_PREC_VEC_D = 0, NSX_PREC_VEC_D_INV, NSX_PREC_VEC_NEG_D_INV, NSX_PREC_VEC_LUMP_M, NSX_PREC_VEC_SCHUR_W, NSX_PREC_VEC_DIRMASK,
+       NSX_PREC_VEC_COUNT };
+int nsx_prec_get_vector(nsx_handle *h, int which, double *values);
 
 /* ---- export in the reference's own layout (Trilinos block CSR with all velocity couplings stored) ---- */
 /* which: 0 system_matrix, 1 mass_matrix, 2 convection_matrix, 3 stiffness_matrix, 4 pressure_mass

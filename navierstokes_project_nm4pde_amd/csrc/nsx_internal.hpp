@@ -777,6 +777,7 @@ void part_from_caller(nsx_handle *h, int which, double *dev, const double *host)
 void part_to_caller(nsx_handle *h, int which, const double *dev, double *host);
 void pressure_from_caller(nsx_handle *h, double *dev, const double *host);  // one pressure vector, distributed handles too (globally indexed host, owned entries)
 void pressure_to_caller(nsx_handle *h, const double *dev, double *host);
+void velocity_to_caller(nsx_handle *h, const double *dev, double *host);  // one velocity vector [len_u], distributed handles too: the velocity part of vec_to_caller
 inline int32_t node_to_internal(const nsx_handle *h, int32_t local_node) { return h->layout_on ? h->perm2_h[local_node] : local_node; }
 inline int32_t pnode_to_internal(const nsx_handle *h, int32_t local_node) { return h->layout_on ? h->perm1_h[local_node] : local_node; }
 void ensure_schedules(nsx_handle *h);  // (re)build the ILU schedules if the rank / Schur block tables changed

@@ -311,6 +311,16 @@ void pressure_to_caller(nsx_handle *h, const double *dev, double *host) {
   for (int i = 0; i < h->NP; ++i) host[(size_t)h->goff_p + i] = loc[pnode_to_internal(h, i)];
 }
 
+void velocity_to_caller(nsx_handle *h, const double *dev, double *host) {
+  if (!h->dist) return part_to_caller(h, 0, dev, host);
+  const int dim = h->dim;
+  std::vector<double> loc(h->n_u);
+  HIP_CHECK(hipMemcpyAsync(loc.data(), dev, loc.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIP_CHECK(hipStreamSynchronize(h->stream));
+  for (int i = 0; i < h->N2; ++i)
+    for (int c = 0; c < dim; ++c) host[(size_t)dim * (h->goff_u + i) + c] = loc[(size_t)dim * node_to_internal(h, i) + c];
+}
+
 void vec_from_caller(nsx_handle *h, double *dev, const double *host, bool with_ghosts) {
   const int dim = h->dim;
   if (!h->dist) return io_from_caller(h, host, (size_t)h->n_u + h->n_p, {{0, dev}, {1, dev + h->off_p}});

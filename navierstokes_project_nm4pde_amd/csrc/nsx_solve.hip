@@ -716,6 +716,18 @@ int nsx_prec_initialize(nsx_handle *h, int prec_type) {
   NSX_CATCH(h)
 }
 
+int nsx_prec_get_vector(nsx_handle *h, int which, double *values) {
+  NSX_TRY(h)
+  if (!values) NSX_THROW(NSX_ERR_ARG, "null output");
+  if (which < 0 || which >= NSX_PREC_VEC_COUNT) NSX_THROW(NSX_ERR_ARG, "unknown set-up vector %d", which);
+  if (which == NSX_PREC_VEC_DIRMASK ? !h->assembled : !h->prec_ready)
+    NSX_THROW(NSX_ERR_ARG, which == NSX_PREC_VEC_DIRMASK ? "no Dirichlet mask: assemble first" : "no set-up vectors: call nsx_prec_initialize first");
+  HIP_CHECK(hipSetDevice(h->prm.device));
+  const nsx::DevBuf<double> *v[NSX_PREC_VEC_COUNT] = {&h->diag_D, &h->diag_D_inv, &h->neg_diag_D_inv, &h->lump_M, &h->schur_w, &h->dirmask};
+  nsx::velocity_to_caller(h, v[which]->p, values);
+  NSX_CATCH(h)
+}
+
 int nsx_prec_vmult(nsx_handle *h, int prec_type, double inner_rtol, int inner_maxiter, double *dst, const double *src, nsx_solve_stats *stats) {
   NSX_TRY(h)
   if (!dst || !src) NSX_THROW(NSX_ERR_ARG, "null vector");

@@ -27,7 +27,7 @@ API = [
     "nsx_set_internal_layout", "nsx_layout_info", "nsx_layout_get", "nsx_gram_schmidt_cycle", "nsx_set_inner_precision",
     "nsx_gram_schmidt_sweeps", "nsx_compute_diagnostics", "nsx_get_cell_diagnostic", "nsx_schur_cg", "nsx_blas1_run", "nsx_gmres",
     "nsx_set_probes", "nsx_get_probe_cells", "nsx_eval_probes", "nsx_set_tracers", "nsx_advect_tracers", "nsx_get_tracers",
-    "nsx_sparse_product", "nsx_compute_nodal_fields", "nsx_nodal_field_components", "nsx_get_nodal_field",
+    "nsx_sparse_product", "nsx_prec_get_vector", "nsx_compute_nodal_fields", "nsx_nodal_field_components", "nsx_get_nodal_field",
     "nsx_extract_isosurface", "nsx_get_isosurface",
     "nsx_set_lattice", "nsx_get_lattice_cells", "nsx_eval_lattice", "nsx_get_lattice",
     "nsx_stats_begin", "nsx_stats_accumulate", "nsx_stats_info", "nsx_stats_components", "nsx_stats_get",
@@ -42,6 +42,8 @@ INNER_FP64, INNER_FP32 = 0, 1  # nsx_set_inner_precision: how F and the ILU(0) e
 DIAG_ENERGY, DIAG_DIV2, DIAG_GRAD2, DIAG_ENSTROPHY, DIAG_CHANGE2, DIAG_VOLUME, DIAG_CFL, DIAG_SPEED, DIAG_COUNT = range(9)
 # ops of nsx_sparse_product (NSX_PROD_*)
 PROD_F, PROD_F_INNER, PROD_F_RESID, PROD_MASS, PROD_B, PROD_B_MINUS_R, PROD_R_MINUS_B, PROD_G, PROD_G_ACC, PROD_S, PROD_SADDLE, PROD_COUNT = range(12)
+# vectors of nsx_prec_get_vector (NSX_PREC_VEC_*)
+PREC_VEC_D, PREC_VEC_D_INV, PREC_VEC_NEG_D_INV, PREC_VEC_LUMP_M, PREC_VEC_SCHUR_W, PREC_VEC_DIRMASK, PREC_VEC_COUNT = range(7)
 TRACER_EULER, TRACER_RK2, TRACER_RK4 = 1, 2, 4                                   # NSX_TRACER_*: scheme
 TRACER_FROZEN, TRACER_LINEAR = 0, 1                                              # field
 TRACER_NOT_FOUND, TRACER_ACTIVE, TRACER_EXITED, TRACER_LOST = 0, 1, 2, 3         # status
@@ -214,6 +216,7 @@ def lib():
     L.nsx_inner_F_vmult.argtypes = [vp, _f64p, _f64p]
     L.nsx_schur_cg.argtypes = [vp, C.c_double, C.c_int, _f64p, _f64p, C.POINTER(C.c_int), _f64p, C.POINTER(C.c_int)]
     L.nsx_sparse_product.argtypes = [vp, C.c_int, _f64p, _f64p, _f64p]
+    L.nsx_prec_get_vector.argtypes = [vp, C.c_int, _f64p]
     L.nsx_gmres.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_int, _f64p, _f64p, _f64p, C.POINTER(C.c_int), _f64p]
     L.nsx_blas1_run.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, _f64p, C.c_int, C.POINTER(Blas1Op), _f64p, _f64p, C.c_int]
     L._nsx_ready = True
@@ -520,6 +523,13 @@ class Nsx:
         dst = np.zeros_like(x)
         self._ck(self.L.nsx_sparse_product(self._h, int(op), _d(dst), _d(x), None if aux is None else _d(aux)))
         return dst
+
+    def prec_vector(self, which):
+        """nsx_prec_get_vector: one vector of the preconditioner set-up (PREC_VEC_*) as the last prec_initialize left it, length n_u in the
+        caller's numbering.  Distributed handles: global-sized, the entries this rank owns filled, the rest 0."""
+        v = np.zeros(self.n_u)
+        self._ck(self.L.nsx_prec_get_vector(self._h, int(which), _d(v)))
+        return v
 
     def ilu_apply(self, which, src):
         src = _cd(src)
