@@ -546,9 +546,8 @@ extern "C" int nsx_path_info(nsx_handle *h, int info[32]) {
   // masked ones; 0 = the resident grid does not hold the vector
   if (!h->mgs.disabled) {
     nsx::mgs_setup(h);
-    const int es[3] = {8, 10, 12};
     auto fit = [&](int n, const int *caps, int n_inst) {
-      const nsx::MgsPick p = nsx::mgs_pick(n, caps, n_inst, es);
+      const nsx::MgsPick p = nsx::mgs_pick(n, caps, n_inst, nsx::MGS_ENTRIES);
       return p.fits() ? p.e : 0;
     };
     info[16] = fit(h->n_u, h->mgs.max_wg_dist, 1);

@@ -1,5 +1,5 @@
 // nsx_grid.hpp — device-side pieces shared by the persistent (one launch, grid-wide exchanges) kernels:
-// the Gram-Schmidt sweep k_mgs (nsx_mgs.hip) and the Schur-complement CG k_cg_schur (nsx_cg.hip).
+// the Gram-Schmidt sweep k_mgs_one (nsx_mgs.hip) and the Schur-complement CG k_cg_schur (nsx_cg.hip).
 //
 // A grid-wide sum without atomics on shared counters: workgroup b stores the BIT PATTERN of its partial sum in
 // mailbox[b] (initially GX_EMPTY), workgroup 0 waits for all of them, adds them in a fixed order and stores the total in

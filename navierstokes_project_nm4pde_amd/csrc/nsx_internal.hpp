@@ -309,11 +309,10 @@ struct MgsState {
   // ---- per handle: allocated / read from the environment once (mgs_setup, mgs_lowsync), given up by mgs_recover after a time-out
   GridBox box;                         // persistent sweep: mailbox regions, then one commit word per workgroup
   int max_wg = 0;                      // 0: the launch-per-link chain is used
-  int used_wg[2] = {0, 0}, used_steps[2] = {0, 0};  // what the last launch on each region filled (the sweep's own clearing protocol)
-  int max_wg_e[3] = {0, 0, 0};         // resident-grid limit of the 8 / 10 / 12 (link-by-link variants: 20) entries-per-thread instantiations
+  int used_words[2] = {0, 0};          // mailbox words the last launch on each region filled (the sweep's own clearing protocol)
+  int max_wg_e[3] = {0, 0, 0};         // resident-grid limits of k_mgs_one's instantiations, MGS_ENTRIES[k] entries per thread
   int max_wg_dist[3] = {0, 0, 0};      // resident-grid limits of the distributed instantiations (8 / 10 / 12 entries per thread), room left for the collective
   int dist_cap_reserved[3] = {0, 0, 0};  // grid limits of the distributed sweep's instantiations on the masked compute stream
-  int links = 0;                       // links of the add_and_dot chain per grid-wide exchange (NSX_MGS_LINKS; 0 = all of them: k_mgs_one, 1 = k_mgs)
   bool disabled = false;
   double guard_override = -1.0;        // >= 0: threshold of the Gram formula for |w'|^2 for the duration of nsx_gram_schmidt_cycle
   // distributed sweep with two collectives (mgs_lowsync): partial sums / all-reduced values / one 32 x 32 Gram matrix per GMRES nesting level
@@ -324,7 +323,6 @@ struct MgsState {
   DevBuf<unsigned long long> ext_words;  // [0] release flag, [1] arrival counter (32 bits used), [2] the sweep the grid gave up on
   unsigned int ext_expected = 0;
   int ext_parity = 0;
-  bool redo_ahead = false;             // a sweep fell back to the chain after work depending on its w had been enqueued (read and cleared by the GMRES driver)
   // ---- per communicator: what the ranks chose together (krylov_new_communicator / krylov_communicator_gone; dist_fit also krylov_new_schedules)
   int dist_state = -1;                 // -1 not decided yet, 0 two-pass sweep (mgs_lowsync), 1 the collective inside the persistent grid
   std::map<int, int> dist_fit;         // role of the vector in the solve (mgs_role) -> do ALL ranks' resident grids hold their vector of that role (agreed once per role; asked again when the sizes change)
@@ -873,11 +871,19 @@ void v_dot(nsx_handle *h, Span n, const double *a, const double *b, int slot);  
 void v_add_and_dot(nsx_handle *h, Span n, double *d, double a, int aslot, const double *v, const double *w, int slot);
                                                                                             // d += a*scal[aslot]*v ; scal[slot] = d.w
 // modified Gram-Schmidt sweep of SolverGMRES (w against v_0..v_{dim-1}): out[i] = h(i), out[dim] = |w|^2 afterwards (host
-// values; scal[slot0+i] holds them too).  normalize: also w *= 1/|w| if the sweep runs as one launch; returns whether it did.
+// values; scal[slot0+i] holds them too).  normalize: also w *= 1/|w| if the sweep runs as one launch; `normalized` says whether it did.
 // after_launch (optional) runs between the launch and the wait for the coefficients, only when the sweep is one launch
-// AND normalises w: the caller may enqueue work that depends on the finished w alone.
-bool v_mgs(nsx_handle *h, Span n, double *w, int dim, double *const *vs, int slot0, bool normalize, double *out,
-           const std::function<void()> *after_launch = nullptr, bool consider = false, double *gram = nullptr, const double *ilu_rhs = nullptr);
+// AND normalises w: the caller may enqueue work that depends on the finished w alone.  ahead_stale: after_launch ran, but w was not
+// final then after all (the sweep was redone without the persistent grid, or its norm came later): what it enqueued must be redone.
+struct MgsResult {
+  bool normalized = false, ahead_stale = false;
+};
+MgsResult v_mgs(nsx_handle *h, Span n, double *w, int dim, double *const *vs, int slot0, bool normalize, double *out,
+                const std::function<void()> *after_launch = nullptr, bool consider = false, double *gram = nullptr, const double *ilu_rhs = nullptr);
+// SolverGMRES' re-orthogonalisation test: a second sweep is asked for when the first one left |vv| <= 10 |vv_start| sqrt(eps), sqrt(eps) = 2^-26
+// exactly.  nrm = |vv| after the sweep, norm0_sq = |vv_start|^2.  ONE expression for the sweep kernels, v_mgs and gmres(): they must agree to the bit.
+__host__ __device__ inline bool mgs_wants_second_sweep(double nrm, double norm0_sq) { return !(nrm > 10. * sqrt(norm0_sq) * 1.4901161193847656e-08); }
+double *mgs_gram(nsx_handle *h, int depth);  // the Gram matrix (32 x 32) of the basis of the GMRES solve at nesting level depth < 4; allocated and zeroed by the first call
 // ilu_rhs: the sweep's input is w = (LU_F)^-1 ilu_rhs, computed first (inside the sweep's own launch where possible: k_ilu_mgs)
 // consider: also out[dim+1] = |w|^2 BEFORE the sweep (SolverGMRES' re-orthogonalisation test); a single-launch sweep then
 // normalises w only if the test does not ask for a second sweep.
@@ -918,6 +924,7 @@ struct MgsPick {
   int e = 0, nwg = 1, per_thread = 1 << 30;  // entries per thread of the instantiation (0: none available), grid, entries a thread has to take
   bool fits() const { return e != 0 && per_thread <= e; }
 };
+constexpr int MGS_ENTRIES[3] = {8, 10, 12};  // entries per thread of k_mgs_one's instantiations (mgs_one_fn)
 MgsPick mgs_pick(int n, const int *caps, int n_inst, const int *es);
 // persistent CG on the Schur complement (nsx_cg.hip); false: not applicable here, use the launch-per-operation solver
 void build_cg_plan(nsx_handle *h);   // with the ILU schedules

@@ -1,5 +1,5 @@
 // nsx_mgs.hip — the modified Gram-Schmidt sweep of the GMRES drivers (deal.II's SolverGMRES orthogonalisation of the new Krylov
-// vector against the basis): the persistent kernels (k_mgs, k_mgs_blk, k_mgs_one, k_ilu_mgs), the two-pass distributed sweep
+// vector against the basis): the persistent kernels (k_mgs_one, k_ilu_mgs), the two-pass distributed sweep
 // (k_ls_*, mgs_lowsync), their set-up, their recovery after a time-out, and the host driver v_mgs that chooses among them.
 // The launch-per-link chain it falls back to is made of the BLAS-1 reductions of nsx_blas.hip.
 #include "nsx_grid.hpp"
@@ -11,18 +11,26 @@ namespace nsx {
 // deal.II's SolverGMRES orthogonalises the new Krylov vector w with the chain  h(0) = w.v_0 ;
 // h(i+1) = w.add_and_dot(-h(i), v_i, v_{i+1}) ; |w|^2 = w.add_and_dot(-h(dim-1), v_{dim-1}, w): dim+1 dependent global
 // reductions.  As separate launches every link streams w (read + write) and two basis vectors, 32 B per entry; here the
-// grid is co-resident, every thread keeps its entries of w and of the current v_i in registers for the whole sweep, and a
-// link costs ONE read of the next basis vector (8 B per entry, prefetched before the wait) plus a grid-wide exchange of
-// the partial sums (nsx_grid.hpp: mailboxes, no atomics on shared counters): workgroup 0 waits for all mailboxes, adds them
-// in a fixed order and publishes the total, which every workgroup picks up.  (Letting every workgroup read all mailboxes
-// itself — one hop instead of two — measured slower: 60 against 50 us per sweep, the polling traffic gets in its own way.)
+// grid is co-resident, every thread keeps its entries of w and of the newest basis vectors in registers for the whole sweep,
+// every basis vector is read once (8 B per entry; the oldest ones twice when the block does not fit), and ALL links share one
+// grid-wide exchange of partial sums (nsx_grid.hpp: mailboxes, no atomics on shared counters; the algebra is at k_mgs_one).
 // The arithmetic of each entry is that of the chain (w += (-h) v_i), sums are fixed-order, so results do not depend on
 // timing.  Every wait is bounded by a wall-clock timeout: a grid that is not co-resident (another stream or process holds
 // compute units) ends without touching w, and the host falls back to the launch-per-link chain (v_mgs).
 constexpr int MGS_MAX_WG = 512;
-constexpr int MGS_STEPS = 32;     // mailbox rows / basis pointers of one sweep
+constexpr int MGS_STEPS = 32;     // basis pointers of one sweep; a sweep against dim vectors is taken for dim + 2 <= MGS_STEPS
 static_assert(MGS_STEPS >= KRYLOV_N_TMP + 2, "a sweep against dim vectors needs dim + 2 rows");
-constexpr size_t MGS_REGION = (size_t)MGS_STEPS * MGS_MAX_WG + MGS_STEPS;  // words per mailbox region (+ the totals)
+// Mailbox region of one sweep (h->mgs.box holds two, used in turn): the single exchange carries r_j and g_j (j < MGS_STEPS - 2),
+// |w|^2 before the sweep and, in the second exchange, |w|^2 after it.  Value v of workgroup wg sits at box[v * nwg + wg]
+// (nwg <= MGS_MAX_WG), the grid totals behind all mailboxes at box[MGS_ONE_VALS * MGS_MAX_WG + v].
+constexpr int MGS_ONE_VALS = 2 * (MGS_STEPS - 2) + 2;  // r_j, g_j (j < 30), |w|^2 before, |w|^2 after (second exchange)
+// words per region: the mailboxes, then the totals, rounded up to 512 bytes so that the second region and the commit words behind it start on
+// a cache line as the first one does (31 806 words would put them 48 bytes into one; bench.py, three runs each: 14.75 - 14.83 time steps per
+// second unrounded, 14.86 - 15.00 rounded, against 14.86 - 14.98 for the 57 408-word regions this one replaced, also a multiple of 512 bytes)
+constexpr size_t MGS_BOX_REGION = ((size_t)MGS_ONE_VALS * MGS_MAX_WG + MGS_ONE_VALS + 63) / 64 * 64;
+static_assert(2 * (MGS_STEPS - 2) + 1 < MGS_ONE_VALS, "the largest value index of a sweep (2 dim + 1, dim = MGS_STEPS - 2) needs a mailbox row and a total");
+static_assert((size_t)MGS_ONE_VALS * MGS_MAX_WG + MGS_ONE_VALS <= MGS_BOX_REGION,
+              "k_mgs_one and k_ilu_mgs put their MGS_ONE_VALS totals behind MGS_ONE_VALS rows of MGS_MAX_WG mailboxes: all of it lies inside a region");
 // after the two mailbox regions: one word per workgroup = sequence number of the last sweep whose part of w it wrote back
 // (distinct addresses: a shared counter would serialise 512 atomics at the end of every sweep)
 constexpr size_t MGS_TAIL = MGS_MAX_WG;
@@ -31,20 +39,13 @@ struct MgsArgs {
   const double *v[MGS_STEPS];
 };
 
-// ---- pieces every persistent sweep kernel has
+// ---- pieces both persistent sweep kernels have
 // SolverGMRES' re-orthogonalisation test: a second sweep is asked for when the first one left |vv| <= 10 |vv_start| sqrt(eps), sqrt(eps) = 2^-26.
-// The kernels normalise w only if it does not; the host (v_mgs) takes the same decision from the same two numbers.
-__host__ __device__ inline bool mgs_wants_second_sweep(double nrm, double norm0_sq) { return !(nrm > 10. * sqrt(norm0_sq) * 1.4901161193847656e-08); }
-// (The prologue -- idx[k] = the thread's k-th entry of the span, wv[k] = w there -- stays pasted in the kernels: as an inlined helper it
-// costs k_mgs_one<8, 10, true> eight more spilled SGPRs and reorders the instruction streams of k_mgs and k_mgs_blk<20, 5, false>.)
-// the end of a sweep that went through: this workgroup commits its part of w (tail[wg] = seq) and writes it back (k_mgs, k_mgs_blk)
-template <int E>
-__device__ __forceinline__ void mgs_commit_w(unsigned long long *tail, int wg, unsigned long long seq, double *w, const int (&idx)[E], const double (&wv)[E]) {
-  if (threadIdx.x == 0) tail[wg] = seq;
-#pragma unroll
-  for (int k = 0; k < E; ++k)
-    if (idx[k] >= 0) w[idx[k]] = wv[k];
-}
+// The kernels normalise w only if it does not; the host (v_mgs, gmres) takes the same decision from the same two numbers: mgs_wants_second_sweep
+// (nsx_internal.hpp).
+// (The prologue -- idx[k] = the thread's k-th entry of the span, wv[k] = w there -- and the commit at the end -- tail[wg] = seq, then w written
+// back -- stay pasted in the kernels: as an inlined helper the prologue costs k_mgs_one<8, 10, true> eight more spilled SGPRs, and the commit as
+// a call changes the instruction streams of the 10- and 12-entry instantiations.)
 // the end of a sweep that gave up (a bounded wait ran out): w stays as it was.  Tell the host (mapped word) and, from workgroup 0, wake it up
 __device__ __forceinline__ void mgs_give_up(int *err_host, unsigned long long *pub_flag, unsigned long long seq, int wg) {
   if (threadIdx.x == 0) {
@@ -55,128 +56,6 @@ __device__ __forceinline__ void mgs_give_up(int *err_host, unsigned long long *p
     }
   }
 }
-
-template <int E>
-__global__ __launch_bounds__(256) void k_mgs(int n, int split, int gap, double *__restrict__ w, MgsArgs V, int dim,
-                                             unsigned long long *box, unsigned long long *box_next, int reset_wg, int reset_steps,
-                                             double *__restrict__ scal_out, int *err_host, unsigned long long *tail, int normalize, int consider,
-                                             double *pub_vals, unsigned long long *pub_flag, unsigned long long seq, int drop_wg) {
-  __shared__ double sh[2][4];  // two buffers: a wave may start the next sum while a slower one still reads this one
-  __shared__ unsigned long long bc;
-  __shared__ int s_err;  // raised by any thread whose wait timed out; read after the next barrier
-  __shared__ double tots[MGS_STEPS];
-  const int nwg = gridDim.x, wg = blockIdx.x, T = nwg * 256, t = wg * 256 + threadIdx.x;
-  if (threadIdx.x == 0) s_err = 0;
-  unsigned long long *total = box + (size_t)MGS_STEPS * MGS_MAX_WG, *total_next = box_next + (size_t)MGS_STEPS * MGS_MAX_WG;
-  // leave the other region empty for the next launch (stream order makes this visible to it): its last user filled
-  // reset_steps rows of reset_wg mailboxes, possibly more than this grid has workgroups
-  for (int q = t; q < reset_steps * reset_wg; q += T) box_next[(size_t)(q / reset_wg) * MGS_MAX_WG + q % reset_wg] = GX_EMPTY;
-  if (wg == 0 && threadIdx.x < MGS_STEPS) total_next[threadIdx.x] = GX_EMPTY;
-  double wv[E], vc[E], vn[E];
-  int idx[E];
-#pragma unroll
-  for (int k = 0; k < E; ++k) {
-    const int i0 = t + k * T;
-    idx[k] = i0 < n ? i0 + (i0 >= split ? gap : 0) : -1;
-    wv[k] = idx[k] >= 0 ? w[idx[k]] : 0.0;
-    vc[k] = idx[k] >= 0 ? ld_stream<1>(V.v[0] + idx[k]) : 0.0;
-    vn[k] = 0.0;
-  }
-  // consider: SolverGMRES' re-orthogonalisation test (every 5th inner iteration) needs |w| BEFORE the sweep: one more link
-  // in front (mailbox row dim + 1), and the decision whether w may be normalised is taken here exactly as the host takes it
-  double norm0_sq = 0.0;
-  int lerr = 0;
-  bool dead = false;
-  for (int s = consider ? -1 : 0; s <= dim; ++s) {
-    const bool pre = s < 0;
-    const int ri = pre ? dim + 1 : s;
-    double acc = 0.0;
-#pragma unroll
-    for (int k = 0; k < E; ++k) acc += wv[k] * ((!pre && s < dim) ? vc[k] : wv[k]);
-    const double part = gx_block_sum(acc, sh[0]);
-    unsigned long long *row = box + (size_t)ri * MGS_MAX_WG;
-    if (threadIdx.x == 0 && wg != drop_wg) gx_post(row + wg, part);  // drop_wg >= 0: fault injection (NSX_GX_DROP_WG), a workgroup that never arrives
-    if (wg == 0) {
-      double a = 0.0;
-      for (int q = threadIdx.x; q < nwg; q += 256) a += gx_wait_value(row + q, &lerr);
-      if (lerr) s_err = 1;
-      const double tot = gx_block_sum(a, sh[1]);
-      // a total built on a timed-out mailbox must never go out: the others then time out as well and nobody writes w
-      if (threadIdx.x == 0 && !s_err) {
-        scal_out[ri] = tot;
-        gx_post(total + ri, tot);
-        tots[ri] = tot;
-      }
-    }
-    // The next basis vector is fetched while the sums are exchanged.  Its loads are issued AFTER this workgroup's partial sum
-    // (and, in workgroup 0, the total) has gone out and after the first poll: issued in front, they queue ahead of the exchange's
-    // own traffic (tools/exchange_bench.hip: 3.2 against 3.0 us per link at 512 workgroups x 8 loads per thread)
-    unsigned long long first = GX_EMPTY;
-    if (threadIdx.x == 0) first = gx_load(total + ri);
-    if (!pre && s + 1 < dim) {
-      const double *__restrict__ vp = V.v[s + 1];
-#pragma unroll
-      for (int k = 0; k < E; ++k) vn[k] = idx[k] >= 0 ? ld_stream<1>(vp + idx[k]) : 0.0;
-    }
-    if (threadIdx.x == 0) {
-      bc = first != GX_EMPTY ? first : gx_wait(total + ri, &lerr);
-      if (lerr) s_err = 1;
-    }
-    __syncthreads();
-    dead = s_err != 0;
-    const double hs = __longlong_as_double((long long)bc);
-    if (dead) break;
-    if (pre) {
-      norm0_sq = hs;
-      continue;
-    }
-    if (s < dim) {
-      const double alpha = -1.0 * hs;
-#pragma unroll
-      for (int k = 0; k < E; ++k) {
-        wv[k] += alpha * vc[k];
-        vc[k] = vn[k];
-      }
-    } else if (normalize) {  // vv *= 1. / s with s = sqrt(|vv|^2), skipped for s == 0 (SolverGMRES)
-      const double nrm = sqrt(hs);
-      const bool second_sweep = consider && mgs_wants_second_sweep(nrm, norm0_sq);  // then no normalisation
-      if (nrm != 0.0 && !second_sweep) {
-        const double inv = 1. / nrm;
-#pragma unroll
-        for (int k = 0; k < E; ++k) wv[k] = inv * wv[k];
-      }
-    }
-  }
-  if (dead) {
-    mgs_give_up(err_host, pub_flag, seq, wg);
-    return;
-  }
-  // hand the coefficients to the host: values, then the flag it is polling, both in fine-grained mapped host memory.  The
-  // stores are acknowledged (vmcnt) before the flag goes out; a system-scope release would also write back the whole L2.
-  if (wg == 0) {
-    __syncthreads();
-    if ((int)threadIdx.x <= dim + (consider ? 1 : 0)) __hip_atomic_store(pub_vals + threadIdx.x, tots[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) __hip_atomic_store(pub_flag, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
-  mgs_commit_w<E>(tail, wg, seq, w, idx, wv);
-}
-
-// ---- the same sweep with M links per grid-wide exchange ---------------------------------------------------------------
-// The chain's coefficients are h_j = v_j . w_j with w_{j+1} = w_j - h_j v_j.  For the links j0 .. j0+M-1 of a block, by
-// linearity of the dot product (no orthogonality of the basis is assumed),
-//     h_j = v_j . (w_{j0} - sum_{j0 <= i < j} h_i v_i) = r_j - sum_{j0 <= i < j} (v_i . v_j) h_i ,   r_j = v_j . w_{j0} :
-// the M numbers r_j and the M (M-1) / 2 numbers v_i . v_j are sums over the SAME registers (the block's M basis vectors and
-// w_{j0} are held by the thread), so they travel in ONE exchange, workgroup 0 solves the unit lower-triangular M x M system
-// and hands out h_{j0..j0+M-1}, and every thread applies w += (-h_j) v_j for j ascending exactly as the chain does.  The
-// entries of w see the chain's operations in the chain's order; the coefficients differ from the chain's by the rounding
-// of the dot products only (identical in exact arithmetic, whatever the basis).  A sweep of `dim` links costs
-// ceil(dim / M) + 1 exchanges instead of dim + 1 (tools/exchange_bench.hip: 2.4 - 3.7 us each).  M = 1 is k_mgs.
-// Mailboxes: value-major, box[(x * NV + v) * nwg + wg] for exchange x, so workgroup 0 reads them coalesced.
-constexpr int MGS_BLK_TOT = 64;  // words reserved for the totals of a region ((M + 1) per exchange)
-constexpr size_t MGS_BLK_REGION = 57344 + MGS_BLK_TOT;  // (ceil(28 / M) + 1) * NV * 512 words for M <= 5, + the totals
-constexpr size_t MGS_BOX_REGION = MGS_REGION > MGS_BLK_REGION ? MGS_REGION : MGS_BLK_REGION;  // words of either mailbox region of h->mgs.box: every variant fits
 
 #ifdef NSX_MGS_TRACE  // development only (tools/mgs_bench.hip): wall-clock stamps of workgroup 0 and of the last workgroup
 __device__ unsigned long long *g_mgs_trace = nullptr;
@@ -191,258 +70,30 @@ __device__ unsigned long long *g_mgs_trace = nullptr;
   } while (0)
 #endif
 
-template <int E, int M, bool PF>
-__global__ __launch_bounds__(256) void k_mgs_blk(int n, int split, int gap, double *__restrict__ w, MgsArgs V, int dim, unsigned long long *box,
-                                                 unsigned long long *box_next, int reset_words, double *__restrict__ scal_out, int *err_host,
-                                                 unsigned long long *tail, int normalize, int consider, double *pub_vals,
-                                                 unsigned long long *pub_flag, unsigned long long seq, int drop_wg) {
-  constexpr int NP = M * (M - 1) / 2, NV = M + NP + 1;  // r_0..r_{M-1}, pairs (i < j) at M + j (j - 1) / 2 + i, |w|^2 before the sweep
-  __shared__ double sh[4][NV];
-  __shared__ double bc[M + 1];
-  __shared__ int s_err;
-  __shared__ double tots[MGS_STEPS + 2];
-  const int nwg = gridDim.x, wg = blockIdx.x, T = nwg * 256, t = wg * 256 + threadIdx.x;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  [[maybe_unused]] int n_stamp = 0;
-  MGS_STAMP();
-  if (threadIdx.x == 0) s_err = 0;
-  unsigned long long *total = box + (MGS_BLK_REGION - MGS_BLK_TOT), *total_next = box_next + (MGS_BLK_REGION - MGS_BLK_TOT);
-  for (int q = t; q < reset_words; q += T) box_next[q] = GX_EMPTY;
-  if (wg == 0 && threadIdx.x < MGS_BLK_TOT) total_next[threadIdx.x] = GX_EMPTY;
-  double wv[E], vb[M][E], vn[PF ? M : 1][PF ? E : 1];
-  int idx[E];
-#pragma unroll
-  for (int k = 0; k < E; ++k) {
-    const int i0 = t + k * T;
-    idx[k] = i0 < n ? i0 + (i0 >= split ? gap : 0) : -1;
-    wv[k] = idx[k] >= 0 ? w[idx[k]] : 0.0;
-  }
-  auto load_block = [&](double (&dst)[M][E], int j0) {
-#pragma unroll
-    for (int i = 0; i < M; ++i) {
-      if (j0 + i < dim) {
-        const double *__restrict__ vp = V.v[j0 + i];
-#pragma unroll
-        for (int k = 0; k < E; ++k) dst[i][k] = idx[k] >= 0 ? ld_stream<1>(vp + idx[k]) : 0.0;
-      } else {
-#pragma unroll
-        for (int k = 0; k < E; ++k) dst[i][k] = 0.0;
-      }
-    }
-  };
-  load_block(vb, 0);
-  const int nblk = (dim + M - 1) / M;
-  double norm0_sq = 0.0;
-  int lerr = 0;
-  bool dead = false;
-  for (int x = 0; x <= nblk; ++x) {
-    const bool last = x == nblk;
-    const int j0 = x * M, mb = last ? 0 : (dim - j0 < M ? dim - j0 : M);
-    const bool pre = x == 0 && consider;
-    // which of the NV values this exchange carries (wave-uniform)
-    unsigned int used = last ? 1u : ((1u << mb) - 1u) | (((1u << (mb * (mb - 1) / 2)) - 1u) << M) | (pre ? 1u << (NV - 1) : 0u);
-    double acc[NV];
-#pragma unroll
-    for (int v = 0; v < NV; ++v) acc[v] = 0.0;
-    if (last) {
-#pragma unroll
-      for (int k = 0; k < E; ++k) acc[0] += wv[k] * wv[k];
-    } else {
-#pragma unroll
-      for (int i = 0; i < M; ++i)
-        if (i < mb) {
-#pragma unroll
-          for (int k = 0; k < E; ++k) acc[i] += wv[k] * vb[i][k];
-#pragma unroll
-          for (int i2 = 0; i2 < i; ++i2) {
-#pragma unroll
-            for (int k = 0; k < E; ++k) acc[M + i * (i - 1) / 2 + i2] += vb[i2][k] * vb[i][k];
-          }
-        }
-      if (pre) {
-#pragma unroll
-        for (int k = 0; k < E; ++k) acc[NV - 1] += wv[k] * wv[k];
-      }
-    }
-    // fixed-order sums over the workgroup, one barrier for all values
-#pragma unroll
-    for (int v = 0; v < NV; ++v)
-      if (used >> v & 1u) {
-        const double s = gx_wave_sum(acc[v]);
-        if (lane == 0) sh[wave][v] = s;
-      }
-    __syncthreads();
-    MGS_STAMP();  // local sums done (the block's loads have arrived)
-    unsigned long long *xbox = box + (size_t)x * NV * nwg;
-    if (threadIdx.x < NV && (used >> threadIdx.x & 1u) && wg != drop_wg) {  // drop_wg: fault injection, see k_mgs
-      const int v = threadIdx.x;
-      gx_post(xbox + (size_t)v * nwg + wg, (sh[0][v] + sh[1][v]) + (sh[2][v] + sh[3][v]));
-    }
-    unsigned long long *xtot = total + x * (M + 1);
-    if (wg == 0) {
-      __syncthreads();  // sh is reused below
-      double a[NV];
-#pragma unroll
-      for (int v = 0; v < NV; ++v) a[v] = 0.0;
-      for (int q = threadIdx.x; q < nwg; q += 256) {
-        unsigned long long b[NV], t0 = 0;
-        for (unsigned int spin = 1;; ++spin) {
-          bool all = true;
-#pragma unroll
-          for (int v = 0; v < NV; ++v)
-            if (used >> v & 1u) b[v] = gx_load(xbox + (size_t)v * nwg + q);
-#pragma unroll
-          for (int v = 0; v < NV; ++v)
-            if (used >> v & 1u) all = all && b[v] != GX_EMPTY;
-          if (all) break;
-          __builtin_amdgcn_s_sleep(1);
-          if ((spin & 255u) == 0) {
-            const unsigned long long now = wall_clock64();
-            if (t0 == 0) t0 = now;
-            else if (now - t0 > GX_TIMEOUT_TICKS) {
-              lerr = 1;
-              break;
-            }
-          }
-        }
-        if (lerr) break;
-#pragma unroll
-        for (int v = 0; v < NV; ++v)
-          if (used >> v & 1u) a[v] += __longlong_as_double((long long)b[v]);
-      }
-      if (lerr) s_err = 1;
-#pragma unroll
-      for (int v = 0; v < NV; ++v)
-        if (used >> v & 1u) {
-          const double s = gx_wave_sum(a[v]);
-          if (lane == 0) sh[wave][v] = s;
-        }
-      __syncthreads();
-      // a coefficient built on a timed-out mailbox must never go out: the others then time out as well and nobody writes w
-      if (threadIdx.x == 0 && !s_err) {
-        double tv[NV];
-#pragma unroll
-        for (int v = 0; v < NV; ++v) tv[v] = (used >> v & 1u) ? (sh[0][v] + sh[1][v]) + (sh[2][v] + sh[3][v]) : 0.0;
-        if (last) {
-          scal_out[dim] = tv[0];
-          gx_post(xtot, tv[0]);
-          tots[dim] = tv[0];
-        } else {
-          double hc[M];
-#pragma unroll
-          for (int j = 0; j < M; ++j) {
-            double s = tv[j];
-#pragma unroll
-            for (int i = 0; i < j; ++i) s -= tv[M + j * (j - 1) / 2 + i] * hc[i];
-            hc[j] = s;
-            if (j < mb) {
-              scal_out[j0 + j] = s;
-              gx_post(xtot + j, s);
-              tots[j0 + j] = s;
-            }
-          }
-          if (pre) {
-            scal_out[dim + 1] = tv[NV - 1];
-            gx_post(xtot + M, tv[NV - 1]);
-            tots[dim + 1] = tv[NV - 1];
-          }
-        }
-      }
-    }
-    MGS_STAMP();  // posted (workgroup 0: coefficients out)
-    // the next block of basis vectors is fetched while the sums are exchanged (behind this workgroup's post and first poll,
-    // see k_mgs)
-    const int nw = last ? 1 : mb + (pre ? 1 : 0);  // words to pick up: h of the block (+ |w|^2 before the sweep in word M)
-    unsigned long long first = GX_EMPTY;
-    const int myword = (int)threadIdx.x < (last ? 1 : mb) ? (int)threadIdx.x : M;
-    if ((int)threadIdx.x < nw) first = gx_load(xtot + myword);
-    if constexpr (PF) {
-      if (!last && x + 1 < nblk) load_block(vn, j0 + M);
-    }
-    if ((int)threadIdx.x < nw) {
-      const unsigned long long b = first != GX_EMPTY ? first : gx_wait(xtot + myword, &lerr);
-      if (lerr) s_err = 1;
-      bc[myword] = __longlong_as_double((long long)b);
-    }
-    __syncthreads();
-    MGS_STAMP();  // coefficients picked up
-    dead = s_err != 0;
-    if (dead) break;
-    if (last) {
-      if (normalize) {  // vv *= 1. / s with s = sqrt(|vv|^2), skipped for s == 0 (SolverGMRES)
-        const double nrm = sqrt(bc[0]);
-        const bool second_sweep = consider && mgs_wants_second_sweep(nrm, norm0_sq);  // then no normalisation
-        if (nrm != 0.0 && !second_sweep) {
-          const double inv = 1. / nrm;
-#pragma unroll
-          for (int k = 0; k < E; ++k) wv[k] = inv * wv[k];
-        }
-      }
-    } else {
-      if (pre) norm0_sq = bc[M];
-#pragma unroll
-      for (int i = 0; i < M; ++i)
-        if (i < mb) {
-          const double alpha = -1.0 * bc[i];
-#pragma unroll
-          for (int k = 0; k < E; ++k) wv[k] += alpha * vb[i][k];
-        }
-      if (x + 1 < nblk) {
-        if constexpr (PF) {
-#pragma unroll
-          for (int i = 0; i < M; ++i)
-#pragma unroll
-            for (int k = 0; k < E; ++k) vb[i][k] = vn[i][k];
-        } else {
-          load_block(vb, j0 + M);
-        }
-      }
-    }
-    __syncthreads();  // bc and sh are rewritten by the next exchange
-  }
-  if (dead) {
-    mgs_give_up(err_host, pub_flag, seq, wg);
-    return;
-  }
-  if (wg == 0) {
-    if ((int)threadIdx.x <= dim + (consider ? 1 : 0)) __hip_atomic_store(pub_vals + threadIdx.x, tots[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) __hip_atomic_store(pub_flag, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
-  mgs_commit_w<E>(tail, wg, seq, w, idx, wv);
-  MGS_STAMP();
-}
-
 // ---- the whole sweep in ONE grid-wide exchange ---------------------------------------------------------------------------
-// The linearity that k_mgs_blk uses for M links of the chain holds for all of them:  h_j = r_j - sum_{i<j} G_ji h_i  with
-// r_j = v_j . w (the vector as it ENTERS the sweep) and G the Gram matrix of the basis (no orthogonality assumed).  G is kept
+// The chain's coefficients are h_j = v_j . w_j with w_{j+1} = w_j - h_j v_j and w_0 = w, the vector as it ENTERS the sweep.  By
+// linearity of the dot product (no orthogonality of the basis is assumed)
+//     h_j = v_j . (w - sum_{i<j} h_i v_i) = r_j - sum_{i<j} G_ji h_i ,   r_j = v_j . w ,   G_ji = v_j . v_i  (the basis' Gram matrix):
+// a unit-lower-triangular system whose data are sums over vectors that do not change during the sweep.  G is kept
 // on the device per GMRES nesting level: the sweep that meets v_{dim-1} for the first time computes its row g_i = v_{dim-1} . v_i
 // beside the r_j (the same registers), all older rows were computed by the earlier sweeps of the cycle.  So ONE exchange carries
 // r_0..r_{dim-1}, g_0..g_{dim-1} and |w|^2; every workgroup then solves the same unit-lower-triangular system from the same
-// totals, applies  w += (-h_j) v_j  for j ascending (the chain's operations on every entry, in the chain's order) from the
+// totals, applies  w += (-h_j) v_j  for j ascending (the chain's operations on every entry, in the chain's order; the coefficients
+// differ from the chain's by the rounding of the dot products only) from the
 // basis vectors it still holds in registers, and gets |w|^2 AFTER the sweep without another exchange from
 //     |w - sum_j h_j v_j|^2 = |w|^2 - 2 h.r + h^T G h
 // (a difference of numbers of size |w|^2: taken when the sweep leaves more than 1 % of the norm, i.e. its rounding error stays
 // below 1e-12 |w'|^2; otherwise a second exchange sums |w'|^2 itself).  A sweep of `dim` links costs one exchange (two when
-// the formula is refused) instead of dim / 2 + 1, and every basis vector is still read exactly once as long as the thread can
+// the formula is refused) instead of the chain's dim + 1, and every basis vector is still read exactly once as long as the thread can
 // keep the block (dim <= DMAX); beyond, the oldest dim - DMAX vectors are streamed twice (dots, then update).
-// The exchange is two hops like the others: value v is summed over the workgroups' mailboxes by workgroup v % nwg (the 2 dim + 1
-// sums are spread over the grid instead of queueing in workgroup 0), the totals are picked up by everybody.
+// The exchange is two hops: value v is summed over the workgroups' mailboxes by workgroup v % nwg (the 2 dim + 1
+// sums are spread over the grid instead of queueing in workgroup 0), the totals are picked up by everybody.  (Letting every workgroup
+// read all mailboxes itself -- one hop -- measured slower, the polling traffic gets in its own way.)
 // Mailboxes: box[v * nwg + wg], totals behind them at box[MGS_ONE_VALS * MGS_MAX_WG + v].
 // Basis vectors beyond the block kept in registers are read TWICE by a sweep (dot pass, update pass).  The register-resident ones
 // are streamed with non-temporal loads (-DNSX_NT & 1: they must not evict F and the ILU factors from the 256-MiB Infinity Cache,
 // profiles/r02_cache_policy_and_links.txt); the older ones take the default policy, so that the update pass finds in that cache what
-// the dot pass brought in (-DNSX_MGS_OLD_NT=1: non-temporal as well, rounds 2-3).
-#ifndef NSX_MGS_OLD_NT
-#define NSX_MGS_OLD_NT 0
-#endif
-__device__ __forceinline__ double ld_twice(const double *p) {
-  if constexpr (NSX_MGS_OLD_NT != 0) return ld_stream<1>(p);
-  else return *p;
-}
-constexpr int MGS_ONE_VALS = 2 * (MGS_STEPS - 2) + 2;  // r_j, g_j (j < 30), |w|^2 before, |w|^2 after (second exchange)
-static_assert((size_t)MGS_ONE_VALS * MGS_MAX_WG + MGS_ONE_VALS <= MGS_BLK_REGION, "the one-exchange sweep shares the mailbox regions of k_mgs_blk");
+// the dot pass brought in.
 
 // ---- the same sweep in a DISTRIBUTED run (DIST): the single exchange also crosses the ranks -------------------------------------
 // The reducers leave the LOCAL totals in ext.vals (one word each) and count themselves in at ext.arrive.  On the communication
@@ -554,7 +205,7 @@ __global__ __launch_bounds__(256) void k_mgs_one(int n, int split, int gap, doub
     double ar = 0.0, ag = 0.0;
 #pragma unroll
     for (int k = 0; k < E; ++k) {
-      const double x_ = idx[k] >= 0 ? ld_twice(vp + idx[k]) : 0.0;
+      const double x_ = idx[k] >= 0 ? vp[idx[k]] : 0.0;
       ar += wv[k] * x_;
       ag += vl[k] * x_;
     }
@@ -585,7 +236,7 @@ __global__ __launch_bounds__(256) void k_mgs_one(int n, int split, int gap, doub
   // ---- hop 1: mailboxes; value v is summed by workgroup v % nwg
   int lerr = 0;
   for (int v = threadIdx.x; v < nvals; v += 256)
-    if (wg != drop_wg) gx_post(box + (size_t)v * nwg + wg, (sh[0][v] + sh[1][v]) + (sh[2][v] + sh[3][v]));  // drop_wg: fault injection, see k_mgs
+    if (wg != drop_wg) gx_post(box + (size_t)v * nwg + wg, (sh[0][v] + sh[1][v]) + (sh[2][v] + sh[3][v]));  // drop_wg >= 0: fault injection (NSX_GX_DROP_WG), a workgroup that never arrives
   for (int v = wg; v < nvals; v += nwg) {
     double a = 0.0;
     for (int q = threadIdx.x; q < nwg; q += 256) a += gx_wait_value(box + (size_t)v * nwg + q, &lerr);
@@ -650,7 +301,7 @@ __global__ __launch_bounds__(256) void k_mgs_one(int n, int split, int gap, doub
   bool dead = s_err != 0;
   double xo[E];  // entries of the next streamed (older) vector of the update below
 #pragma unroll
-  for (int k = 0; k < E; ++k) xo[k] = (!dead && j_keep > 0 && idx[k] >= 0) ? ld_twice(V.v[0] + idx[k]) : 0.0;
+  for (int k = 0; k < E; ++k) xo[k] = (!dead && j_keep > 0 && idx[k] >= 0) ? V.v[0][idx[k]] : 0.0;
   if (!dead) {
     // Gram matrix of the basis: older rows parked in G before the exchange, the new row from this exchange; then h by forward substitution and the
     // norm after the sweep, one wave, lane j = link j
@@ -698,7 +349,7 @@ __global__ __launch_bounds__(256) void k_mgs_one(int n, int split, int gap, doub
     for (int j = 0; j < j_keep; ++j) {
       double xn[E];
 #pragma unroll
-      for (int k = 0; k < E; ++k) xn[k] = (j + 1 < j_keep && idx[k] >= 0) ? ld_twice(V.v[j + 1] + idx[k]) : 0.0;
+      for (int k = 0; k < E; ++k) xn[k] = (j + 1 < j_keep && idx[k] >= 0) ? V.v[j + 1][idx[k]] : 0.0;
       const double alpha = -1.0 * hc[j];
 #pragma unroll
       for (int k = 0; k < E; ++k)
@@ -790,7 +441,7 @@ __global__ __launch_bounds__(256) void k_mgs_one(int n, int split, int gap, doub
     __syncthreads();
     if (threadIdx.x == 0) __hip_atomic_store(pub_flag, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   }
-  if (threadIdx.x == 0) tail[wg] = seq;  // mgs_commit_w, pasted: the call changes the instruction stream of the 10- and 12-entry instantiations
+  if (threadIdx.x == 0) tail[wg] = seq;  // this workgroup commits its part of w, then writes it back (pasted in both kernels, see "pieces" above)
   MGS_STAMP();  // update done
 #pragma unroll
   for (int k = 0; k < E; ++k)
@@ -971,7 +622,7 @@ __global__ __launch_bounds__(256) void k_ilu_mgs(int n, double *__restrict__ w, 
     double ar = 0.0, ag = 0.0;
 #pragma unroll
     for (int k = 0; k < E; ++k) {
-      const double x_ = idx[k] >= 0 ? ld_twice(vp + idx[k]) : 0.0;
+      const double x_ = idx[k] >= 0 ? vp[idx[k]] : 0.0;
       ar += wv[k] * x_;
       ag += vl[k] * x_;
     }
@@ -1017,7 +668,7 @@ __global__ __launch_bounds__(256) void k_ilu_mgs(int n, double *__restrict__ w, 
   bool dead = *s_err != 0;
   double xo[E];
 #pragma unroll
-  for (int k = 0; k < E; ++k) xo[k] = (!dead && j_keep > 0 && idx[k] >= 0) ? ld_twice(V.v[0] + idx[k]) : 0.0;
+  for (int k = 0; k < E; ++k) xo[k] = (!dead && j_keep > 0 && idx[k] >= 0) ? V.v[0][idx[k]] : 0.0;
   if (!dead) {
     for (int q = threadIdx.x; q < (dim - 1) * MGS_STEPS; q += 256) {
       const int r_ = q / MGS_STEPS, c_ = q % MGS_STEPS;
@@ -1054,7 +705,7 @@ __global__ __launch_bounds__(256) void k_ilu_mgs(int n, double *__restrict__ w, 
     for (int j = 0; j < j_keep; ++j) {
       double xn[E];
 #pragma unroll
-      for (int k = 0; k < E; ++k) xn[k] = (j + 1 < j_keep && idx[k] >= 0) ? ld_twice(V.v[j + 1] + idx[k]) : 0.0;
+      for (int k = 0; k < E; ++k) xn[k] = (j + 1 < j_keep && idx[k] >= 0) ? V.v[j + 1][idx[k]] : 0.0;
       const double alpha = -1.0 * hc[j];
 #pragma unroll
       for (int k = 0; k < E; ++k)
@@ -1131,7 +782,7 @@ __global__ __launch_bounds__(256) void k_ilu_mgs(int n, double *__restrict__ w, 
     if (threadIdx.x == 0) __hip_atomic_store(pub_flag, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   }
   IM_STAMP(8);  // coefficients, update, norm done
-  if (threadIdx.x == 0) tail[wg] = seq;  // mgs_commit_w, pasted: the call changes the instruction stream
+  if (threadIdx.x == 0) tail[wg] = seq;  // commit, then write back: pasted as in k_mgs_one
 #pragma unroll
   for (int k = 0; k < E; ++k)
     if (idx[k] >= 0) w[idx[k]] = wv[k];
@@ -1145,30 +796,16 @@ static size_t ilu_mgs_lds_doubles(int ilu_doubles, int e) {
 // entries per thread x basis vectors kept in registers: 8 x 10, 10 x 8, 12 x 6 (round 4: 1.28 M velocity dofs per GPU -- the 10.6 M-DoF mesh
 // on 8 GPUs -- need 11.1 entries per thread of the 448-workgroup grid a distributed sweep may use; one GPU: vectors up to 1.57 M entries)
 static const void *mgs_one_fn(int e, bool dist = false) {
-  if (dist) return e <= 8 ? (const void *)k_mgs_one<8, 10, true> : e <= 10 ? (const void *)k_mgs_one<10, 8, true> : (const void *)k_mgs_one<12, 6, true>;
-  return e <= 8 ? (const void *)k_mgs_one<8, 10, false> : e <= 10 ? (const void *)k_mgs_one<10, 8, false> : (const void *)k_mgs_one<12, 6, false>;
-}
-
-template <int M>
-static const void *mgs_blk_fn(int e) {
-  return e <= 8 ? (const void *)k_mgs_blk<8, M, true> : e <= 10 ? (const void *)k_mgs_blk<10, M, true> : (const void *)k_mgs_blk<20, M, false>;
-}
-static const void *mgs_fn(int m, int e) {
-  switch (m) {
-    case 0: return mgs_one_fn(e);
-    case 2: return mgs_blk_fn<2>(e);
-    case 3: return mgs_blk_fn<3>(e);
-    case 4: return mgs_blk_fn<4>(e);
-    case 5: return mgs_blk_fn<5>(e);
-    default: return e <= 10 ? (const void *)k_mgs<10> : (const void *)k_mgs<20>;
-  }
+  constexpr int E0 = MGS_ENTRIES[0], E1 = MGS_ENTRIES[1], E2 = MGS_ENTRIES[2];
+  if (dist) return e <= E0 ? (const void *)k_mgs_one<E0, 10, true> : e <= E1 ? (const void *)k_mgs_one<E1, 8, true> : (const void *)k_mgs_one<E2, 6, true>;
+  return e <= E0 ? (const void *)k_mgs_one<E0, 10, false> : e <= E1 ? (const void *)k_mgs_one<E1, 8, false> : (const void *)k_mgs_one<E2, 6, false>;
 }
 
 // The error word clear, nothing remembered about what the regions hold: what goes with emptied mailboxes
 static void mgs_boxes_cleared(nsx_handle *h) {
   MgsState &m = h->mgs;
   *pub_word_host(h, PUB_MGS_ERR) = 0;
-  m.used_wg[0] = m.used_wg[1] = m.used_steps[0] = m.used_steps[1] = 0;
+  m.used_words[0] = m.used_words[1] = 0;
 }
 // Both mailbox regions empty, the commit words behind them zero, and the above: a new handle's state
 static void mgs_clear_boxes(nsx_handle *h) {
@@ -1191,24 +828,20 @@ void mgs_setup(nsx_handle *h) {
     h->mgs.disabled = true;
     return;
   }
-  // links per exchange: 0 = all of them (k_mgs_one, the default), 1 = deal.II's chain link by link (k_mgs), 2..5 = k_mgs_blk
-  h->mgs.links = std::max(0, std::min(5, env_int("NSX_MGS_LINKS", 0)));
   h->mgs.box.alloc(MGS_BOX_REGION, MGS_TAIL);
   mgs_clear_boxes(h);
-  const int es[3] = {8, 10, h->mgs.links == 0 ? 12 : 20};
   // NSX_MGS_MAXWG caps every grid limit (tests: a small mesh then needs the instantiations a large one does)
   auto capped = [](int limit) { return env_set("NSX_MGS_MAXWG") ? std::max(1, mgs_maxwg_cap(limit)) : limit; };
   for (int k = 0; k < 3; ++k) {
-    const ResidentGrid g = resident_grid(h, mgs_fn(h->mgs.links, es[k]), 256);
+    const ResidentGrid g = resident_grid(h, mgs_one_fn(MGS_ENTRIES[k]), 256);
     h->mgs.max_wg_e[k] = capped(std::min(MGS_MAX_WG, g.slots()));
-    if (nsx_debug()) fprintf(stderr, "[nsx] mgs sweep (%d links per exchange, %d entries per thread): %d CUs x %d resident workgroups\n", h->mgs.links, es[k], g.cus, g.per_cu);
+    if (nsx_debug()) fprintf(stderr, "[nsx] mgs sweep (%d entries per thread): %d CUs x %d resident workgroups\n", MGS_ENTRIES[k], g.cus, g.per_cu);
   }
   h->mgs.max_wg = h->mgs.max_wg_e[1];
   // distributed instantiations: the collective's own kernels (RCCL's all-reduce, the two one-thread kernels around it) must find a
   // place on the device WHILE the grid is resident and waiting for them: an eighth of the slots (at least 32) stays free
-  const int es_one[3] = {8, 10, 12};
   for (int k = 0; k < 3; ++k) {
-    const ResidentGrid g = resident_grid(h, mgs_one_fn(es_one[k], true), 256);
+    const ResidentGrid g = resident_grid(h, mgs_one_fn(MGS_ENTRIES[k], true), 256);
     const int slots = g.slots();
     h->mgs.max_wg_dist[k] = capped(std::max(0, std::min(MGS_MAX_WG, slots - std::max(32, slots / 8))));
     // on a compute stream that leaves one CU per XCD to the collective's kernel: every shader engine counts as the one that lost a CU
@@ -1253,7 +886,7 @@ static void mgs_chain(nsx_handle *h, Span sp, double *w, int dim, double *const 
 
 // ---- the sweep with TWO collectives (distributed runs) ------------------------------------------------------------------
 // With a communicator every link of the chain is a launch plus an all-reduce (dim + 1 collectives per sweep, the reference
-// pays one MPI_Allreduce per link as well).  The same linearity that k_mgs_blk uses for M links holds for all of them:
+// pays one MPI_Allreduce per link as well).  By the linearity that k_mgs_one rests on (derived there), with w the vector as it enters,
 //     h_j = v_j . w - sum_{i < j} (v_i . v_j) h_i ,
 // so one pass computes r_j = v_j . w for every j and the new row of the basis' Gram matrix (v_{dim-1} . v_i, i < dim - 1; the
 // older rows were computed by the earlier sweeps of this GMRES cycle and are kept on the device), ONE all-reduce sums them over
@@ -1477,7 +1110,7 @@ static int ilu_mgs_entries(nsx_handle *h, Span sp, int dim, const double *gram) 
   // The default therefore stays with the separate kernels and rounds 3-4's history.
   const bool wanted = ilu_mgs_wanted();
   const IluSchedule &s = h->schedF;
-  if (!wanted || h->comm || h->mgs.disabled || !h->mgs.box.allocated() || h->mgs.links != 0 || !gram || dim + 2 > MGS_STEPS) return 0;
+  if (!wanted || h->comm || h->mgs.disabled || !h->mgs.box.allocated() || !gram || dim + 2 > MGS_STEPS) return 0;
   if (sp.n != h->n_u || sp.split != sp.n || sp.gap != 0 || (h->dim != 2 && h->dim != 3)) return 0;
   if (!s.packed_ok || s.levelled || s.stream_ncomp != h->dim || s.stream_epl != 2 || s.n_waves < 1 || s.n_waves > MGS_MAX_WG) return 0;
   if (ilu_lanes_pf() != 8) return 0;  // (the fused kernel keeps 8 slabs in flight)
@@ -1537,9 +1170,8 @@ static MgsPlan mgs_plan(nsx_handle *h, Span sp, int dim, const double *gram, int
   }
   bool dist = h->comm && m.dist_state == 1 && !m.disabled && gram;
   if (!h->comm || dist) mgs_setup(h);
-  dist = dist && m.links == 0 && 2 * dim + 1 < MGS_EXT_LEAVE;
-  // entries per thread: the smallest instantiation (8, 10, 20) whose resident grid covers the vector; the one-exchange sweep keeps a
-  // block of basis vectors in registers: 8, 10 or 12 entries per thread.
+  dist = dist && 2 * dim + 1 < MGS_EXT_LEAVE;
+  // entries per thread: the smallest instantiation (MGS_ENTRIES: 8, 10, 12) whose resident grid covers the vector.
   // With the collective inside the grid only the 8-entry instantiation: it holds 246 VGPRs (248 allocated), so a CU that carries
   // ONE of its workgroups keeps 264 registers per SIMD lane free -- exactly what a wave of RCCL's generic kernel needs (264; 256
   // threads, 19.7 KB of LDS) -- and the grid limit leaves such CUs (mgs_setup).  The 10- and 12-entry instantiations allocate 256:
@@ -1547,9 +1179,8 @@ static MgsPlan mgs_plan(nsx_handle *h, Span sp, int dim, const double *gram, int
   // collective, tools/r04_self_p2p.sh: level 5, 8 entries: 23.0 -> 30.9 us per sweep, no fallback; level 7, 10 entries: time-out)
   // ... unless the compute stream leaves one CU per XCD to the communication stream (comm_reserve_cus, below): then any instantiation
   const bool only8 = dist && !h->cu_reserved;
-  const int es[3] = {8, 10, m.links == 0 ? 12 : 20}, es_one[3] = {8, 10, 12};
-  p.pick = mgs_pick(n, dist ? (h->cu_reserved ? m.dist_cap_reserved : m.max_wg_dist) : m.max_wg_e, m.max_wg ? (only8 ? 1 : 3) : 0, es);
-  int per_thread_max = only8 ? 8 : es[2];
+  p.pick = mgs_pick(n, dist ? (h->cu_reserved ? m.dist_cap_reserved : m.max_wg_dist) : m.max_wg_e, m.max_wg ? (only8 ? 1 : 3) : 0, MGS_ENTRIES);
+  int per_thread_max = MGS_ENTRIES[only8 ? 0 : 2];
   const int role = mgs_role(h, sp);
   if (only8 && !h->cu_reserve_failed && m.dist_fit.find(role) == m.dist_fit.end()) {
     // too long for the 8-entry grid somewhere, but not for the larger instantiations on a masked compute stream?  NSX_COMM_CU_RESERVE:
@@ -1558,7 +1189,7 @@ static MgsPlan mgs_plan(nsx_handle *h, Span sp, int dim, const double *gram, int
     // (no masked stream, the probe) every rank goes back to its plain streams and nobody asks again on this communicator.
     static const int reserve = env_int("NSX_COMM_CU_RESERVE", 1);
     const bool fits8 = p.pick.e != 0 && p.pick.per_thread <= 8;
-    const bool fits_reserved = mgs_pick(n, m.dist_cap_reserved, 3, es_one).fits();
+    const bool fits_reserved = mgs_pick(n, m.dist_cap_reserved, 3, MGS_ENTRIES).fits();
     const bool all8 = reserve > 0 ? comm_agree_all(h, fits8) : true;
     if (reserve > 0 && (reserve > 1 || !all8) && comm_agree_all(h, fits_reserved)) {
       const bool mine = comm_reserve_cus(h);
@@ -1567,8 +1198,8 @@ static MgsPlan mgs_plan(nsx_handle *h, Span sp, int dim, const double *gram, int
         h->cu_reserve_failed = true;
       }
       if (h->cu_reserved) {  // choose the instantiation again, with the masked stream's limits
-        per_thread_max = 12;
-        p.pick = mgs_pick(n, m.dist_cap_reserved, 3, es_one);
+        per_thread_max = MGS_ENTRIES[2];
+        p.pick = mgs_pick(n, m.dist_cap_reserved, 3, MGS_ENTRIES);
       }
     }
   }
@@ -1582,7 +1213,7 @@ static MgsPlan mgs_plan(nsx_handle *h, Span sp, int dim, const double *gram, int
   p.dist = dist;
   // no persistent sweep: a distributed solve off the in-grid collective, no resident grid, too many vectors for the mailbox rows, a vector
   // too long for the largest instantiation, or no Gram cache for the one-exchange sweep
-  p.persistent = fused_e || !((h->comm && !dist) || m.max_wg == 0 || dim + 2 > MGS_STEPS || p.pick.per_thread > per_thread_max || (m.links == 0 && !gram));
+  p.persistent = fused_e || !((h->comm && !dist) || m.max_wg == 0 || dim + 2 > MGS_STEPS || p.pick.per_thread > per_thread_max || !gram);
   // (one GPU, vector too long for the persistent sweep: the same two passes read the basis twice instead of four times)
   p.two_pass = h->comm || (!m.disabled && p.pick.per_thread > per_thread_max);
   if (fused_e) p.pick.nwg = h->schedF.n_waves, p.pick.e = p.pick.per_thread = fused_e;
@@ -1632,7 +1263,7 @@ static void ilu_mgs_trace_dump(nsx_handle *h, const DevBuf<unsigned long long> &
 static double *mgs_launch(nsx_handle *h, const MgsPlan &p, Span sp, double *w, int dim, double *const *vs, int slot0, bool normalize, bool consider, double *gram,
                           const double *ilu_rhs, unsigned long long seq) {
   MgsState &m = h->mgs;
-  const int n = sp.n, nwg = p.pick.nwg, M = m.links, fused_e = p.fused_e;
+  const int n = sp.n, nwg = p.pick.nwg, fused_e = p.fused_e;
   m.last_e = p.pick.e;
   m.last_fused = fused_e ? 1 : 0;
   m.fused_launches += fused_e ? 1 : 0;
@@ -1650,13 +1281,11 @@ static double *mgs_launch(nsx_handle *h, const MgsPlan &p, Span sp, double *w, i
   unsigned long long *pub_flag = pub_word_dev<unsigned long long>(h, PUB_FLAG), seq_ = seq;
   int *err = pub_word_dev(h, PUB_MGS_ERR);  // mapped host word
   unsigned long long *tail = m.box.tail();
-  int reset_wg = m.used_wg[1 - parity], reset_steps = m.used_steps[1 - parity], reset_words = reset_wg * reset_steps;
+  int reset_words = m.used_words[1 - parity];  // what the other region's last user filled: this launch empties it for the next one
   int drop_wg = h->gx_drop_wg;
   double *gram_ = gram, guard_ = mgs_norm_guard(h);
   double *ext_vals_this = nullptr;
-  // what this launch fills of its region: k_mgs rows of mailboxes; the others a flat array of words ("steps" counts words, "wg" is 1)
-  int used_wg = 1, used_steps = (2 * dim + 2) * nwg;  // k_mgs_one, k_ilu_mgs: mailboxes box[v * nwg + wg] for the 2 dim + 1 values of the single exchange (+ 1 for the explicit norm)
-  const void *fn = fused_e ? ilu_mgs_fn(h->dim, fused_e) : p.dist ? mgs_one_fn(p.pick.e, true) : mgs_fn(M, p.pick.e);
+  const void *fn = fused_e ? ilu_mgs_fn(h->dim, fused_e) : mgs_one_fn(p.pick.e, p.dist);
   if (fused_e) {
     const IluSchedule &s_ = h->schedF;
     IluMgsArgs I{s_.pk_row_ptr.p, s_.pk_rows.p, s_.pk_slab_ptr.p, reinterpret_cast<const uint32_t *>(s_.pk_meta.p), s_.pk_val.p, s_.pk_dinv.p, ilu_rhs,
@@ -1674,7 +1303,7 @@ static double *mgs_launch(nsx_handle *h, const MgsPlan &p, Span sp, double *w, i
     void *args[] = {&n_, &w, &V, &dim_, &gram_, &box, &box_next, &reset_words, &sout, &err, &tail, &norm_, &consider_, &pub_vals, &pub_flag, &seq_, &drop_wg, &guard_, &I};
     HIP_CHECK(hipLaunchKernel(fn, dim3(nwg), dim3(256), args, shm, h->stream));
     if (traced) ilu_mgs_trace_dump(h, trace_buf, trace_path, dim, nwg, fused_e);
-  } else if (M == 0) {
+  } else {
     MgsExt ext{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0};
     if (p.dist) {
       ext.leave = m.leave_req ? 1 : 0;
@@ -1695,19 +1324,10 @@ static double *mgs_launch(nsx_handle *h, const MgsPlan &p, Span sp, double *w, i
       m.ext_parity ^= 1;
       h->slot_nb[S_LS_NORM] = 0;
     }
-  } else if (M == 1) {
-    void *args[] = {&n_, &split, &gap, &w, &V, &dim_, &box, &box_next, &reset_wg, &reset_steps, &sout, &err, &tail, &norm_, &consider_, &pub_vals, &pub_flag, &seq_, &drop_wg};
-    HIP_CHECK(hipLaunchKernel(fn, dim3(nwg), dim3(256), args, 0, h->stream));
-    used_wg = nwg;
-    used_steps = dim + 2;
-  } else {  // k_mgs_blk: (exchanges x values x workgroups) words
-    void *args[] = {&n_, &split, &gap, &w, &V, &dim_, &box, &box_next, &reset_words, &sout, &err, &tail, &norm_, &consider_, &pub_vals, &pub_flag, &seq_, &drop_wg};
-    HIP_CHECK(hipLaunchKernel(fn, dim3(nwg), dim3(256), args, 0, h->stream));
-    used_steps = (cdiv(dim, M) + 1) * (M + M * (M - 1) / 2 + 1) * nwg;
   }
-  m.used_wg[parity] = used_wg;
-  m.used_steps[parity] = used_steps;
-  m.used_wg[1 - parity] = m.used_steps[1 - parity] = 0;
+  // this launch fills the mailboxes box[v * nwg + wg] of the 2 dim + 1 values of the single exchange (+ 1 for the explicit norm); the other region is empty now
+  m.used_words[parity] = (2 * dim + 2) * nwg;
+  m.used_words[1 - parity] = 0;
   m.box.flip();
   for (int i = 0; i <= dim + 1; ++i) h->slot_nb[slot0 + i] = 0;
   return ext_vals_this;
@@ -1761,9 +1381,9 @@ static bool mgs_finish_late(nsx_handle *h, Span sp, double *w, int dim, double *
   return true;
 }
 
-// out[0..dim) = h(i), out[dim] = |w|^2 after the sweep.  Returns true when w was also normalised (only if asked to).
-bool v_mgs(nsx_handle *h, Span sp, double *w, int dim, double *const *vs, int slot0, bool normalize, double *out,
-           const std::function<void()> *after_launch, bool consider, double *gram, const double *ilu_rhs) {
+// out[0..dim) = h(i), out[dim] = |w|^2 after the sweep.  normalized: w was also normalised (only if asked to).
+MgsResult v_mgs(nsx_handle *h, Span sp, double *w, int dim, double *const *vs, int slot0, bool normalize, double *out,
+                const std::function<void()> *after_launch, bool consider, double *gram, const double *ilu_rhs) {
   MgsState &m = h->mgs;
   // ilu_rhs: w = (LU)^-1 ilu_rhs (the velocity ILU(0) of the last initialisation) comes FIRST -- inside the sweep's launch when
   // that is possible (k_ilu_mgs), as the separate kernel otherwise
@@ -1776,7 +1396,7 @@ bool v_mgs(nsx_handle *h, Span sp, double *w, int dim, double *const *vs, int sl
   const MgsPlan p = mgs_plan(h, sp, dim, gram, fused_e);
   if (!p.persistent) {
     mgs_fallback(h, sp, w, dim, vs, slot0, out, consider, gram, p.two_pass);
-    return false;
+    return {false, false};
   }
   const unsigned long long seq = ++h->pub_seq;
   const double *ext_vals = mgs_launch(h, p, sp, w, dim, vs, slot0, normalize, consider, gram, ilu_rhs, seq);
@@ -1798,11 +1418,10 @@ bool v_mgs(nsx_handle *h, Span sp, double *w, int dim, double *const *vs, int sl
       }
     }
     // what after_launch enqueued (the next operator application) used the unfinished w: its result is a temporary that the
-    // caller recomputes when told that w was not normalised here
-    if (ran_ahead) m.redo_ahead = true;
-    return false;
+    // caller recomputes when told so
+    return {false, ran_ahead};
   }
-  for (int i = 0; i <= dim + ((consider || m.links == 0) ? 1 : 0); ++i) out[i] = h->pub_host[slot0 + i];
+  for (int i = 0; i <= dim + 1; ++i) out[i] = h->pub_host[slot0 + i];
   if (p.dist && h->pub_host[slot0 + dim + 2] != 0.0) {
     // the Gram formula for |w'|^2 was refused (alike on every rank): the grid left its local sum in the scalar slot and did not
     // normalise; the second collective of the sweep sums it over the ranks.  (A NaN -- a mailbox of that sum timed out somewhere --
@@ -1814,12 +1433,20 @@ bool v_mgs(nsx_handle *h, Span sp, double *w, int dim, double *const *vs, int sl
       nrm2 = read_scalar(h, S_LS_NORM);
     }
     out[dim] = nrm2;
-    if (ran_ahead) m.redo_ahead = true;  // what was enqueued behind the launch used the unnormalised w
-    return false;
+    return {false, ran_ahead};  // what was enqueued behind the launch used the unnormalised w
   }
-  if (!normalize) return false;
+  if (!normalize) return {false, false};
   // the kernel's own decision, recomputed from the same two numbers
-  return !consider || !mgs_wants_second_sweep(std::sqrt(out[dim]), out[dim + 1]);
+  return {!consider || !mgs_wants_second_sweep(std::sqrt(out[dim]), out[dim + 1]), false};
+}
+
+// The Gram matrices of the GMRES bases, one 32 x 32 block per nesting level (depth < 4), zeroed when first asked for
+double *mgs_gram(nsx_handle *h, int depth) {
+  if (!h->mgs.ls_gram.p) {
+    h->mgs.ls_gram.alloc(4 * 1024);
+    h->mgs.ls_gram.zero(h->stream);
+  }
+  return h->mgs.ls_gram.p + (size_t)depth * 1024;
 }
 
 // diagnostics (nsx_persistent_state): words of the region the next sweep would use that are not empty.  A healthy handle keeps
@@ -1855,10 +1482,7 @@ extern "C" int nsx_gram_schmidt_sweeps(nsx_handle *h, int n, int split, int gap,
   const size_t len = (size_t)n + gap;
   std::vector<nsx::DevBuf<double>> v(m);
   for (int k = 0; k < m; ++k) v[k].upload(vectors + (size_t)k * len, len, h->stream);
-  if (!h->mgs.ls_gram.p) {
-    h->mgs.ls_gram.alloc(4 * 1024);
-    h->mgs.ls_gram.zero(h->stream);
-  }
+  double *gram = nsx::mgs_gram(h, 0);
   const bool consider = (flags & 1) != 0, normalize = (flags & 2) == 0;
   const double keep = h->mgs.guard_override;
   h->mgs.guard_override = norm_guard;
@@ -1871,7 +1495,7 @@ extern "C" int nsx_gram_schmidt_sweeps(nsx_handle *h, int n, int split, int gap,
     for (int k = 1; k < m; ++k) {
       double *vs[nsx::KRYLOV_N_TMP + 2], out[nsx::KRYLOV_N_TMP + 4];
       for (int i = 0; i < k; ++i) vs[i] = v[i].p;
-      const bool done = nsx::v_mgs(h, sp, v[k].p, k, vs, nsx::S_H, normalize, out, nullptr, consider, h->mgs.ls_gram.p);
+      const bool done = nsx::v_mgs(h, sp, v[k].p, k, vs, nsx::S_H, normalize, out, nullptr, consider, gram).normalized;
       for (int i = 0; i < k; ++i) coeffs[(size_t)k * m + i] = out[i];
       norms2[k] = out[k];
       norms2_before[k] = consider ? out[k + 1] : 0.0;

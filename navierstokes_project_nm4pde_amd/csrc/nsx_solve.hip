@@ -130,14 +130,7 @@ static SolveResult gmres(nsx_handle *h, const Op &A, double *x, const double *b,
     explicit Depth(nsx_handle *h_) : h(h_), d(h_->gmres_depth++) {}
     ~Depth() { h->gmres_depth--; }
   } depth(h);
-  double *gram = nullptr;
-  if (depth.d < 4) {  // also used on one GPU when a vector is too long for the persistent sweep (v_mgs)
-    if (!h->mgs.ls_gram.p) {
-      h->mgs.ls_gram.alloc(4 * 1024);
-      h->mgs.ls_gram.zero(h->stream);
-    }
-    gram = h->mgs.ls_gram.p + (size_t)depth.d * 1024;
-  }
+  double *gram = depth.d < 4 ? mgs_gram(h, depth.d) : nullptr;  // also used on one GPU when a vector is too long for the persistent sweep (v_mgs)
   // (in place needs the lane-owner stream: its kernel loads the right-hand side rows into LDS before it writes anything)
   const bool ilu_conv = o.P_is_ilu_F && h->inner_precision == NSX_INNER_FP64 /* the fused kernel reads the double stream only */ && !h->comm && h->schedF.packed_ok && !h->schedF.levelled && h->schedF.stream_ncomp == h->dim &&
                         ilu_mgs_wanted();  // opt-in: see ilu_mgs_entries (nsx_mgs.hip)
@@ -227,18 +220,13 @@ static SolveResult gmres(nsx_handle *h, const Op &A, double *x, const double *b,
           }
         }
       };
-      bool normalized = v_mgs(h, n, vv, dim, basis, S_H, !re_orth, hh, &next_A, consider, gram, fuse ? vv : nullptr);
-      if (h->mgs.redo_ahead) {  // the sweep fell back to the launch-per-link chain: A * vv was enqueued on an unfinished vv
-        h->mgs.redo_ahead = false;
-        ahead = 0;
-      }
+      const MgsResult swept = v_mgs(h, n, vv, dim, basis, S_H, !re_orth, hh, &next_A, consider, gram, fuse ? vv : nullptr);
+      bool normalized = swept.normalized;
+      if (swept.ahead_stale) ahead = 0;  // the sweep fell back to the launch-per-link chain: A * vv was enqueued on an unfinished vv
       double s = std::sqrt(hh[dim]);
-      if (consider) {
-        const double norm_vv_start = std::sqrt(hh[dim + 1]);  // |vv| before the sweep, computed inside it
-        if (!(s > 10. * norm_vv_start * std::sqrt(2.220446049250313e-16))) re_orth = true;
-      }
+      if (consider && mgs_wants_second_sweep(s, hh[dim + 1])) re_orth = true;  // hh[dim + 1] = |vv|^2 before the sweep, computed inside it
       if (re_orth) {
-        normalized = v_mgs(h, n, vv, dim, basis, S_H2, true, h2, nullptr, false, gram);
+        normalized = v_mgs(h, n, vv, dim, basis, S_H2, true, h2, nullptr, false, gram).normalized;
         for (int i = 0; i < dim; ++i) hh[i] += h2[i];
         s = std::sqrt(h2[dim]);
       }

@@ -46,13 +46,12 @@ HARD_LIMIT = 1e-10  # no asserted bound may reach this (relative, on the scales 
 KINDS = ("gauss", "dependent")
 SEED = 2024
 # vector lengths of tests/test_gpu_mgs_sweep.py: the real grid (one entry up to more than 256 workgroups), and the edges of the
-# instantiations mgs_pick chooses for a grid capped at one workgroup (8 / 10 / 12 entries per thread, 20 with NSX_MGS_LINKS >= 1,
+# instantiations mgs_pick chooses for a grid capped at one workgroup (8 / 10 / 12 entries per thread,
 # two passes beyond) and at three
 SIZES_GRID = (1, 2, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025, 5000, 100001, 300001, 600001)
 SIZES_WG1 = (2047, 2048, 2049, 2560, 2561, 3072, 3073)
-SIZES_WG1_LINKS = SIZES_WG1 + (5120, 5121)
 SIZES_WG3 = (6144, 6145, 7681)
-ALL_SIZES = tuple(sorted(set(SIZES_GRID + SIZES_WG1_LINKS + SIZES_WG3)))
+ALL_SIZES = tuple(sorted(set(SIZES_GRID + SIZES_WG1 + SIZES_WG3)))
 
 
 def spans(n):

@@ -3,10 +3,10 @@ SolverGMRES' modified Gram-Schmidt chain (tests/mgs_reference.py), through the t
 come back entry by entry, the coefficients, |w'|^2, |w|^2 before the sweep, the sweep's own decision whether it may normalise, and the
 gap entries of a block vector's layout bit for bit -- at the edges of every instantiation:
 
-  variants        NSX_MGS=0 (launch-per-link chain on k_reduce), NSX_MGS_LINKS=0 (k_mgs_one), 1 (k_mgs), 2..5 (k_mgs_blk), the two-pass
+  variants        NSX_MGS=0 (launch-per-link chain on k_reduce), the default one-exchange sweep (k_mgs_one), the two-pass
                   sweep (k_ls_*: a vector too long for the capped grid), and on a 1-rank RCCL communicator the collective inside the
                   grid (k_mgs_one<.., true>), NSX_MGS_DIST=0 (two passes) and NSX_MGS_DIST=0 NSX_MGS_LOWSYNC=0 (chain)
-  instantiations  NSX_MGS_MAXWG=1 / 3 force the 8 / 10 / 12 (20) entries-per-thread kernels and the two-pass sweep on short vectors, at
+  instantiations  NSX_MGS_MAXWG=1 / 3 force the 8 / 10 / 12 entries-per-thread kernels and the two-pass sweep on short vectors, at
                   n = the last length that fits, and one more; the real grid from one entry to more than 256 workgroups
   basis           30 vectors where the length allows: one cycle passes every dim 1..29, i.e. DMAX and DMAX + 1 of each instantiation
   spans           contiguous, and (split, gap) = (n // 3, 37), (0, 5), (n - 1, 1) with a sentinel in the gap
@@ -34,7 +34,7 @@ pytestmark = pytest.mark.gpu
 
 SENTINEL = -7.0e300
 CONSIDER, NO_NORMALIZE = 1, 2
-ENV_KEYS = ("NSX_MGS", "NSX_MGS_LINKS", "NSX_MGS_MAXWG", "NSX_MGS_DIST", "NSX_MGS_LOWSYNC")
+ENV_KEYS = ("NSX_MGS", "NSX_MGS_MAXWG", "NSX_MGS_DIST", "NSX_MGS_LOWSYNC")
 
 
 @pytest.fixture(scope="module")
@@ -49,12 +49,11 @@ def cdiv(a, b):
 def expected_path(n, env, comm):
     """what v_mgs must run for a vector of n entries: ("chain" | "two_pass" | "sweep", entries per thread or None, workgroups or None) --
     mgs_plan / mgs_pick restated for the grids a test caps (NSX_MGS_MAXWG); the uncapped grid's size is the device's business"""
-    links = int(env.get("NSX_MGS_LINKS", "0"))
     if env.get("NSX_MGS") == "0":
         return "chain", None, None
     if comm and env.get("NSX_MGS_DIST") == "0":
         return ("chain" if env.get("NSX_MGS_LOWSYNC") == "0" else "two_pass"), None, None
-    es = (8,) if comm else (8, 10, 12 if links == 0 else 20)
+    es = (8,) if comm else (8, 10, 12)
     cap = int(env["NSX_MGS_MAXWG"]) if "NSX_MGS_MAXWG" in env else None
     if cap is None:
         return "sweep", None, None
@@ -84,7 +83,6 @@ def run_handle(prob, env, sizes, comm=False, want_paths=()):
     saved = {k: os.environ.pop(k, None) for k in ENV_KEYS}
     os.environ.update(env)
     failures, worst, ran = [], {}, set()
-    links = int(env.get("NSX_MGS_LINKS", "0"))
     dev = None
     try:
         dev = prob.device()
@@ -95,7 +93,7 @@ def run_handle(prob, env, sizes, comm=False, want_paths=()):
             m = R.basis_length(n)
             path, e_want, nwg_want = expected_path(n, env, comm)
             # the Gram formula for |w'|^2: the one-exchange sweep and the two-pass sweep (unless the guard refuses it always)
-            formula_variant = (path == "sweep" and links == 0) or path == "two_pass"
+            formula_variant = path == "sweep" or path == "two_pass"
             for kind, span, flags, guard in cases_for(n, guards=formula_variant):
                 tag = "%s n=%d %s span=%s flags=%d guard=%g" % (env, n, kind, span, flags, guard)
                 ref = R.reference(n, m, R.SEED, kind)
@@ -135,9 +133,9 @@ def run_handle(prob, env, sizes, comm=False, want_paths=()):
                         if e_want is not None and (e, nwg) != (e_want, nwg_want):
                             failures.append("%s: %d entries per thread on %d workgroups, expected %d on %d" % (tag, e, nwg, e_want, nwg_want))
                         if e_want is None:  # the real grid: the smallest instantiation, a workgroup per 1024 entries up to what is resident
-                            if e not in (8, 10, 12, 20) or nwg * 256 * e < n or nwg > 512 or (n <= 100001 and (e, nwg) != (8, cdiv(n, 1024))):
+                            if e not in (8, 10, 12) or nwg * 256 * e < n or nwg > 512 or (n <= 100001 and (e, nwg) != (8, cdiv(n, 1024))):
                                 failures.append("%s: %d entries per thread on %d workgroups" % (tag, e, nwg))
-                            if n >= 300001 and (links == 0) and nwg <= 256:
+                            if n >= 300001 and nwg <= 256:
                                 failures.append("%s: %d workgroups do not reach the reducers' loop over more than 256 mailboxes" % (tag, nwg))
                         if info["sweep_collective_inside"] != (1 if comm else 0):
                             failures.append("%s: collective inside = %d" % (tag, info["sweep_collective_inside"]))
@@ -163,35 +161,27 @@ def run_handle(prob, env, sizes, comm=False, want_paths=()):
     assert not failures, "\n".join(failures[:40] + (["... %d more" % (len(failures) - 40)] if len(failures) > 40 else []))
 
 
-LINKS = ["0", "1", "2", "3", "4", "5"]
-
-
 def test_chain_of_separate_launches(prob):
     """NSX_MGS=0: v_dot + v_add_and_dot per link (k_reduce), the path every fallback ends on"""
     run_handle(prob, {"NSX_MGS": "0"}, R.SIZES_GRID + (3073,), want_paths=[("chain", None)])
 
 
-@pytest.mark.parametrize("links", LINKS)
-def test_persistent_sweep_on_the_real_grid(prob, links):
-    """k_mgs_one<8,10> / k_mgs<10> / k_mgs_blk<8,M>: one entry ... more than 256 workgroups in the reducers' mailbox loop"""
-    run_handle(prob, {"NSX_MGS_LINKS": links}, R.SIZES_GRID, want_paths=[("sweep", 8)])
+def test_persistent_sweep_on_the_real_grid(prob):
+    """k_mgs_one<8,10>: one entry ... more than 256 workgroups in the reducers' mailbox loop"""
+    run_handle(prob, {}, R.SIZES_GRID, want_paths=[("sweep", 8)])
 
 
-@pytest.mark.parametrize("links", LINKS)
-def test_instantiations_of_a_one_workgroup_grid(prob, links):
-    """NSX_MGS_MAXWG=1: 8 entries per thread up to n = 2048, 10 up to 2560, 12 up to 3072 (one exchange) or 20 up to 5120 (links >= 1),
-    two passes beyond -- each at its last length and one more (a thread's tail entry, the first entry of the next instantiation)"""
-    big = 12 if links == "0" else 20
-    sizes = R.SIZES_WG1 if links == "0" else R.SIZES_WG1_LINKS
-    run_handle(prob, {"NSX_MGS_LINKS": links, "NSX_MGS_MAXWG": "1"}, sizes,
-               want_paths=[("sweep", 8), ("sweep", 10), ("sweep", big), ("two_pass", None)])
+def test_instantiations_of_a_one_workgroup_grid(prob):
+    """NSX_MGS_MAXWG=1: 8 entries per thread up to n = 2048, 10 up to 2560, 12 up to 3072, two passes beyond -- each at its last
+    length and one more (a thread's tail entry, the first entry of the next instantiation)"""
+    run_handle(prob, {"NSX_MGS_MAXWG": "1"}, R.SIZES_WG1,
+               want_paths=[("sweep", 8), ("sweep", 10), ("sweep", 12), ("two_pass", None)])
 
 
-@pytest.mark.parametrize("links", LINKS)
-def test_instantiations_of_a_three_workgroup_grid(prob, links):
-    """NSX_MGS_MAXWG=3: three workgroups reduce up to 59 values (value v by workgroup v % 3) at 8, 10 and 12 (20) entries per thread"""
-    run_handle(prob, {"NSX_MGS_LINKS": links, "NSX_MGS_MAXWG": "3"}, R.SIZES_WG3,
-               want_paths=[("sweep", 8), ("sweep", 10), ("sweep", 12 if links == "0" else 20)])
+def test_instantiations_of_a_three_workgroup_grid(prob):
+    """NSX_MGS_MAXWG=3: three workgroups reduce up to 59 values (value v by workgroup v % 3) at 8, 10 and 12 entries per thread"""
+    run_handle(prob, {"NSX_MGS_MAXWG": "3"}, R.SIZES_WG3,
+               want_paths=[("sweep", 8), ("sweep", 10), ("sweep", 12)])
 
 
 def test_two_pass_sweep(prob):

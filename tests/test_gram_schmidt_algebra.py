@@ -1,5 +1,5 @@
-"""CPU check of the algebra behind the Gram-Schmidt sweeps that exchange several links at once (csrc/nsx_mgs.hip: k_mgs_blk for M
-links per grid-wide exchange, mgs_lowsync for a whole sweep with two collectives).  SolverGMRES' add_and_dot chain computes
+"""CPU check of the algebra behind the Gram-Schmidt sweeps that exchange several links at once (csrc/nsx_mgs.hip: k_mgs_one for a
+whole sweep in one grid-wide exchange, mgs_lowsync for a whole sweep with two collectives).  SolverGMRES' add_and_dot chain computes
 h_j = v_j . w_j, w_{j+1} = w_j - h_j v_j.  By linearity h_j = v_j . w_{j0} - sum_{j0 <= i < j} (v_i . v_j) h_i for any j0 <= j:
 no orthogonality of the basis is needed, so the blocked evaluation must reproduce the chain's coefficients to rounding even for a
 basis that has lost orthogonality."""

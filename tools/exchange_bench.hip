@@ -1,5 +1,5 @@
 // exchange_bench.hip — what does one grid-wide sum cost inside a persistent kernel on MI355X, and which shape is fastest?
-// Development tool behind the choices in csrc/nsx_grid.hpp (k_mgs, k_cg_schur).  Build + run on the GPU box:
+// Development tool behind the choices in csrc/nsx_grid.hpp (k_mgs_one, k_cg_schur).  Build + run on the GPU box:
 //   hipcc -O3 --offload-arch=gfx950 -o gpurun_out/exchange_bench tools/exchange_bench.hip && gpurun_out/exchange_bench
 // Every workgroup contributes one double per exchange; all workgroups need the fixed-order total before they go on.
 // Variants: polling (single load + s_sleep / three loads in flight, bunched / evenly spaced), reducer shape (workgroup 0 /

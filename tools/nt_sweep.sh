@@ -5,8 +5,6 @@ OUT=${1:?usage: tools/nt_sweep.sh OUTDIR}
 mkdir -p $OUT
 for NT in ${NT_LIST:-0 1 4 5}; do
   make -B device HIPFLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -munsafe-fp-atomics -Wall -Wno-unused-parameter -DNSX_NT=$NT" > $OUT/nt_build_$NT.log 2>&1
-  for L in ${LINKS_LIST:-2}; do
-    NSX_MGS_LINKS=$L python bench.py --full --steps 6 --warmup 2 --spinup 5 --no-cpu --profile-steps 4 > $OUT/nt_${NT}_l$L.json 2> $OUT/nt_${NT}_l$L.err
-    echo "NT=$NT links=$L done"
-  done
+  python bench.py --full --steps 6 --warmup 2 --spinup 5 --no-cpu --profile-steps 4 > $OUT/nt_$NT.json 2> $OUT/nt_$NT.err
+  echo "NT=$NT done"
 done
