@@ -37,7 +37,7 @@ $(ORACLE_MT_SO): oracle/nsx_oracle.c oracle/nsx_oracle.h
 
 DEV_SRC := $(wildcard $(PKG)/csrc/*.hip)
 DEV_HDR := $(wildcard $(PKG)/csrc/*.hpp) include/nsx.h $(PKG)/host/graph.hpp $(PKG)/host/ilu_stream.hpp $(PKG)/host/layout.hpp $(PKG)/host/adjacency.hpp $(PKG)/host/nodal_patch.hpp $(PKG)/host/iso_tables.hpp $(PKG)/host/lattice_box.hpp \
-            $(PKG)/host/gather_map.hpp $(PKG)/host/ilu_levels.hpp $(PKG)/host/spmv_plan.hpp $(PKG)/host/surface_patch.hpp
+            $(PKG)/host/gather_map.hpp $(PKG)/host/ilu_levels.hpp $(PKG)/host/spmv_plan.hpp $(PKG)/host/schur_plan.hpp $(PKG)/host/surface_patch.hpp
 $(DEV_SO): $(DEV_SRC) $(DEV_HDR)
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $(DEV_SRC) -L/opt/rocm/lib -lrccl
 

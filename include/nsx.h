@@ -770,6 +770,16 @@ int nsx_path_info(nsx_handle *h, int info[32]);
 #define NSX_ILU_SOLVE_BLOCK_LDS 4
 #define NSX_ILU_SOLVE_BLOCK_GLOBAL 5
 int nsx_ilu_path_info(nsx_handle *h, int which, int info[16]);
+/* 1 = the last inversion on that schedule (nsx_ilu_path_info [1] == NSX_ILU_INVERT_LDS) read the factor from LDS: the in-block entries of
+ * every block fitted beside its matrix under the device's opt-in limit of dynamic LDS, and NSX_ILU_INVERT_STAGE (read per call,
+ * default 1) was not 0; 0 = it read the factor from global memory, or no inversion in LDS has run.  A test hook. */
+int nsx_ilu_invert_staged(nsx_handle *h, int which, int *staged);
+/* The plan of the Schur product S = B diag(w) B^T (host/schur_plan.hpp) -- a test hook: info[0] 1 = the handle's Schur graph is
+ * planned (0: not built yet, a row of block(1,0) of 65535 entries or more, or a distributed handle), [1] 1 = the last product ran the
+ * planned kernel (NSX_SCHUR_PLAN, read per call, default 1; handles with a communicator or a distributed mesh always run the merge
+ * kernel), [2] entries of S, [3] terms over all entries, [4] 32-bit words of the plan, [5] its bytes on the device, [6] longest row of
+ * block(1,0), [7] host time of the plan in microseconds. */
+int nsx_schur_plan_info(nsx_handle *h, long long info[8]);
 
 /* SolverGMRES' orthogonalisation (deal.II's modified Gram-Schmidt add_and_dot chain inside every solver.solve of the path: reference
  * NavierStokes3D.cpp:574, Preconditioners.hpp:173,273,288,382,405) on the caller's vectors, through the very sweep kernel the solvers

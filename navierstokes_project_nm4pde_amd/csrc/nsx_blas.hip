@@ -595,3 +595,18 @@ extern "C" int nsx_ilu_path_info(nsx_handle *h, int which, int info[16]) {
   info[15] = s.path.factor_lds_bytes;
   return NSX_OK;
 }
+
+extern "C" int nsx_ilu_invert_staged(nsx_handle *h, int which, int *staged) {
+  if (!h || !staged || which < 0 || which > 1) return NSX_ERR_ARG;
+  *staged = h->have_mesh && (which == 0 ? h->schedF : h->schedS).path.invert_staged ? 1 : 0;
+  return NSX_OK;
+}
+
+extern "C" int nsx_schur_plan_info(nsx_handle *h, long long info[8]) {
+  if (!h || !info) return NSX_ERR_ARG;
+  const nsx::SchurPlanDev &p = h->schur_plan;
+  const bool have = h->have_mesh && p.current;
+  const long long v[8] = {have && p.ok, have && p.used_last, p.entries, p.matches, p.slots, p.bytes, p.max_row, (long long)(1e6 * p.build_s)};
+  for (int k = 0; k < 8; ++k) info[k] = have ? v[k] : 0;
+  return NSX_OK;
+}

@@ -106,13 +106,79 @@ __global__ __launch_bounds__(ILU_WAVES * 64) void k_ilu_factor(const int32_t *__
 // entries of its column that the same thread wrote a few rows earlier -- through global memory that is a store -> load round trip
 // through L2 per row (0.76 ms per step for 511 blocks of <= 96 rows), through LDS a few hundred cycles.  Same operations on the same
 // operands in the same order: bit-identical (tests/test_gpu_errors.py).
+// STAGE: all threads of the workgroup walk the same (column, value) sequence of every row, so the block's IN-BLOCK factor entries --
+// per row the strict-lower ones from column r0 on, the diagonal, the strict-upper ones below column r0 + n, in CSR order: exactly the
+// entries the sweeps below do not skip -- are copied once into LDS behind Ps (value + 16-bit local column, compact row starts from the
+// schedule's in_cptr / in_cpos as k_ilu_factor_lds stages them) and the sweeps read nothing from global memory.  Same operations,
+// operands and order.  ilu_invert_stage_bytes says what that takes; where it does not fit the device, STAGE = false reads the factor
+// from global memory as before.
+__host__ __device__ inline size_t ilu_invert_stage_bytes(int max_rows, int max_nz) {
+  return (size_t)max_rows * max_rows * sizeof(double) + (size_t)max_nz * sizeof(double) + (((size_t)max_nz * sizeof(uint16_t) + 7) & ~(size_t)7);
+}
+constexpr size_t ILU_INVERT_STATIC_LDS = (113 + 112) * sizeof(int);  // s_rp, s_dg below: the tables
+
+// acc - value * P[k][j]: the statement of both sweeps, the expression `acc -= lu[p] * Ps[k * n + j]` of the unstaged loops (one
+// fused multiply-add either way: tests/test_gpu_ilu_invert_stage.py compares the two bit for bit)
+__device__ __forceinline__ double ilu_invert_term(double acc, double value, double p) { return acc - value * p; }
+
+// acc minus the entries [c0, c1) of the staged factor times their rows of column j (Pcol = Ps + j), in order.  Eight entries per trip:
+// none of their loads depends on acc (only the sums chain), so the compiler overlaps them; a trip's slots beyond c1 fetch entry c and
+// are dropped.  Measured at 1.09 M DoF: 0.333 ms per step against 0.372 ms entry by entry; sixteen per trip with the three stages held
+// apart by scheduling barriers and branches instead of selects: 0.382 ms.
+__device__ __forceinline__ double ilu_invert_row(double acc, const double *sval, const uint16_t *scol, const double *Pcol, int n, int c0, int c1) {
+  constexpr int U = 8;
+  for (int c = c0; c < c1; c += U) {
+    double v[U], p[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int cc = c + u < c1 ? c + u : c;
+      v[u] = sval[cc];
+      p[u] = Pcol[scol[cc] * n];
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) acc = c + u < c1 ? ilu_invert_term(acc, v[u], p[u]) : acc;
+  }
+  return acc;
+}
+
+template <bool STAGE>
 __global__ __launch_bounds__(128) void k_ilu_invert_lds(const int32_t *__restrict__ bptr, const int64_t *__restrict__ off,
                                                         const int32_t *__restrict__ rp, const int32_t *__restrict__ ci,
-                                                        const int32_t *__restrict__ diag, const double *__restrict__ lu, double *__restrict__ P) {
+                                                        const int32_t *__restrict__ diag, const double *__restrict__ lu, double *__restrict__ P,
+                                                        const int32_t *__restrict__ in_lo, const int32_t *__restrict__ in_cptr,
+                                                        const int32_t *__restrict__ in_cpos) {
   extern __shared__ double Ps[];  // [n][n] row-major: column j of all rows by thread j, consecutive threads on consecutive banks
   __shared__ int s_rp[113], s_dg[112];  // the rows' entry ranges and diagonal positions: one trip for the block instead of one per row
   const int blk = blockIdx.x, r0 = bptr[blk], n = bptr[blk + 1] - r0;
   const int j = threadIdx.x;
+  if constexpr (STAGE) {
+    const int c0 = in_cptr[r0], nz = in_cptr[r0 + n] - c0;
+    double *sval = Ps + n * n;                    // [nz] the in-block entries in compact order
+    uint16_t *scol = (uint16_t *)(sval + nz);     // [nz] their columns, local to the block
+    for (int t = threadIdx.x; t <= n; t += 128) s_rp[t] = in_cptr[r0 + t] - c0;
+    for (int t = threadIdx.x; t < n; t += 128) s_dg[t] = in_cptr[r0 + t] - c0 + (diag[r0 + t] - in_lo[r0 + t]);
+    for (int c = threadIdx.x; c < nz; c += 128) {
+      const int p = in_cpos[c0 + c];
+      sval[c] = lu[p];
+      scol[c] = (uint16_t)(ci[p] - r0);
+    }
+    __syncthreads();
+    if (j < n) {
+      // the row bounds are the same in every lane: as scalars, so that the entry loops are not loops under a lane mask
+      for (int i = 0; i < n; ++i) {  // Y = L^-1 (unit lower)
+        const int c0 = __builtin_amdgcn_readfirstlane(s_rp[i]), pe = __builtin_amdgcn_readfirstlane(s_dg[i]);
+        Ps[i * n + j] = ilu_invert_row(i == j ? 1.0 : 0.0, sval, scol, Ps + j, n, c0, pe);
+      }
+      for (int i = n - 1; i >= 0; --i) {  // P = U^-1 (D^-1 Y), in place from the last row up
+        const int pd = __builtin_amdgcn_readfirstlane(s_dg[i]), pe = __builtin_amdgcn_readfirstlane(s_rp[i + 1]);
+        Ps[i * n + j] = ilu_invert_row(sval[pd] * Ps[i * n + j], sval, scol, Ps + j, n, pd + 1, pe);
+      }
+    }
+    __syncthreads();
+    double *Pb = P + off[blk];
+    for (int q = threadIdx.x; q < n * n; q += 128) Pb[q] = Ps[q];
+    return;
+  }
   for (int t = threadIdx.x; t <= n; t += 128) s_rp[t] = rp[r0 + t];
   for (int t = threadIdx.x; t < n; t += 128) s_dg[t] = diag[r0 + t];
   __syncthreads();
@@ -582,14 +648,26 @@ void ilu_factor(nsx_handle *h, const DevCsr &g, IluSchedule &s, const double *va
     // blocks of up to 112 rows (98 KB of LDS: one workgroup per CU and half) keep the n x n matrix in LDS while it is built
     const bool inv_lds = env_on("NSX_ILU_INVERT_LDS");  // read per call: the tests switch it inside one process
     const size_t shm = (size_t)s.max_rows * s.max_rows * sizeof(double);
+    s.path.invert_staged = false;
     if (inv_lds && s.max_rows <= 112) {
-      static bool attr_set = false;
-      if (!attr_set && shm > 64 * 1024) {
-        HIP_CHECK(hipFuncSetAttribute((const void *)k_ilu_invert_lds, hipFuncAttributeMaxDynamicSharedMemorySize, 112 * 112 * (int)sizeof(double)));
-        attr_set = true;
-      }
+      // the factor's in-block entries beside the matrix (NSX_ILU_INVERT_STAGE, read per call) where both fit the device's opt-in limit: a
+      // dense 112-row block does not (98 KB + 125 KB), the flagship's 96-row blocks of the Schur graph do
+      // (NSX_LDS_OPTIN, read per call: a lower limit than the device's, so that the tests reach the fallback on the graphs of real meshes)
+      const size_t staged = ilu_invert_stage_bytes(s.max_rows, s.max_block_nnz);
+      const size_t limit = (size_t)std::max<int64_t>(0, std::min<int64_t>(h->lds_optin, env_i64("NSX_LDS_OPTIN", h->lds_optin)));
+      const bool stage = env_on("NSX_ILU_INVERT_STAGE") && s.max_block_nnz < 65535 && staged + ILU_INVERT_STATIC_LDS <= limit;
+      const size_t lds = stage ? staged : shm;
+      const void *fn = stage ? (const void *)k_ilu_invert_lds<true> : (const void *)k_ilu_invert_lds<false>;
+      // the attribute belongs to the function on the current device: set whenever the launch needs it (a repeated call costs microseconds)
+      if (lds > 64 * 1024) HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::max(lds, (size_t)112 * 112 * sizeof(double))));
       s.path.invert = NSX_ILU_INVERT_LDS;
-      hipLaunchKernelGGL(k_ilu_invert_lds, dim3(s.n_blocks), dim3(128), shm, h->stream, s.block_ptr.p, s.dn_off.p, g.rowptr.p, g.colind.p, g.diag.p, lu, s.dn_P.p);
+      s.path.invert_staged = stage;
+      if (stage)
+        hipLaunchKernelGGL(k_ilu_invert_lds<true>, dim3(s.n_blocks), dim3(128), lds, h->stream, s.block_ptr.p, s.dn_off.p, g.rowptr.p, g.colind.p, g.diag.p, lu,
+                           s.dn_P.p, s.in_lo.p, s.in_cptr.p, s.in_cpos.p);
+      else
+        hipLaunchKernelGGL(k_ilu_invert_lds<false>, dim3(s.n_blocks), dim3(128), lds, h->stream, s.block_ptr.p, s.dn_off.p, g.rowptr.p, g.colind.p, g.diag.p, lu,
+                           s.dn_P.p, s.in_lo.p, s.in_cptr.p, s.in_cpos.p);
     } else {
       s.path.invert = NSX_ILU_INVERT_GLOBAL;
       hipLaunchKernelGGL(k_ilu_invert, dim3(s.n_blocks), dim3(256), 0, h->stream, s.block_ptr.p, s.dn_off.p, g.rowptr.p, g.colind.p, g.diag.p, lu,

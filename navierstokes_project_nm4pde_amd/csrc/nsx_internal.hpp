@@ -193,6 +193,7 @@ struct IluSchedule {
   //      codes).  Written by ilu_factor / ilu_solve, cleared when the schedule is rebuilt.
   struct Path {
     int factor = 0, invert = 0, factor_lds_bytes = 0;
+    bool invert_staged = false;  // k_ilu_invert_lds read the factor from its LDS copy (nsx_ilu_invert_staged)
     int solve = 0, solve_pf = 0, solve_ncomp = 0, solve_f32 = 0;
   };
   mutable Path path;
@@ -244,6 +245,19 @@ struct SpmvBlocked {
   DevBuf<int32_t> desc_if;
   int grid_if = 0, n_chunks_if = 0;
   double frac_if = 0;
+};
+
+// The planned Schur product (host/schur_plan.hpp, k_schur_planned): per group of 64 entries of a row of S a slab [step][lane] of packed
+// term positions.  Built with the ILU schedules (ensure_schedules), stale whenever the Schur graph is rebuilt (build_schur_graph).
+struct SchurPlanDev {
+  bool current = false, ok = false;  // current: built for the handle's Schur graph; ok: the graph could be planned
+  bool used_last = false;            // the last schur_numeric ran the planned kernel (nsx_schur_plan_info)
+  int max_row = 0;                   // longest row of block(1,0): the LDS both Schur kernels ask for
+  int64_t entries = 0, matches = 0, slots = 0, bytes = 0;
+  double build_s = 0;                // host time of the plan
+  DevBuf<int32_t> row_grp;
+  DevBuf<int64_t> grp_off;
+  DevBuf<uint32_t> words;
 };
 
 // Mailboxes of a persistent grid: two regions used alternately by successive launches (a launch empties the other region for its
@@ -618,6 +632,8 @@ struct nsx_handle {
   std::vector<int32_t> rank_u_h, rank_p_h, sblk_h;
   nsx::DevBuf<int32_t> rank_u;             // node units
   nsx::IluSchedule schedF, schedS;
+  nsx::SchurPlanDev schur_plan;
+  int lds_optin = 0;                       // the device's opt-in limit of dynamic LDS per workgroup, queried once (nsx_create)
   nsx::DevBuf<double> dbar;                // per-rank Dirichlet diagonal
   nsx::DevBuf<int32_t> bc_dofs;
   nsx::DevBuf<double> bc_vals;
@@ -779,6 +795,7 @@ void velocity_to_caller(nsx_handle *h, const double *dev, double *host);  // one
 inline int32_t node_to_internal(const nsx_handle *h, int32_t local_node) { return h->layout_on ? h->perm2_h[local_node] : local_node; }
 inline int32_t pnode_to_internal(const nsx_handle *h, int32_t local_node) { return h->layout_on ? h->perm1_h[local_node] : local_node; }
 void ensure_schedules(nsx_handle *h);  // (re)build the ILU schedules if the rank / Schur block tables changed
+void ensure_schur_plan(nsx_handle *h);  // (re)build the plan of the Schur product if the Schur graph changed
 
 // assembly (nsx_assemble.hip)
 void run_assemble(nsx_handle *h, bool first, int flags);

@@ -7,6 +7,7 @@
 // Kept here: argument checks and connectivity, cell geometry, the knob reads and path choices, error codes, debug lines, and the one
 // kernel, k_perm_vec, behind the caller-order <-> internal-order staging of vectors.
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <numeric>
 
@@ -15,6 +16,7 @@
 #include "../host/ilu_levels.hpp"
 #include "../host/ilu_stream.hpp"
 #include "../host/layout.hpp"
+#include "../host/schur_plan.hpp"
 #include "../host/spmv_plan.hpp"
 
 using namespace nsx;
@@ -195,6 +197,49 @@ void build_schur_graph(nsx_handle *h) {
   upload_csr(h, h->gS, true);
   h->vSchur.alloc(h->gS.nnz());
   h->luS.alloc(h->gS.nnz());
+  h->schur_plan.current = false;  // planned again for the new graph by the next ensure_schedules
+}
+
+// The term lists of the Schur product (host/schur_plan.hpp) for the current Schur graph.  Distributed handles keep the merge kernel
+// (schur_numeric): for them only the longest row of block(1,0) is taken, which both kernels size their LDS by.
+void ensure_schur_plan(nsx_handle *h) {
+  SchurPlanDev &d = h->schur_plan;
+  if (d.current) return;
+  const auto t0 = std::chrono::steady_clock::now();
+  SchurPlan pl;
+  if (h->dist) {
+    const Csr &B = h->gB.host;
+    for (int i = 0; i < B.n_rows; ++i) pl.max_row = std::max(pl.max_row, B.rowptr[i + 1] - B.rowptr[i]);
+  } else {
+    // a group is as long as its longest lane (the diagonal entry's: all of row i), so most words say "no term": at most 2 GiB of them
+    pl = build_schur_plan(h->gS.host, h->gB.host, env_i64("NSX_SCHUR_PLAN_MAX", (int64_t)1 << 29));
+  }
+  d.ok = pl.ok;
+  d.used_last = false;
+  d.max_row = pl.max_row;
+  d.entries = pl.entries;
+  d.matches = pl.matches;
+  d.slots = pl.slots();
+  d.bytes = pl.ok ? pl.bytes() : 0;
+  if (pl.ok) {
+    d.row_grp.upload(pl.row_grp, h->stream);
+    d.grp_off.upload(pl.grp_off, h->stream);
+    d.words.upload(pl.words, h->stream);
+  } else {
+    d.row_grp.release();
+    d.grp_off.release();
+    d.words.release();
+  }
+  d.build_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  d.current = true;
+  if (nsx_debug()) {
+    if (pl.ok)
+      fprintf(stderr, "[nsx] schur plan: entries %lld matches %lld (%.1f per entry) slab fill %.2f, %.1f MB, longest row of block(1,0) %d, built in %.3f s\n",
+              (long long)d.entries, (long long)d.matches, (double)d.matches / (double)std::max<int64_t>(1, d.entries), pl.fill(), 1e-6 * (double)d.bytes,
+              d.max_row, d.build_s);
+    else
+      fprintf(stderr, "[nsx] schur plan: none (%s), longest row of block(1,0) %d\n", h->dist ? "distributed handle" : "a row of block(1,0) is too long, or the plan would exceed NSX_SCHUR_PLAN_MAX words", d.max_row);
+  }
 }
 
 static void default_ranks(nsx_handle *h) {
@@ -215,6 +260,7 @@ static void refresh_rank_products(nsx_handle *h) {
 }
 
 void ensure_schedules(nsx_handle *h) {
+  ensure_schur_plan(h);  // its own flag: it follows the Schur graph, not the rank tables
   if (!h->sched_dirty) return;
   build_blocked(h, h->gA.host, spmv_chunks(h), h->blkA, h->N2);
   // blocks per wave: enough rows to keep the 64 lanes of the lane-owner stream busy (~680 rows: 8 blocks of ~85 rows measured
@@ -391,6 +437,16 @@ int nsx_create(const nsx_params *p, nsx_handle **out) {
     if (p->device < 0 || p->device >= ndev) NSX_THROW(NSX_ERR_ARG, "device %d out of range (%d visible)", p->device, ndev);
     HIP_CHECK(hipSetDevice(p->device));
     HIP_CHECK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+    {  // what a kernel may ask for as dynamic LDS once its function attribute is raised (k_ilu_invert_lds sizes its staging by it)
+      int optin = 0, plain = 0;
+      HIP_CHECK(hipDeviceGetAttribute(&plain, hipDeviceAttributeMaxSharedMemoryPerBlock, p->device));
+      if (hipDeviceGetAttribute(&optin, hipDeviceAttributeSharedMemPerBlockOptin, p->device) != hipSuccess) {
+        (void)hipGetLastError();
+        optin = 0;
+      }
+      h->lds_optin = std::max(optin, plain);
+      if (nsx_debug()) fprintf(stderr, "[nsx] device %d: dynamic LDS per workgroup %d bytes, opt-in %d\n", p->device, plain, optin);
+    }
     h->scal.alloc(N_SLOTS);
     h->scal.zero(h->stream);
     h->red_partial.alloc((size_t)N_SLOTS * 1024);

@@ -10,6 +10,7 @@
 // All kernels are HBM/L2-bandwidth bound; reductions inside a row use wavefront shuffles (64-wide waves, sub-groups of
 // 8/16/32/64 lanes per row chosen from the average row length: lane_group_sum, nsx_internal.hpp).
 #include "nsx_internal.hpp"
+#include "../host/schur_plan.hpp"
 
 namespace nsx {
 
@@ -608,6 +609,14 @@ void abs_rowsum(nsx_handle *h, const DevCsr &g, const double *vals, double *d) {
 //   S_ij = sum_{k in row_i(B) ^ row_j(B)} sum_c B[i,k][c] * w[k][c] * B[j,k][c],   w = -v * dirichlet_mask.
 // One wave per row i: row i (columns + dim weighted values) is staged in LDS, each lane takes one S entry (i,j),
 // walks row j of B and merges its (sorted) columns with the LDS copy.
+// THE arithmetic of one term, for the merge kernel and the planned one alike: one statement, so the two cannot be contracted differently
+template <int DIM>
+__device__ __forceinline__ double schur_term(double acc, const double *rv, const double *__restrict__ bv) {
+#pragma unroll
+  for (int c = 0; c < DIM; ++c) acc += rv[c] * bv[c];
+  return acc;
+}
+
 template <int DIM>
 __global__ __launch_bounds__(64) void k_schur(int n_rows, const int32_t *__restrict__ srp, const int32_t *__restrict__ sci,
                                               const int32_t *__restrict__ brp, const int32_t *__restrict__ bci,
@@ -638,26 +647,72 @@ __global__ __launch_bounds__(64) void k_schur(int n_rows, const int32_t *__restr
     for (int p = brp[j]; p < brp[j + 1]; ++p) {
       const int k = bci[p];
       while (q < nb && rc[q] < k) ++q;
-      if (q < nb && rc[q] == k) {
-#pragma unroll
-        for (int c = 0; c < DIM; ++c) acc += rv[q * DIM + c] * bv[(size_t)p * DIM + c];
-      }
+      if (q < nb && rc[q] == k) acc = schur_term<DIM>(acc, rv + q * DIM, bv + (size_t)p * DIM);
     }
     sv[e] = acc;
   }
 }
 
+// The same product from the plan (host/schur_plan.hpp): which columns rows i and j share, and in which order they enter the sum, is a
+// constant of the mesh, so the merge above is done once on the host.  One wave per row i as before; a lane reads its packed terms
+// (position q in row i | offset in row j), 256 contiguous bytes per wave and step, and gathers only the entries of row j that
+// contribute.  Same operands in the same order through the same schur_term: sv comes out bit for bit, the exact 0.0 of an entry whose
+// terms are all masked included.  A lane without a term in a step (or without an entry) computes on (rv[0], bv[0]) and drops the result.
+template <int DIM>
+__global__ __launch_bounds__(64) void k_schur_planned(int n_rows, const int32_t *__restrict__ srp, const int32_t *__restrict__ sci,
+                                                      const int32_t *__restrict__ brp, const int32_t *__restrict__ bci,
+                                                      const double *__restrict__ bv, const double *__restrict__ w,
+                                                      const int32_t *__restrict__ row_grp, const int64_t *__restrict__ grp_off,
+                                                      const uint32_t *__restrict__ words, double *__restrict__ sv) {
+  extern __shared__ double smem[];
+  double *rv = smem;  // [max_row][DIM]
+  const int i = blockIdx.x;
+  if (i >= n_rows) return;
+  const int b0 = brp[i], nb = brp[i + 1] - b0;
+  for (int t = threadIdx.x; t < nb; t += 64) {
+    const int k = bci[b0 + t];
+#pragma unroll
+    for (int c = 0; c < DIM; ++c) rv[t * DIM + c] = bv[(size_t)(b0 + t) * DIM + c] * w[(size_t)k * DIM + c];
+  }
+  __syncthreads();
+  const int e1 = srp[i + 1], g1 = row_grp[i + 1];
+  int e = srp[i] + threadIdx.x;
+  for (int g = row_grp[i]; g < g1; ++g, e += 64) {
+    const int64_t o1 = grp_off[g + 1];
+    const bool live = e < e1;
+    const size_t pj = live ? (size_t)brp[sci[e]] : 0;
+    double acc = 0.0;
+#pragma unroll 4
+    for (int64_t o = grp_off[g] + threadIdx.x; o < o1; o += 64) {
+      const uint32_t word = __builtin_nontemporal_load(words + o);  // read once per product: the gathered rows of B are what should stay in cache
+      const bool term = word != SCHUR_NO_TERM;
+      const int q = term ? (int)(word >> 16) : 0;
+      const size_t p = term ? pj + (word & 0xffffu) : 0;
+      const double with = schur_term<DIM>(acc, rv + q * DIM, bv + p * DIM);
+      acc = term ? with : acc;
+    }
+    if (live) sv[e] = acc;
+  }
+}
+
 void schur_numeric(nsx_handle *h, const double *w) {
   comm_halo_u(h, w);  // weights of ghost velocity dofs
-  int max_row = 0;
-  const Csr &B = h->gB.host;
-  for (int i = 0; i < B.n_rows; ++i) max_row = std::max(max_row, B.rowptr[i + 1] - B.rowptr[i]);
-  const size_t shm = (size_t)max_row * (h->dim * 8 + 4) + 8;
+  ensure_schur_plan(h);  // (current since the first assembly: here it only hands over the longest row)
+  SchurPlanDev &pl = h->schur_plan;
+  const int max_row = pl.max_row;
+  // NSX_SCHUR_PLAN is read per call like its neighbours.  Handles of a distributed mesh or with a communicator stay on the merge kernel.
+  const bool planned = env_on("NSX_SCHUR_PLAN") && pl.ok && !h->dist && !h->comm;
+  const size_t shm = (size_t)max_row * (h->dim * 8 + (planned ? 0 : 4)) + 8;
   if (shm > 160 * 1024) NSX_THROW(NSX_ERR_UNSUPPORTED, "row of block(1,0) too long for the Schur kernel (%d)", max_row);
+  pl.used_last = planned;
   LaunchScope ls(h, "schur_numeric", 0);
   with_int<2, 3>(h->dim, [&](auto D) {
-    hipLaunchKernelGGL((k_schur<decltype(D)::value>), dim3(h->NP), dim3(64), shm, h->stream, h->NP, h->gS.rowptr.p, h->gS.colind.p, h->gB.rowptr.p,
-                       h->gB.colind.p, h->vB.p, w, max_row, h->vSchur.p);
+    if (planned)
+      hipLaunchKernelGGL((k_schur_planned<decltype(D)::value>), dim3(h->NP), dim3(64), shm, h->stream, h->NP, h->gS.rowptr.p, h->gS.colind.p, h->gB.rowptr.p,
+                         h->gB.colind.p, h->vB.p, w, pl.row_grp.p, pl.grp_off.p, pl.words.p, h->vSchur.p);
+    else
+      hipLaunchKernelGGL((k_schur<decltype(D)::value>), dim3(h->NP), dim3(64), shm, h->stream, h->NP, h->gS.rowptr.p, h->gS.colind.p, h->gB.rowptr.p,
+                         h->gB.colind.p, h->vB.p, w, max_row, h->vSchur.p);
   });
 }
 

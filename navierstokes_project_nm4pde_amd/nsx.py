@@ -22,7 +22,7 @@ API = [
     "nsx_set_rhs", "nsx_assemble", "nsx_assemble_time_step", "nsx_add_rhs", "nsx_apply_boundary_values",
     "nsx_solve_time_step", "nsx_prec_initialize", "nsx_prec_vmult", "nsx_system_vmult", "nsx_ilu_apply",
     "nsx_export_block", "nsx_schur_nnz", "nsx_schur_get", "nsx_scalar_graph_nnz", "nsx_scalar_graph", "nsx_ilu_get",
-    "nsx_profile_enable", "nsx_profile_reset", "nsx_profile_count", "nsx_profile_get", "nsx_persistent_state", "nsx_path_info", "nsx_ilu_path_info", "nsx_comm_self_halo_test", "nsx_comm_unique_id",
+    "nsx_profile_enable", "nsx_profile_reset", "nsx_profile_count", "nsx_profile_get", "nsx_persistent_state", "nsx_path_info", "nsx_ilu_path_info", "nsx_ilu_invert_staged", "nsx_schur_plan_info", "nsx_comm_self_halo_test", "nsx_comm_unique_id",
     "nsx_comm_init", "nsx_comm_init_callbacks", "nsx_comm_counters", "nsx_set_mesh_distributed", "nsx_set_force_faces", "nsx_compute_forces",
     "nsx_set_internal_layout", "nsx_layout_info", "nsx_layout_get", "nsx_gram_schmidt_cycle", "nsx_set_inner_precision",
     "nsx_gram_schmidt_sweeps", "nsx_compute_diagnostics", "nsx_get_cell_diagnostic", "nsx_schur_cg", "nsx_blas1_run", "nsx_gmres",
@@ -176,6 +176,8 @@ def lib():
     L.nsx_profile_get.argtypes = [vp, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), _f64p, _f64p]
     L.nsx_persistent_state.argtypes = [vp, C.POINTER(C.c_int)]
     L.nsx_ilu_path_info.argtypes = [vp, C.c_int, C.POINTER(C.c_int)]
+    L.nsx_ilu_invert_staged.argtypes = [vp, C.c_int, C.POINTER(C.c_int)]
+    L.nsx_schur_plan_info.argtypes = [vp, C.POINTER(C.c_longlong)]
     L.nsx_comm_unique_id.argtypes = [C.POINTER(C.c_uint8)]
     L.nsx_comm_init.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_uint8)]
     L.nsx_comm_init_callbacks.argtypes = [vp, C.c_int, C.c_int, ALLREDUCE_FN, EXCHANGE_FN, C.c_void_p]
@@ -357,6 +359,20 @@ class Nsx:
         d = {k: int(v[i]) for i, k in enumerate(self.ILU_PATH_KEYS)}
         d["factor"], d["invert"], d["solve"] = self.ILU_FACTOR[d["factor"]], self.ILU_INVERT[d["invert"]], self.ILU_SOLVE[d["solve"]]
         return d
+
+    def ilu_invert_staged(self, which):
+        """whether the last inversion in LDS on that schedule read the factor from its LDS copy (nsx_ilu_invert_staged)"""
+        v = C.c_int(0)
+        self._ck(self.L.nsx_ilu_invert_staged(self._h, int(which), C.byref(v)))
+        return bool(v.value)
+
+    SCHUR_PLAN_KEYS = ("planned", "used", "entries", "matches", "words", "bytes", "max_row", "build_us")
+
+    def schur_plan_info(self):
+        """dict: the plan of the Schur product and whether the last product ran the planned kernel (nsx_schur_plan_info)"""
+        v = (C.c_longlong * 8)()
+        self._ck(self.L.nsx_schur_plan_info(self._h, v))
+        return {k: int(v[i]) for i, k in enumerate(self.SCHUR_PLAN_KEYS)}
 
     def comm_counters(self):
         """(all-reduces, ghost exchanges) issued since the communicator was set"""
